@@ -9,11 +9,16 @@ weights of the SD-v1-4 architecture and synthetic text embeddings (no checkpoint
 Multi-GPU: one process per GPU (torch.distributed.run), prompts sharded round-robin, the frozen
 weights broadcast once from rank 0 over RCCL before the timed region; no communication inside it.
 
-Prints ONE JSON line on rank 0 (see the task contract) including
+Prints ONE JSON line on rank 0 (see the task contract). A plain run sets up, warms up, times --steps steps and reports
+the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step);
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs). --full adds, after the headline run,
   roofline     — the dominant cross-attention forward kernel: algorithmic bytes and flops / per-launch
                  time measured here with HIP events on the launch stream, against the 8 TB/s HBM3E and 2.5 PFLOP/s
-                 dense 16-bit MFMA peaks (the binding one is `bound`);
+                 dense 16-bit MFMA peaks (the binding one is `bound`), and the hostile_logits leg beside it;
+  side runs    — the other 16-bit type, BASELINE configs[3]'s per-GPU shard, configs[4] at 768x768, configs[2] (weight
+                 optimisation);
   cpu_baseline — the same workload through the CPU oracle (fp32 torch), on a bounded sample.
+The --no-* switches thin out what --full adds.
 """
 import argparse
 import json
@@ -47,12 +52,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure everything beside it: the roofline and hostile-logits legs, the side runs "
+                         "and the CPU baseline (each can be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy in float32 (see dump_outputs), for an output-by-output "
+                         "comparison of two builds; the inputs are seeded, identical from run to run for the same arguments")
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--ddim_steps", type=int, default=50)
     ap.add_argument("--objects", type=int, default=2)
     ap.add_argument("--images-per-step", type=int, default=None,
                     help="independent prompts sampled together per step (one CFG batch of 2I per UNet call); default 64 for "
-                         "fixed weights at 512^2 (one step = the 64 prompts of BASELINE configs[3]; +2.3 % images/s over 32 same box; 4 above "
+                         "fixed weights at 512^2 (one step = the 64 prompts of BASELINE configs[3]; +2.3 %% images/s over 32 same box; 4 above "
                          "512^2), 1 with --opt-epochs > 0")
     ap.add_argument("--no-graph", action="store_true", help="issue the UNet eagerly instead of replaying a hipGraph")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -93,6 +104,8 @@ def parse():
                     help="weight-optimisation epochs (0 = fixed weights = BASELINE configs[1], the headline; 3 = configs[2] "
                          "with a CLIP stand-in loss, reported as a side measurement)")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1 (the timed region is --steps steps)")
     if a.scaling == "strong":
         world = int(os.environ.get("WORLD_SIZE", "1"))
         if 64 % world:
@@ -598,6 +611,34 @@ def side_run(dev, dtype_name, opt_epochs, images, steps, warmup, res, ddim_steps
     return out
 
 
+DUMP_SAMPLE = 4 << 20      # elements kept of an output larger than this (16 MB in float32; the bench's image is 50 M values)
+
+
+def dump_outputs(path, result):
+    """--dump-outputs: what a caller of the timed path receives from its last step (sampler.last_result of rank 0) as
+    <path>/<name>.npy in float32: `x0` (the final latents, full), `W` (the blend weights, full), `losses` (weight optimisation
+    only) and `image_sample` — the decoded, clamped images are larger than DUMP_SAMPLE, so they are stored as a fixed sample:
+    the values at DUMP_SAMPLE indices of the flattened [I, 3, H, W] array drawn (sorted, with repetition) from a CPU generator
+    seeded with 0, the same indices in every run with the same arguments. The inputs are seeded too, but the sampling path is not
+    bitwise deterministic: two runs of one build on one MI355X agreed in W exactly and in x0 to 2.5e-3 of max|x0| (1.9e-3 in the
+    mean), so two builds compare within such a tolerance. -> {file name: shape}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name in ("x0", "W", "image", "losses"):
+        val = result.get(name)
+        if val is None:
+            continue
+        t = torch.as_tensor(val).detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        arr = t.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        written[name + ".npy"] = list(arr.shape)
+    return written
+
+
 _T0 = time.perf_counter()
 
 
@@ -775,6 +816,8 @@ def main():
     peak_gb = torch.cuda.max_memory_allocated() / 2 ** 30
     if rank != 0:
         return
+    if a.dump_outputs:
+        _phase("outputs of the last timed step written: %s" % dump_outputs(a.dump_outputs, r))
     out = {
         "metric": "images/sec at 512x512, 50 PLMS steps, 2 objects", "value": world * a.steps * I / elapsed, "unit": "images/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
@@ -796,6 +839,9 @@ def main():
     # to the standard softmax, launches that sat the optimistic path out — the level-0 roofline figure belongs to the optimistic path
     # only if fallbacks and launches_sat_out are (near) 0; `hostile_logits` beside `roofline` shows the other regime
     out["config"]["xattn_optimistic"] = _ops.proj_stats_summary()
+    if not a.full:          # a plain run ends with the headline line: what follows is measured under --full only
+        print(json.dumps(out))
+        return
     if not a.no_roofline:
         out["roofline"] = roofline_leg(model, dev, dt, a.dtype, I, K, lat, prompts[mine(0)[0]], centres)
     if not a.no_roofline and a.opt_epochs > 1 and K > 0:

@@ -149,3 +149,24 @@ def test_bench_strong_scaling_split_and_world_mismatch():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     bad = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--dry-launch"], env=env, capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "WORLD_SIZE=1" in bad.stderr and not [ln for ln in bad.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, at most 64 MB in all at the bench's own sizes (64 images of 512 x 512), the
+    image as a fixed sample (the same values for the same result in every run), and a timed region of at least one step."""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(3)
+    res = {"x0": torch.randn(64, 4, 64, 64, generator=g).half(), "image": torch.rand(64, 3, 512, 512, generator=g).half(),
+           "W": torch.full((64, 2, 50), 2.5), "losses": None}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), res)
+    bench.dump_outputs(str(tmp_path / "b"), res)
+    assert shapes == {"x0.npy": [64, 4, 64, 64], "W.npy": [64, 2, 50], "image_sample.npy": [bench.DUMP_SAMPLE]}
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in shapes) <= 64 << 20
+    for f in shapes:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "x0.npy"), res["x0"].float().numpy())
+    assert np.isin(np.load(tmp_path / "a" / "image_sample.npy"), res["image"].float().numpy().ravel()).all()
+    r, lines = _run_bench("--steps", "0")
+    assert r.returncode != 0 and not lines and "--steps must be at least 1" in r.stderr

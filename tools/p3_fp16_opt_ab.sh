@@ -1,7 +1,7 @@
 # level 0 in fp16: the optimistic softmax (product build) against -DSTA_P3_OPTIMISTIC=0, the headline workload + its in-situ roofline leg, same box
 # (build/ab/libsta_{opt,std}.so are built beforehand, GPU-less: AB_ROUNDS=0 python tools/lib_ab.py bench.py --steps 1 -- opt= std=-DSTA_P3_OPTIMISTIC=0)
 cd $GRAFT_REPO_ROOT
-AB_ROUNDS=2 python tools/lib_ab.py bench.py --steps 1 --warmup 1 --no-side-runs --no-cpu-baseline -- opt= std=-DSTA_P3_OPTIMISTIC=0 2>/dev/null | python -c "
+AB_ROUNDS=2 python tools/lib_ab.py bench.py --full --steps 1 --warmup 1 --no-side-runs --no-cpu-baseline -- opt= std=-DSTA_P3_OPTIMISTIC=0 2>/dev/null | python -c "
 import json, sys
 for line in sys.stdin:
     tag, _, rest = line.partition('] ')

@@ -3,6 +3,7 @@
 #   gpurun_out/prof_$1_kernel_stats.csv, prof_$1_breakdown.txt, prof_$1_bench.json   (copy to profiles/ as $1_*)
 # usage (GPU box, repo root): bash tools/profile_bench.sh r02 [extra bench.py args]
 tag=${1:-r02}; shift
+set -- --full "$@"      # the roofline leg the trace is read against runs under bench.py --full
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_$tag
