@@ -27,6 +27,7 @@ from torch import nn
 from ldm.modules.diffusionmodules.util import checkpoint, zero_module, Normalize
 from sta import fused as _fused
 from sta import ops as _ops
+from sta.mxfp8 import MxFp8Linear
 from sta import prompt_state as _ps
 
 
@@ -36,6 +37,8 @@ class GEGLU(nn.Module):
         self.proj = nn.Linear(dim_in, dim_out * 2)
 
     def forward(self, x):
+        if isinstance(self.proj, MxFp8Linear):
+            return self.proj.forward_geglu(x)         # projection + gelu + mul as ONE MXFP8 GEMM (csrc/sta_mxfp8.hip)
         h = self.proj(x)
         if _fused.usable(h):
             return _fused.geglu(h)                     # chunk + gelu + mul in one pass (csrc/sta_unet.hip)
@@ -54,7 +57,12 @@ class FeedForward(nn.Module):
         self.net = nn.Sequential(first, nn.Dropout(dropout), nn.Linear(inner, dim_out))
 
     def forward(self, x):
-        return self.net(x)
+        net = self.net
+        if isinstance(net[0], GEGLU) and isinstance(net[0].proj, MxFp8Linear) and isinstance(net[2], MxFp8Linear):
+            # MXFP8 (sta.mxfp8): the GEGLU GEMM writes h as MXFP8 and the output Linear reads it as it is — no quantiser pass
+            # between them (net[1] is the inference-time identity Dropout)
+            return net[2](net[0].proj.forward_geglu(x, mx_out=True), out_dtype=x.dtype)
+        return net(x)
 
 
 class CrossAttention(nn.Module):
@@ -125,6 +133,8 @@ class CrossAttention(nn.Module):
         transposed because the PV product wants keys contiguous per channel: ONE plain GEMM W_v . X^T over the
         flattened batch gives [C, B*N], which the kernel reads through (row, batch) strides. (A batched
         `matmul(W_v, x^T)` with the weight broadcast over the batch faults inside the GEMM library from batch 40 up.)"""
+        if isinstance(self.to_q, MxFp8Linear):
+            return self._self_attention_hip_mx(x)
         if not isinstance(self.to_q, nn.Linear):
             return self._self_attention_hip_fp8(x)
         wq, wk = self.to_q.weight, self.to_k.weight
@@ -154,6 +164,23 @@ class CrossAttention(nn.Module):
         xq, sx = _fp8.quant_rows(x.reshape(b * n, c))
         qk = _fp8.scaled_mm(xq, self._wqk8.weight_q.t(), sx, self._wqk8.weight_scale, None, x.dtype).view(b, n, 2 * c)
         vt = self.to_v.forward_transposed(xq, sx, x.dtype).view(c, b, n).permute(1, 0, 2)
+        o = _ops.self_attention(qk[..., :c], qk[..., c:], vt, self.heads, _ops.LN2)
+        return self.to_out(o)
+
+    def _self_attention_hip_mx(self, x):
+        """The same with MXFP8 weights (sta.mxfp8): x is quantised ONCE per call (sta_mx8_quant_rows) and feeds both GEMMs —
+        [Wq; Wk] with softmax scale * log2(e) applied to q's fp32 accumulators (col_scale), and W_v . x^T with the operands swapped."""
+        from sta import mxfp8 as _mx
+        if getattr(self, "_wqk_mx", None) is None or self._wqk_mx_src is not self.to_q.weight_q:
+            c = self.to_q.out_features
+            self._wqk_mx = (torch.cat([self.to_q.weight_q, self.to_k.weight_q]), torch.cat([self.to_q.weight_scale, self.to_k.weight_scale]),
+                            torch.cat([torch.full((c,), self.scale * 1.4426950408889634), torch.ones(c)]).to(x.device))
+            self._wqk_mx_src = self.to_q.weight_q
+        b, n, c = x.shape
+        xq, xs = _mx.quant_rows_mx(x.reshape(b * n, c))
+        wq, ws, col_scale = self._wqk_mx
+        qk = _mx.gemm(xq, xs, wq, ws, x.dtype, col_scale=col_scale).view(b, n, 2 * c)
+        vt = self.to_v.forward_transposed((xq, xs), out_dtype=x.dtype).view(c, b, n).permute(1, 0, 2)
         o = _ops.self_attention(qk[..., :c], qk[..., c:], vt, self.heads, _ops.LN2)
         return self.to_out(o)
 

@@ -64,6 +64,10 @@ def build_parser(default_dataset):
                         "the weight memory; their GEMMs become hipBLASLt's row-scaled e4m3 GEMMs behind a per-row activation quantiser, "
                         "which measures SLOWER than 16 bit here (a memory option, not a rate option: DESIGN.md section 5); fixed blend "
                         "weights only (--opt_epochs 0)")
+    p.add_argument("--mxfp8", action="store_true",
+                   help="store the same Linear weights as OCP MXFP8 (e4m3 elements, one e8m0 scale per 32 inputs) and run their GEMMs on "
+                        "this project's block-scaled fp8 MFMA kernel (csrc/sta_mxfp8.hip; sta.mxfp8); exclusive with --fp8; fixed blend "
+                        "weights only (--opt_epochs 0)")
     p.add_argument("--clip_tokenizer", type=str, default=None, help="directory with the CLIP tokenizer files (with --ckpt)")
     p.add_argument("--synthetic", action="store_true", help="synthetic weights/text embeddings when no checkpoint is available")
     p.add_argument("--batch_prompts", type=int, default=1,
@@ -71,8 +75,17 @@ def build_parser(default_dataset):
     return p
 
 
+def check_options(opt):
+    """Refusals that need no GPU (raised before anything is built)."""
+    if opt.mxfp8 and opt.fp8:
+        raise SystemExit("--mxfp8 and --fp8 are exclusive")
+    if opt.mxfp8 and opt.opt_epochs > 0:
+        raise SystemExit("--mxfp8 is an inference option: use --opt_epochs 0")
+
+
 def run(kind, default_dataset):
     opt = build_parser(default_dataset).parse_args()
+    check_options(opt)
     if not opt.plms:
         raise SystemExit("only --plms works with the spatial-temporal UNet (DDIM/DPM-Solver call apply_model with the "
                          "wrong positional arguments in the reference, ddim.py:172-177 vs ddpm.py:1420)")
@@ -118,6 +131,10 @@ def run(kind, default_dataset):
         from sta import fp8
         n, before, after = fp8.convert_transformer_linears_(model.model.diffusion_model)
         print("[rank %d] %d Linear layers -> e4m3: %.2f GB -> %.2f GB" % (rank, n, before / 1e9, after / 1e9))
+    if opt.mxfp8:
+        from sta import mxfp8
+        n, before, after = mxfp8.convert_transformer_linears_mx_(model.model.diffusion_model)
+        print("[rank %d] %d Linear layers -> MXFP8: %.2f GB -> %.2f GB" % (rank, n, before / 1e9, after / 1e9))
     sampler = PLMSSampler(model, opt_epochs=opt.opt_epochs, loss_model=loss_model)
     os.makedirs(opt.outdir, exist_ok=True)
 

@@ -41,7 +41,7 @@ from collections import namedtuple
 Finding = namedtuple("Finding", "kernel line rule producer consumer have need")
 
 # MFMA mnemonic -> (passes, registers of D)
-_MFMA_RE = re.compile(r"^v_mfma_(?:f32|i32|f64)_(\d+)x(\d+)x(\d+)")
+_MFMA_RE = re.compile(r"^v_mfma_(?:scale_)?(?:f32|i32|f64)_(\d+)x(\d+)x(\d+)")
 _TRANS = ("v_rcp_", "v_rsq_", "v_sqrt_", "v_exp_", "v_log_", "v_sin_", "v_cos_", "v_rcp_iflag")
 MAX_WINDOW = 13
 # round 6 (profiles/r06_bwd_race.md): an optional rule — wait states between an MFMA and an LDS / vector-memory load whose DESTINATION
@@ -57,7 +57,11 @@ def _mfma_info(mn):
         return None
     M, N, Kd = int(m.group(1)), int(m.group(2)), int(m.group(3))
     flops = M * N * Kd
-    if "f8f6f4" in mn or "fp8" in mn or "bf8" in mn:
+    if mn.startswith("v_mfma_scale_"):
+        # block-scaled f8f6f4 (MXFP8 in csrc/sta_mxfp8.hip): with e4m3 operands twice the cycles of the bf16 form of the same M x N
+        # (MI355X_MICROARCH matrix-core table); fp6 / fp4 operands take fewer, so the e4m3 count is the conservative one
+        passes = 16 if M == 32 else 8
+    elif "f8f6f4" in mn or "fp8" in mn or "bf8" in mn:
         passes = 8 if (M == 16 and Kd >= 128) or (M == 32 and Kd >= 64) else 4
     elif M == 32:
         passes = 8 if Kd >= 8 else 16
@@ -126,6 +130,9 @@ class Ins:
             self.defs = regs[0] or set()
             self.a, self.b, self.c = regs[1] or set(), regs[2] or set(), (regs[3] or set()) if len(regs) > 3 else set()
             self.uses = self.a | self.b | self.c
+            for r in regs[4:6]:          # v_mfma_scale_*: the A and B scale VGPRs
+                if r:
+                    self.uses |= r
         elif mn.startswith(("v_permlane16_swap", "v_permlane32_swap", "v_swap_b32")):
             for r in regs[:2]:
                 if r:

@@ -177,6 +177,27 @@ int sta_add_bias_rows(const void* a, const void* b, const void* bias, void* y, l
 int sta_quant_rows_fp8(const void* x, void* xq, float* scale, long rows, int C, int dtype, void* stream);
 
 /*
+ * MXFP8 (OCP MX v1.0: e4m3fn elements, one e8m0 scale byte per 32 consecutive K elements) for the transformer-block Linears on
+ * gfx950's block-scaled MFMA (v_mfma_scale_f32_32x32x64_f8f6f4: twice the 16-bit rate). csrc/sta_mxfp8.hip.
+ *
+ * sta_mx8_quant_rows: x [rows][K] dtype -> xq [rows][K] e4m3fn bytes, xs [rows][K/32] e8m0 bytes (both plain row-major); K % 32 == 0,
+ *   x and xq 16-byte aligned. Per 32-block: X = 2^clamp(floor(log2 amax) - 8, -127, 127), xq = e4m3fn(x / X) rounded to nearest even
+ *   and saturated to +-448, xs = log2 X + 127. An all-zero block: codes 0, scale byte 127 (X = 1).
+ * sta_mx8_gemm: out[m][n] = sum_k P[m][k] 2^(ps[m][k/32] - 127) * Q[n][k] 2^(qs[n][k/32] - 127), fp32 accumulation.
+ *   P [M][K], Q [N][K] e4m3fn (16-byte aligned), ps [M][K/32], qs [N][K/32] e8m0; K % 32 == 0 (K % 64 == 32 runs a zero half-step).
+ *   flags 0: out [M][ldo] dtype, out[m][n] = acc * col_scale[n] + bias[n] (col_scale fp32 [N], bias dtype [N]; either may be NULL).
+ *   flags STA_MX8_GEGLU: Q holds the GEGLU projection packed in groups of 64 rows (32 value rows h .. h+31, then the gate rows
+ *     H + h .. H + h + 31; H = N / 2, N % 64 == 0) and bias [N] packed the same way; out [M][ldo] dtype with
+ *     out[m][h] = value * gelu_erf(gate) (reference attention.py:47-49), ldo % 4 == 0.
+ *   flags STA_MX8_GEGLU | STA_MX8_MX_OUT: the same result as MXFP8 — out [M][H] e4m3fn bytes, out_scale [M][H/32] e8m0 (ldo == H),
+ *     quantised from the 16-bit-rounded GEGLU values by the sta_mx8_quant_rows rule (same scales; codes bit-identical in bf16).
+ */
+enum { STA_MX8_GEGLU = 1, STA_MX8_MX_OUT = 2 };
+int sta_mx8_quant_rows(const void* x, void* xq, void* xs, long rows, int K, int dtype, void* stream);
+int sta_mx8_gemm(const void* p, const void* ps, const void* q, const void* qs, void* out, void* out_scale, const void* bias,
+                 const float* col_scale, long M, int N, int K, long ldo, int flags, int dtype, void* stream);
+
+/*
  * Input gradients of the glue kernels, for the tracked (weight-optimisation) epochs (plms.py:220-277): the blend weights
  * are the only leaf and every model parameter is frozen, so each op needs d(input) only. csrc/sta_unet_bwd.hip.
  *
