@@ -243,9 +243,8 @@ class PLMSSampler(object):
             assert len(boxes) == len(names) == b and all(len(bx) == len(nm) for bx, nm in zip(boxes, names))
         K = len(boxes[0])
         assert all(len(bx) == K for bx in boxes), "images of a batch must have the same number of objects"
-        timesteps = self.ddim_timesteps
-        S = timesteps.shape[0]
-        time_range = np.flip(timesteps)
+        time_range = self._time_range()          # the model times of the trajectory's UNet calls, one column of W each
+        S = len(time_range)
         img_input = (torch.randn(shape, device=device) if x_T is None else x_T.to(device)).clone()
 
         # tell the 16 blocks a new prompt (batch) starts (replaces the `time == 981` test + cwd files)
@@ -330,6 +329,9 @@ class PLMSSampler(object):
         Image.fromarray(arr).save(os.path.join(self.outdir, "final%d_s%d_index_%d.png" % (epoch, seed, prompt_idx)))
 
     # --------------------------------------------------------------------------------------------------
+    def _time_range(self):
+        return np.flip(self.ddim_timesteps)
+
     def _trajectory(self, img, cond, uncond, scale, time_range, W, bboxs_curr, text_index, graph=False, call_recompute=False):
         """W: [K, S] for one image or [I, K, S] for a batch; column i of every image is used at step i."""
         S, b, device = len(time_range), img.shape[0], img.device
@@ -366,10 +368,13 @@ class PLMSSampler(object):
         free += torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
         return int(max(0, min(n_calls, (free - 4 * est - (24 << 30)) // max(est, 1))))
 
-    def _make_eps_fn(self, cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute=False, keep_last=0, n_calls=0):
+    def _make_eps_fn(self, cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute=False, keep_last=0, n_calls=0,
+                     raw=False):
         """eps(x, t, coef) with classifier-free guidance. The UNet batch is [uncond_0, cond_0, uncond_1, cond_1, ...]:
         for one image this is the reference's `cat([uc, c])` (:304-308); for a batch the pairs stay adjacent,
-        which is the layout the fused kernel indexes (image-major, row 0 = uncond, row 1 = cond)."""
+        which is the layout the fused kernel indexes (image-major, row 0 = uncond, row 1 = cond).
+        raw=True (the step-kernel samplers, SolverSamplerBase): returns the UNet's [2b] output itself, and x may already be
+        that batch's input pair [2b] (sta_sampler_step writes it in the UNet's dtype)."""
         if uncond is None or scale == 1.0:
             raise ValueError("the spatial-temporal path needs classifier-free guidance (scale != 1, uc given): "
                              "the blend subtracts the unconditional row (attention.py:290)")
@@ -385,7 +390,7 @@ class PLMSSampler(object):
             apply_fn = self._graphs.bind(c_in, bboxs_curr, text_index)
 
         def unet(fn, x, t, coef):
-            return fn(pair(x, x), text_index, pair(t, t), c_in, coef=coef, bboxs_curr=bboxs_curr)
+            return fn(x if x.shape[0] == 2 * b else pair(x, x), text_index, pair(t, t), c_in, coef=coef, bboxs_curr=bboxs_curr)
 
         calls = [0]
 
@@ -404,6 +409,8 @@ class PLMSSampler(object):
                                            lambda x_, t_, c_: unet(self.model.apply_model_extra, x_, t_, c_), t, x, coef)
             else:
                 out = unet(apply_fn, x, t, coef)
+            if raw:
+                return out
             out = out.reshape(b, 2, *out.shape[1:])
             e_u, e_c = out[:, 0], out[:, 1]
             return e_u + scale * (e_c - e_u)
@@ -442,3 +449,45 @@ class PLMSSampler(object):
         eps_fn = self._make_eps_fn(c, unconditional_conditioning, unconditional_guidance_scale,
                                    [] if bboxs_curr is None else bboxs_curr, text_index, False, x)
         return self._plms_update(eps_fn, x, t, t_next, index, [] if old_eps is None else old_eps, coef)
+
+
+class SolverSamplerBase(PLMSSampler):
+    """The epoch loop, weights and keyword surface of PLMSSampler around a trajectory of exactly S UNet calls whose per-call
+    arithmetic is one sta_sampler_step launch (sta.solver): DPMSolverSampler (dpm_solver/sampler.py) and DDIMSampler (ddim.py).
+    Call i uses column i of W[K, S]. With fixed weights on the GPU the kernel also writes the next call's 16-bit input pair, so
+    nothing but the (graph-replayed) UNet call and that one launch runs per step; tracked epochs differentiate through
+    sta.solver.SolverStepFn (backward = sta_sampler_step_bwd), per-call recomputation included."""
+    t_dtype = torch.float32
+    tables = None
+
+    def _time_range(self):
+        return self.tables["t_in"]
+
+    def _coef(self, i, scale):
+        raise NotImplementedError
+
+    def _noise(self, i, x):
+        return None
+
+    def _trajectory(self, img, cond, uncond, scale, time_range, W, bboxs_curr, text_index, graph=False, call_recompute=False):
+        from sta import solver
+        S, b, device = len(time_range), img.shape[0], img.device
+        self._call_key = (tuple(img.shape[1:]), int(W.shape[-2]))
+        grad = torch.is_grad_enabled()
+        keep = self._calls_to_keep(S, b) if call_recompute and grad else 0
+        if call_recompute and grad:
+            self.last_kept_calls = keep
+        eps_fn = self._make_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute, keep_last=keep, n_calls=S,
+                                   raw=True)
+        wdtype = next(self.model.model.parameters()).dtype
+        fast = img.is_cuda and not grad
+        x, m_prev = img, None
+        xin = solver._pair(img).to(wdtype) if fast else None
+        for i in range(S):
+            t_val = float(time_range[i]) if self.t_dtype.is_floating_point else int(time_range[i])
+            t = torch.full((b,), t_val, device=device, dtype=self.t_dtype)
+            out = eps_fn(x if xin is None else xin, t, W[..., i])
+            c = self._coef(i, scale)
+            noise = self._noise(i, x) if c.c_n else None
+            x, m_prev, xin = solver.solver_step(out, x, m_prev, noise, c, dtype=wdtype, want_xin=fast and i + 1 < S)
+        return x

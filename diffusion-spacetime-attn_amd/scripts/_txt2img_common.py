@@ -1,7 +1,7 @@
 """Shared body of scripts/txt2img-{gpt,mscoco,vsr}.py — the reference's three entry points differ only
 in the dataset they read (scripts/txt2img-gpt.py vs -mscoco.py vs -vsr.py: lines 255-261).
 
-Kept from the reference CLI (txt2img-gpt.py:105-247): --plms --ddim_steps --H --W --C --f --n_samples --scale
+Kept from the reference CLI (txt2img-gpt.py:105-247): --plms / --dpm_solver / neither (DDIM; sampler_choice) --ddim_steps --H --W --C --f --n_samples --scale
 --ddim_eta --fixed_code --config --ckpt --precision --outdir --seed --process_id (+ the flags it parses and
 ignores, accepted for compatibility). Added: --layout (JSON replacing the layout-predictor call),
 --dataset (path override), --opt_epochs (0 = fixed weights), --limit/--start, --dtype, --synthetic,
@@ -83,15 +83,33 @@ def check_options(opt):
         raise SystemExit("--mxfp8 is an inference option: use --opt_epochs 0")
 
 
+def sampler_choice(opt):
+    """(sampler class name, eta) as the reference picks them (txt2img-gpt.py:268-273): --dpm_solver -> DPM-Solver++ (order 2,
+    multistep; --ddim_eta ignored), else --plms -> PLMS, else DDIM with --ddim_eta."""
+    if opt.dpm_solver:
+        return "DPMSolverSampler", 0.0
+    if opt.plms:
+        return "PLMSSampler", opt.ddim_eta
+    return "DDIMSampler", opt.ddim_eta
+
+
+def sampler_class(name):
+    if name == "DPMSolverSampler":
+        from ldm.models.diffusion.dpm_solver.sampler import DPMSolverSampler
+        return DPMSolverSampler
+    if name == "DDIMSampler":
+        from ldm.models.diffusion.ddim import DDIMSampler
+        return DDIMSampler
+    from ldm.models.diffusion.plms import PLMSSampler
+    return PLMSSampler
+
+
 def run(kind, default_dataset):
     opt = build_parser(default_dataset).parse_args()
     check_options(opt)
-    if not opt.plms:
-        raise SystemExit("only --plms works with the spatial-temporal UNet (DDIM/DPM-Solver call apply_model with the "
-                         "wrong positional arguments in the reference, ddim.py:172-177 vs ddpm.py:1420)")
+    sampler_name, eta = sampler_choice(opt)
     if opt.n_samples != 1:
         raise SystemExit("--n_samples must be 1 (the blocks reshape to the CFG batch of 2, attention.py:282)")
-    from ldm.models.diffusion.plms import PLMSSampler
     from sta import datasets, parallel
     from sta.pipeline import build_sd_v1, conditionings, use_shipped_miopen_db
 
@@ -135,7 +153,7 @@ def run(kind, default_dataset):
         from sta import mxfp8
         n, before, after = mxfp8.convert_transformer_linears_mx_(model.model.diffusion_model)
         print("[rank %d] %d Linear layers -> MXFP8: %.2f GB -> %.2f GB" % (rank, n, before / 1e9, after / 1e9))
-    sampler = PLMSSampler(model, opt_epochs=opt.opt_epochs, loss_model=loss_model)
+    sampler = sampler_class(sampler_name)(model, opt_epochs=opt.opt_epochs, loss_model=loss_model)
     os.makedirs(opt.outdir, exist_ok=True)
 
     seed = 1                                                            # txt2img-gpt.py:304
@@ -150,7 +168,7 @@ def run(kind, default_dataset):
         uc, c, local_c = conditionings(model, prompt, names, dtype)
         x_T = torch.randn([opt.n_samples, *shape], device=dev) if opt.fixed_code else None
         sampler.sample(S=opt.ddim_steps, conditioning=c, batch_size=opt.n_samples, shape=shape, verbose=False,
-                       unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, eta=opt.ddim_eta, x_T=x_T,
+                       unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, eta=eta, x_T=x_T,
                        text_index=0, curr_text=prompt, bboxs_curr=[layout[n] for n in names], seed=seed,
                        prompt_idx=prompt_idx, object_names=names, local_conditionings=local_c)
 
@@ -165,7 +183,7 @@ def run(kind, default_dataset):
                              unconditional_conditionings=[c[0] for c in conds],
                              bboxs=[[l[n] for n in l] for _, _, l in group], object_names=[list(l.keys()) for _, _, l in group],
                              local_conditionings=[c[2] for c in conds], curr_texts=[p for _, p, _ in group],
-                             x_T=x1.expand(len(group), -1, -1, -1), unconditional_guidance_scale=opt.scale, eta=opt.ddim_eta,
+                             x_T=x1.expand(len(group), -1, -1, -1), unconditional_guidance_scale=opt.scale, eta=eta,
                              seed=seed, prompt_indices=[i for i, _, _ in group])
 
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}) for i, p in mine]

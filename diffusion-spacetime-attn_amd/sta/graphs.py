@@ -8,7 +8,8 @@ What makes the capture reusable across prompts: nothing per-prompt is baked into
 ADDRESSES. The per-prompt data — packed K/V images, disc masks — live in buffers that each
 transformer block allocates once per shape and refills in place (BasicTransformerBlock.prepare_prompt);
 the per-step data — latent, timestep, weights column — are copied into static input tensors before
-each replay.
+each replay. One capture per (input shape, input dtype, timestep dtype, object count): PLMS calls with integer timesteps and a
+float32 latent pair, DDIM (integer) and DPM-Solver++ (fractional float32 timesteps) with the 16-bit pair sta_sampler_step writes.
 """
 import torch
 
@@ -37,7 +38,9 @@ class GraphedEps:
         boxes = [list(map(list, c)) for c in centres] if n_img > 1 else [list(b) for b in centres[0]]
 
         def apply(x_in, text_index_, t_in, c_in_, coef=None, bboxs_curr=None):
-            key = (tuple(x_in.shape), x_in.dtype, K)
+            # the timestep dtype is part of the key: a capture with PLMS's / DDIM's integer timesteps would truncate DPM-Solver's
+            # fractional model times (949.05 -> 949) in ent.t.copy_
+            key = (tuple(x_in.shape), x_in.dtype, t_in.dtype, K)
             ent = self._entries.get(key)
             if ent is None:
                 ent = self._capture(key, x_in, t_in, c_in, coef, boxes, K, text_index)

@@ -216,6 +216,27 @@ int sta_geglu_bwd(const void* x, const void* dy, void* dx, long R, int D, int dt
 int sta_layernorm_bwd(const void* s, const void* gamma, const void* dy, const void* dres, void* ds, long R, int C, float eps,
                       int dtype, void* stream);
 
+/*
+ * One step of the DPM-Solver++(2M) / DDIM samplers after a CFG UNet call, in one pass (csrc/sta_sampler.hip):
+ *     e      = eps[2i] + scale (eps[2i+1] - eps[2i])         guided noise (dpm_solver.py:345-346, ddim.py:176-177)
+ *     m      = (x - sigma_t e) / alpha_t                      data prediction at the call's time (dpm_solver.py:393, ddim.py:190)
+ *     x_next = c_x x + c_m m + c_p m_prev + c_e e + c_n noise
+ * DPM-Solver++ multistep, order 2 (dpm_solver.py:755-790, predict_x0, solver_type "dpm_solver"):
+ *     c_x = sigma_next / sigma_t, c_m = -alpha_next (e^-h - 1)(1 + 1/(2 r0)), c_p = alpha_next (e^-h - 1)/(2 r0), c_e = c_n = 0;
+ *     first-order steps (dpm_solver.py:525-530) have c_p = 0.
+ * DDIM (ddim.py:180-205): c_m = sqrt(a_prev), c_e = sqrt(1 - a_prev - sigma^2), c_n = sigma, c_x = c_p = 0.
+ *   eps: [2b][n] dtype, uncond / cond rows adjacent per image;  x, m_prev, noise, x_next, m: [b][n] fp32 (m_prev / noise may be NULL
+ *   when their coefficient is 0);  xin: NULL, or [2b][n] dtype = (x_next, x_next) per image, the next UNet call's input.
+ *   n % 8 == 0; every pointer 16-byte aligned; outputs may not alias inputs.
+ * sta_sampler_step_bwd: the step is linear in (eps, x, m_prev). Given g_xn = dL/dx_next and g_m = dL/dm (NULL = 0), writes
+ *   g_x = dL/dx [b][n] fp32, g_eps = dL/deps [2b][n] dtype, g_mprev = dL/dm_prev [b][n] fp32 (NULL = not written). No noise gradient.
+ */
+int sta_sampler_step(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin,
+                     long b, long n, float scale, float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n,
+                     int dtype, void* stream);
+int sta_sampler_step_bwd(const float* g_xn, const float* g_m, float* g_x, void* g_eps, float* g_mprev, long b, long n, float scale,
+                         float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
