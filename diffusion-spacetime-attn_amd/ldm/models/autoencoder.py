@@ -1,8 +1,11 @@
-"""KL-VAE decoder of SD-v1 (first_stage_model) — the image end of the loss path
-(reference ldm/models/autoencoder.py:330-333, ldm/modules/diffusionmodules/model.py:462-560).
-Stays on PyTorch-ROCm/MIOpen; parameter names follow the SD-v1-4 state_dict
-(`first_stage_model.post_quant_conv`, `first_stage_model.decoder.*`). Encoder is not needed for
-text-to-image sampling and is not provided."""
+"""KL-VAE of SD-v1 (first_stage_model): the decoder — the image end of the loss path (reference
+ldm/models/autoencoder.py:330-333, ldm/modules/diffusionmodules/model.py:462-560) — and, for img2img, the encoder
+(model.py:368-459, autoencoder.py:324-328) with the posterior (ldm/modules/distributions/distributions.py:24-37).
+Parameter names follow the SD-v1-4 state_dict (`first_stage_model.post_quant_conv`, `first_stage_model.decoder.*`,
+`first_stage_model.encoder.*`, `first_stage_model.quant_conv`). The encoder is built only when asked
+(`AutoencoderKL.add_encoder`, sta.pipeline.build_sd_v1(with_encoder=True)): text-to-image never runs it. On an NHWC
+16-bit encoder outside autograd its 3x3 convolutions run on csrc/sta_conv.hip and its Downsample convolutions on
+csrc/sta_encode.hip; conv_in (3 channels in) and conv_out (8 out) stay library convolutions."""
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -143,15 +146,124 @@ class Decoder(nn.Module):
         return self.conv_out(_norm_silu(self.norm_out, h))
 
 
+class Downsample(nn.Module):
+    """F.pad(x, (0, 1, 0, 1)) + 3x3 convolution with stride 2 (reference model.py:60-79). NHWC 16-bit outside autograd: one
+    sta_conv3x3_s2_nhwc launch that reads the pad as zeros (no padded copy) and leaves the next GroupNorm's statistics."""
+
+    def __init__(self, channels):
+        super().__init__()
+        self.conv = nn.Conv2d(channels, channels, 3, stride=2, padding=0)
+
+    def forward(self, x):
+        if _fused.conv3x3_s2_supported(x, self.conv.weight):
+            return _fused.conv3x3_s2_nhwc(x, _fused.packed_conv_weight(self, self.conv), self.conv.weight.shape[0], bias=self.conv.bias,
+                                          stats=_fused.GN_STATS_FROM_PRODUCER)
+        return self.conv(F.pad(x, (0, 1, 0, 1), mode="constant", value=0))
+
+
+class Encoder(nn.Module):
+    """The SD-v1 encoder (reference model.py:368-459) without timestep embedding, dropout or per-level attention (v1-inference.yaml:
+    attn_resolutions = [])."""
+
+    def __init__(self, *, ch=128, out_ch=3, ch_mult=(1, 2, 4, 4), num_res_blocks=2, attn_resolutions=(), dropout=0.0,
+                 in_channels=3, resolution=256, z_channels=4, double_z=True, **ignored):
+        super().__init__()
+        if attn_resolutions:
+            raise NotImplementedError("SD-v1 encoder has no per-level attention")
+        self.num_resolutions, self.num_res_blocks = len(ch_mult), num_res_blocks
+        self.conv_in = nn.Conv2d(in_channels, ch, 3, padding=1)
+        in_ch_mult = (1,) + tuple(ch_mult)
+        self.down = nn.ModuleList()
+        block_in = ch
+        for i_level in range(self.num_resolutions):
+            lvl = nn.Module()
+            lvl.block = nn.ModuleList()
+            lvl.attn = nn.ModuleList()
+            block_in, block_out = ch * in_ch_mult[i_level], ch * ch_mult[i_level]
+            for _ in range(num_res_blocks):
+                lvl.block.append(ResnetBlock(block_in, block_out))
+                block_in = block_out
+            if i_level != self.num_resolutions - 1:
+                lvl.downsample = Downsample(block_in)
+            self.down.append(lvl)
+        self.mid = nn.Module()
+        self.mid.block_1 = ResnetBlock(block_in)
+        self.mid.attn_1 = AttnBlock(block_in)
+        self.mid.block_2 = ResnetBlock(block_in)
+        self.norm_out = Normalize(block_in)
+        self.conv_out = nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, 3, padding=1)
+
+    def forward(self, x):
+        h = self.conv_in(x)
+        for i_level in range(self.num_resolutions):
+            lvl = self.down[i_level]
+            for j, blk in enumerate(lvl.block):
+                # a level's last block feeds the Downsample convolution, not a GroupNorm: its producer keeps no statistics
+                h = blk(h, gn_next=not (j == len(lvl.block) - 1 and i_level != self.num_resolutions - 1))
+            if i_level != self.num_resolutions - 1:
+                h = lvl.downsample(h)
+        h = self.mid.block_2(self.mid.attn_1(self.mid.block_1(h)))
+        return self.conv_out(_norm_silu(self.norm_out, h))
+
+
+class DiagonalGaussianDistribution(object):
+    """The encoder's posterior (reference distributions.py:24-37): mean, logvar = chunk(moments, 2), logvar clamped to [-30, 20].
+    `sample()` draws its noise as the reference does: torch.randn on the CPU default generator, moved to the moments' device."""
+
+    def __init__(self, parameters, deterministic=False):
+        self.parameters = parameters
+        self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
+        self.deterministic = deterministic
+        self.std = torch.exp(0.5 * self.logvar)
+        self.var = torch.exp(self.logvar)
+        if self.deterministic:
+            self.var = self.std = torch.zeros_like(self.mean)
+
+    def sample(self, noise=None):
+        if noise is None:
+            noise = torch.randn(self.mean.shape)
+        return self.mean + self.std * noise.to(device=self.parameters.device)
+
+    def mode(self):
+        return self.mean
+
+
 class AutoencoderKL(nn.Module):
-    """Decode-only AutoencoderKL: `decode(z) = decoder(post_quant_conv(z))` (reference autoencoder.py:330-333)."""
+    """AutoencoderKL: `decode(z) = decoder(post_quant_conv(z))` (reference autoencoder.py:330-333); with `add_encoder()`,
+    `encode(x) = DiagonalGaussianDistribution(quant_conv(encoder(x)))` (:324-328)."""
 
     def __init__(self, ddconfig=None, embed_dim=4, lossconfig=None, **ignored):
         super().__init__()
         ddconfig = dict(ddconfig or dict(double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128,
                                          ch_mult=[1, 2, 4, 4], num_res_blocks=2, attn_resolutions=[], dropout=0.0))
+        self.ddconfig, self.embed_dim = ddconfig, embed_dim
         self.decoder = Decoder(**ddconfig)
         self.post_quant_conv = nn.Conv2d(embed_dim, ddconfig["z_channels"], 1)
+
+    def add_encoder(self):
+        """Register `encoder` and `quant_conv` AFTER the decoder's parameters: the decode-only module's parameters, names and order
+        are unchanged (sta.pipeline.build_sd_v1 fills the two parts from seeds of their own)."""
+        self.encoder = Encoder(**self.ddconfig)
+        self.quant_conv = nn.Conv2d(2 * self.ddconfig["z_channels"], 2 * self.embed_dim, 1)
+        return self
+
+    @property
+    def has_encoder(self):
+        return hasattr(self, "encoder")
+
+    def encode_moments_input(self, x):
+        """encoder(x): the [B, 8, h, w] conv_out result that quant_conv turns into the posterior's moments."""
+        if not self.has_encoder:
+            raise RuntimeError("this AutoencoderKL has no encoder: build it with sta.pipeline.build_sd_v1(with_encoder=True)")
+        w = self.encoder.conv_in.weight
+        x = x.to(w.dtype)
+        if x.is_cuda and not w.is_contiguous() and w.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)       # NHWC encoder: the trunk convolutions on the HIP kernels
+        return self.encoder(x)
+
+    def encode(self, x):
+        return DiagonalGaussianDistribution(self.quant_conv(self.encode_moments_input(x)))
 
     def decode(self, z):
         w = self.decoder.conv_in.weight

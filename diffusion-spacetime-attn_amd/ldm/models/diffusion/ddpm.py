@@ -71,6 +71,23 @@ class LatentDiffusion(nn.Module):
         enc = getattr(self.cond_stage_model, "encode", self.cond_stage_model)
         return enc(c)
 
+    def encode_first_stage(self, x):
+        """The posterior of the image x in [-1, 1] (reference ddpm.py:766-801, without the split-input path)."""
+        if self.first_stage_model is None:
+            raise RuntimeError("no first-stage model configured (first_stage_config)")
+        return self.first_stage_model.encode(x)
+
+    def get_first_stage_encoding(self, encoder_posterior):
+        """scale_factor * z, z a sample of the posterior (reference ddpm.py:544-551)."""
+        from ldm.models.autoencoder import DiagonalGaussianDistribution
+        if isinstance(encoder_posterior, DiagonalGaussianDistribution):
+            z = encoder_posterior.sample()
+        elif torch.is_tensor(encoder_posterior):
+            z = encoder_posterior
+        else:
+            raise NotImplementedError("encoder_posterior of type '%s' not yet implemented" % type(encoder_posterior))
+        return self.scale_factor * z
+
     def decode_first_stage(self, z):
         """Differentiable on purpose: the fidelity loss back-propagates through it (reference :705-764)."""
         if self.first_stage_model is None:

@@ -248,7 +248,7 @@ class PLMSSampler(object):
         img_input = (torch.randn(shape, device=device) if x_T is None else x_T.to(device)).clone()
 
         # tell the 16 blocks a new prompt (batch) starts (replaces the `time == 981` test + cwd files)
-        _ps.begin_prompt(local if (batched or local is None) else local[0], first_timestep=int(time_range[0]))
+        _ps.begin_prompt(local if (batched or local is None) else local[0], first_timestep=int(time_range[self._first_call()]))
         block_boxes = boxes if batched else boxes[0]
 
         W = torch.full((b, K, S), self.weight_init / K if K else 0.0, device=device, dtype=torch.float32)   # :204-209
@@ -331,6 +331,9 @@ class PLMSSampler(object):
     # --------------------------------------------------------------------------------------------------
     def _time_range(self):
         return np.flip(self.ddim_timesteps)
+
+    def _first_call(self):
+        return 0
 
     def _trajectory(self, img, cond, uncond, scale, time_range, W, bboxs_curr, text_index, graph=False, call_recompute=False):
         """W: [K, S] for one image or [I, K, S] for a batch; column i of every image is used at step i."""
@@ -456,9 +459,16 @@ class SolverSamplerBase(PLMSSampler):
     arithmetic is one sta_sampler_step launch (sta.solver): DPMSolverSampler (dpm_solver/sampler.py) and DDIMSampler (ddim.py).
     Call i uses column i of W[K, S]. With fixed weights on the GPU the kernel also writes the next call's 16-bit input pair, so
     nothing but the (graph-replayed) UNet call and that one launch runs per step; tracked epochs differentiate through
-    sta.solver.SolverStepFn (backward = sta_sampler_step_bwd), per-call recomputation included."""
+    sta.solver.SolverStepFn (backward = sta_sampler_step_bwd), per-call recomputation included.
+    A trajectory may start at call `_start` > 0 (DDIMSampler.decode: img2img): calls _start .. S - 1 run, with columns _start .. S - 1,
+    and `_xin0` (if set) is the first call's 16-bit input pair, written by the fused encode step."""
     t_dtype = torch.float32
     tables = None
+    _start = 0
+    _xin0 = None
+
+    def _first_call(self):
+        return self._start
 
     def _time_range(self):
         return self.tables["t_in"]
@@ -474,20 +484,23 @@ class SolverSamplerBase(PLMSSampler):
         S, b, device = len(time_range), img.shape[0], img.device
         self._call_key = (tuple(img.shape[1:]), int(W.shape[-2]))
         grad = torch.is_grad_enabled()
-        keep = self._calls_to_keep(S, b) if call_recompute and grad else 0
+        start = self._start
+        keep = self._calls_to_keep(S - start, b) if call_recompute and grad else 0
         if call_recompute and grad:
             self.last_kept_calls = keep
-        eps_fn = self._make_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute, keep_last=keep, n_calls=S,
-                                   raw=True)
+        eps_fn = self._make_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute, keep_last=keep,
+                                   n_calls=S - start, raw=True)
         wdtype = next(self.model.model.parameters()).dtype
         fast = img.is_cuda and not grad
         x, m_prev = img, None
-        xin = solver._pair(img).to(wdtype) if fast else None
-        for i in range(S):
+        xin = None
+        if fast:
+            xin = self._xin0 if self._xin0 is not None else solver._pair(img).to(wdtype)
+        for i in range(start, S):
             t_val = float(time_range[i]) if self.t_dtype.is_floating_point else int(time_range[i])
             t = torch.full((b,), t_val, device=device, dtype=self.t_dtype)
             out = eps_fn(x if xin is None else xin, t, W[..., i])
             c = self._coef(i, scale)
-            noise = self._noise(i, x) if c.c_n else None
+            noise = self._noise(i - start, x) if c.c_n else None
             x, m_prev, xin = solver.solver_step(out, x, m_prev, noise, c, dtype=wdtype, want_xin=fast and i + 1 < S)
         return x

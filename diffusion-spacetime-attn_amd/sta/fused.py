@@ -370,6 +370,73 @@ def conv3x3_module(owner, conv, x, bias=None, res=None, up2=False, stats=True):
     return h if bias is None and res is None else add_bias_nchw(h if res is None else res, None if res is None else h, bias)
 
 
+CONV_S2 = True          # the HIP stride-2 3x3 convolution of the VAE encoder's Downsample (csrc/sta_encode.hip); False: F.pad + library
+CONV_S2_MIN_ITEMS = 64  # (8 x 16 output tile, 128-channel part) work items below which F.pad + the library convolution stays
+
+
+def conv3x3_s2_work_items(B, H, W, Cout):
+    """Workgroups of one sta_conv3x3_s2_nhwc launch over an H x W input (8 x 16 output tiles x 128-channel parts)."""
+    return B * (H // 16) * (W // 32) * (Cout // 128)
+
+
+def conv3x3_s2_supported(x, weight):
+    """The HIP Downsample convolution (pad (0, 1, 0, 1), 3x3, stride 2) applies to NHWC 16-bit CUDA activations outside autograd at the
+    geometries sta_conv3x3_s2_nhwc_supported lists (one image below the 4 GiB a launch addresses)."""
+    if not (CONV_S2 and usable(x) and x.dim() == 4 and is_nhwc(x) and weight.dtype == x.dtype and tuple(weight.shape[2:]) == (3, 3)):
+        return False
+    B, Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    return bool(lib.load().sta_conv3x3_s2_nhwc_supported(1, H, W, Cin, Cout)) and conv3x3_s2_work_items(B, H, W, Cout) >= CONV_S2_MIN_ITEMS
+
+
+def conv3x3_s2_nhwc(x, w_packed, Cout, bias=None, stats=False):
+    """conv2d(F.pad(x, (0, 1, 0, 1)), w, bias, stride=2) on an NHWC activation [B, Cin, H, W] (channels_last strides); the padded tensor is
+    never written. w_packed: pack_conv3x3_weight's image. Returns [B, Cout, H / 2, W / 2] channels_last; `stats` as for conv3x3_nhwc."""
+    B, Cin, H, W = x.shape
+    Ho, Wo = H // 2, W // 2
+    z = _zeros_page(x.device, 2 * Cin)
+    out = torch.empty((B, Cout, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    if bias is not None:
+        bias = bias.to(x.dtype).contiguous()
+    esz = x.element_size()
+    per_in, per_out = H * W * Cin * esz, Ho * Wo * Cout * esz
+    nb = max(1, min(B, CONV_MAX_BYTES // per_in))
+    L = lib.load()
+    slots = L.sta_conv3x3_s2_stats_slots(H, W) if stats else 0
+    part = torch.empty((B + 1, slots, Cout, 2), dtype=torch.float32, device=x.device) if slots else None
+    for b0 in range(0, B, nb):
+        n = min(nb, B - b0)
+        lib.check(L.sta_conv3x3_s2_nhwc(x.data_ptr() + b0 * per_in, w_packed.data_ptr(), z.data_ptr(), _ptr(bias), out.data_ptr() + b0 * per_out,
+                                        0 if part is None else part.data_ptr() + b0 * slots * Cout * 8, n, H, W, Cin, Cout, _DT[x.dtype],
+                                        _stream()), "sta_conv3x3_s2_nhwc")
+    if part is not None and _version(out) is not None:
+        out._sta_stats = (out._version, _finalize_stats(part, B, slots, Cout))
+    return out
+
+
+def vae_encode_step(h, quant_weight, quant_bias, n_post, n_enc, scale_factor, sqrt_a, sqrt_1ma, want_z0=False, want_xin=True):
+    """The encoder's conv_out result h [B, 8, h, w] (16-bit CUDA, channels_last) -> (x, z0, xin) in one pass (sta_vae_encode_step):
+    quant_conv, the posterior's sample z0 = scale_factor (mean + std n_post), x = sqrt_a z0 + sqrt_1ma n_enc (fp32 [B, 4, h, w]), xin the
+    16-bit CFG input pair [2B, 4, h, w] of x. n_post, n_enc: fp32 [B, 4, h, w] noises."""
+    B, C, Hh, Ww = h.shape
+    if C != 8 or not h.is_cuda or h.dtype not in _DT:
+        raise ValueError("vae_encode_step: 16-bit CUDA h [B, 8, h, w], got %s %s" % (tuple(h.shape), h.dtype))
+    h = h.contiguous(memory_format=torch.channels_last)
+    qw = quant_weight.detach().reshape(8, 8).float().contiguous()
+    qb = quant_bias.detach().float().contiguous()
+    f = lambda t: t.detach().to(device=h.device, dtype=torch.float32).contiguous()
+    n_post, n_enc = f(n_post), f(n_enc)
+    if n_post.shape != (B, 4, Hh, Ww) or n_enc.shape != (B, 4, Hh, Ww):
+        raise ValueError("vae_encode_step: noises must be [B, 4, h, w] = %s" % ((B, 4, Hh, Ww),))
+    x = torch.empty((B, 4, Hh, Ww), dtype=torch.float32, device=h.device)
+    z0 = torch.empty_like(x) if want_z0 else None
+    xin = torch.empty((2 * B, 4, Hh, Ww), dtype=h.dtype, device=h.device) if want_xin else None
+    lib.check(lib.load().sta_vae_encode_step(h.data_ptr(), qw.data_ptr(), qb.data_ptr(), n_post.data_ptr(), n_enc.data_ptr(), x.data_ptr(),
+                                             _ptr(z0), _ptr(xin), B, Hh * Ww, float(scale_factor), float(sqrt_a), float(sqrt_1ma), _DT[h.dtype],
+                                             _stream()), "sta_vae_encode_step")
+    return x, z0, xin
+
+
 CAT_IN_PLACE = True     # output blocks read `cat([h, skip])` in place (GroupNorm and the 1x1 skip GEMM take both tensors); False: torch.cat
 
 

@@ -59,8 +59,12 @@ _REQUIRED_PREFIXES = ("model.diffusion_model.", "first_stage_model.", "cond_stag
 
 
 def build_sd_v1(device="cuda", dtype=torch.float16, ckpt=None, seed=0, with_vae=True, use_checkpoint=False,
-                init_weights=True, unet_overrides=None, channels_last=False, clip_tokenizer=None, real_text_encoder=None):
-    """`ckpt` given: the SD-v1-4 state_dict loads by name INCLUDING the CLIP text encoder
+                init_weights=True, unet_overrides=None, channels_last=False, clip_tokenizer=None, real_text_encoder=None,
+                with_encoder=False):
+    """`with_encoder`: the VAE encoder and quant_conv too (img2img). They are registered after the decoder, so the default build's
+    parameters, names and order are unchanged, and synthetic weights fill them from a seed of their own (seed + 2): the decoder's
+    synthetic values are the same with and without them. With a checkpoint their keys are required like the other prefixes.
+    `ckpt` given: the SD-v1-4 state_dict loads by name INCLUDING the CLIP text encoder
     (`cond_stage_model.transformer.*` -> FrozenCLIPEmbedder, reference v1-inference.yaml:67-68); a key of the
     UNet / VAE decoder / text encoder that the checkpoint lacks raises (the tensors are created uninitialised).
     `ckpt=None`: synthetic weights and the deterministic text stand-in (benchmarks, tests).
@@ -72,6 +76,10 @@ def build_sd_v1(device="cuda", dtype=torch.float16, ckpt=None, seed=0, with_vae=
     with torch.device("meta"):
         unet = UNetModel(**cfg)
         vae = AutoencoderKL() if with_vae else None
+        if with_encoder:
+            if vae is None:
+                raise ValueError("with_encoder needs with_vae")
+            vae.add_encoder()
     unet = unet.to(dtype).to_empty(device=device)
     if vae is not None:
         vae = vae.to(dtype).to_empty(device=device)
@@ -112,17 +120,21 @@ def build_sd_v1(device="cuda", dtype=torch.float16, ckpt=None, seed=0, with_vae=
         bad = [k for k in missing if k.startswith(_REQUIRED_PREFIXES)]
         if bad:
             raise RuntimeError("%s lacks %d tensors of the sampling path (first: %s)" % (ckpt, len(bad), ", ".join(bad[:5])))
-        print("loaded %s: %d unexpected keys ignored (encoder / EMA / loss buffers)" % (ckpt, len(unexpected)))
+        print("loaded %s: %d unexpected keys ignored (%sEMA / loss buffers)" % (ckpt, len(unexpected), "" if with_encoder else "encoder / "))
     elif init_weights:
-        if torch.device(device).type == "cuda":
-            synth.device_fill_(model.model, seed)
-            if vae is not None:
-                synth.device_fill_(vae, seed + 1)
-        else:
-            synth.seeded_fill_(model.model, seed)
-            if vae is not None:
-                synth.seeded_fill_(vae, seed + 1)
+        fill = synth.device_fill_ if torch.device(device).type == "cuda" else synth.seeded_fill_
+        fill(model.model, seed)
+        if vae is not None:
+            # the decode half under the state_dict names it has without an encoder: the same generator stream / per-name values
+            fill(torch.nn.ModuleDict(dict(decoder=vae.decoder, post_quant_conv=vae.post_quant_conv)), seed + 1)
+            if vae.has_encoder:
+                fill(encoder_part(vae), seed + 2)
     return model
+
+
+def encoder_part(vae):
+    """The encoder and quant_conv under their AutoencoderKL state_dict names (encoder.*, quant_conv.*): what the synthetic fills see."""
+    return torch.nn.ModuleDict(dict(encoder=vae.encoder, quant_conv=vae.quant_conv))
 
 
 def set_recompute(model, mode="auto", prompts_per_step=1):

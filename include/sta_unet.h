@@ -212,6 +212,35 @@ int sta_mx8_gemm(const void* p, const void* ps, const void* q, const void* qs, v
 int sta_groupnorm_silu_nhwc_bwd(const void* x, const float* add, const void* gamma, const void* beta, const void* dy, void* dx,
                                 const void* fwd_workspace, void* bwd_workspace, int B, int C, int HW, int G, float eps, int silu,
                                 int dtype, void* stream);
+/*
+ * The VAE encoder's Downsample (reference model.py:60-79: F.pad(x, (0, 1, 0, 1)) then a 3x3 convolution with stride 2) on NHWC
+ * activations, without the padded tensor (csrc/sta_encode.hip):
+ *     out[b][y][x][o] = bias[o] + sum_{ky, kx, i} w[o][i][ky][kx] * x[b][2y + ky][2x + kx][i]      (x = 0 at row >= H or col >= W)
+ *   x: [B][H][W][Cin] dtype (H, W: the INPUT size);  out: [B][H / 2][W / 2][Cout] dtype;  zeros: >= 2 * Cin bytes of zeros;
+ *   bias: [Cout] dtype or NULL;  packed_w: sta_conv3x3_pack_w's image of the [Cout][Cin][3][3] weight (its 128-channel parts);
+ *   stats: NULL, or [B + 1][sta_conv3x3_s2_stats_slots(H, W)][Cout][2] fp32 partial sums / sums of squares of the stored values, folded by
+ *   sta_stats_finalize into the statistics of the GroupNorm that consumes `out` (the next ResnetBlock's norm1), as for sta_conv3x3_nhwc.
+ * sta_conv3x3_s2_nhwc_supported: H % 16 == 0, W % 32 == 0 (8 x 16 output tiles); Cin == Cout (Downsample), a multiple of 128 and not of
+ * 160; x below 4 GiB. The SD-v1 encoder's three Downsample shapes at 512^2 and 768^2 are inside (each measured faster than F.pad + the
+ * library convolution). Everything else stays with F.pad + the library convolution.
+ */
+int sta_conv3x3_s2_nhwc_supported(int B, int H, int W, int Cin, int Cout);
+int sta_conv3x3_s2_stats_slots(int H, int W);
+int sta_conv3x3_s2_nhwc(const void* x, const void* packed_w, const void* zeros, const void* bias, void* out, float* stats, int B, int H, int W,
+                        int Cin, int Cout, int dtype, void* stream);
+
+/*
+ * From the encoder's conv_out result to the first UNet call's input of img2img, per latent pixel, in fp32 (csrc/sta_encode.hip):
+ *     moments    = quant_w h + quant_b                               quant_conv, 8x8 1x1 (reference autoencoder.py:324-328)
+ *     mean       = moments[0:4],  logvar = clamp(moments[4:8], -30, 20)
+ *     z0         = scale_factor (mean + exp(logvar / 2) n_post)       DiagonalGaussianDistribution.sample + get_first_stage_encoding
+ *     x          = sqrt_a z0 + sqrt_1ma n_enc                         DDIMSampler.stochastic_encode
+ *   h: [B][hw][8] dtype (NHWC, 16-byte aligned);  quant_w [8][8], quant_b [8] fp32;  n_post, n_enc, x, z0: [B][4][hw] fp32 (z0 may be NULL);
+ *   xin: NULL, or [2B][4][hw] dtype = (x, x) per image, the first UNet call's CFG input pair (bitwise the 16-bit rounding of x).
+ */
+int sta_vae_encode_step(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x, float* z0,
+                        void* xin, long B, long hw, float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream);
+
 int sta_geglu_bwd(const void* x, const void* dy, void* dx, long R, int D, int dtype, void* stream);
 int sta_layernorm_bwd(const void* s, const void* gamma, const void* dy, const void* dres, void* ds, long R, int C, float eps,
                       int dtype, void* stream);
