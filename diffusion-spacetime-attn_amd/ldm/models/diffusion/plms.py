@@ -16,6 +16,7 @@ blocks instead of being compared with 981.
 MI355X-specific: with `opt_epochs=0` (fixed weights; BASELINE config 2) the whole CFG UNet call is
 captured once into a hipGraph and replayed for the 51 calls of a trajectory (sta.graphs).
 """
+import collections
 import math
 import os
 
@@ -67,16 +68,70 @@ class DCLIPLoss(torch.nn.Module):
         img = torch.nn.functional.interpolate(image.unsqueeze(0), size=(224, 224), mode="bilinear", align_corners=False)
         return self._loss(img, text)
 
+    # ------------------------------------------------------------------ the whole step's views as one batch (sta.clip)
+    TEXT_CACHE = 4096
 
-def load_clip_model(spec=None, device="cuda"):
+    def batch_ready(self, images):
+        """The sampler takes `forward_batch` only for the built-in ViT-B/32 with the image on the GPU (the HIP view kernels);
+        every other loss model keeps the view-by-view calls."""
+        from sta.clip import ClipViTB32
+        return isinstance(self.model, ClipViTB32) and images.is_cuda
+
+    def text_feature(self, text, device):
+        """encode_text of one string, computed once (text features are constant over a prompt's epochs); the last TEXT_CACHE
+        strings are kept."""
+        cache = self.__dict__.setdefault("_text_cache", collections.OrderedDict())
+        key = (text, str(device))
+        if key in cache:
+            cache.move_to_end(key)
+            return cache[key]
+        with torch.no_grad():
+            ft = self.model.encode_text(self._text(text, device))[0].detach()
+        cache[key] = ft
+        while len(cache) > self.TEXT_CACHE:
+            cache.popitem(last=False)
+        return ft
+
+    def forward_batch(self, images, texts, boxes, names, local_weight=5.0):
+        """sum_i (1 - cos(global_i, text_i)) + local_weight sum_k (1 - cos(crop_ik, "A photo of " + name_ik)) over images
+        [b, 3, H, W]: the sum of PLMSSampler._fidelity_loss over the batch (same crop rule and name normalisation), with the
+        b (1 + K) views built by one sta_clip_views launch (CPU tensors: sta.clip.views_reference) and run through the image
+        tower as one batch. Global view: AvgPool(7 H / 224) of the x7 upsample, forward_2's 16 at 512^2."""
+        from sta import clip as _clip
+        b, _, hgt, wid = images.shape
+        assert len(texts) == len(boxes) == len(names) == b
+        view_boxes, strings, weights = [], [], []
+        for i in range(b):
+            view_boxes.append((i, 0, hgt, 0, wid))
+            strings.append(texts[i])
+            weights.append(1.0)
+            for centre, name in zip(boxes[i], names[i]):
+                view_boxes.append((i,) + tuple(object_crop_box(centre, hgt, wid)))
+                strings.append("A photo of " + name.lower().replace("the ", ""))                    # :266-267
+                weights.append(float(local_weight))
+        tower = self.model.dtype
+        rows = _clip.clip_views(images.float(), view_boxes, tower if images.is_cuda else torch.float32)
+        fi = self.model.encode_patches(rows).float()
+        ft = torch.stack([self.text_feature(s, images.device) for s in strings]).float()
+        w = torch.tensor(weights, dtype=torch.float32, device=images.device)
+        return (w * (1 - torch.nn.functional.cosine_similarity(fi, ft))).sum()
+
+
+def load_clip_model(spec=None, device="cuda", dtype=torch.float16, tokenizer_path=None):
     """(model, tokenize) for the fidelity loss.
       spec None           the reference's own call: `clip.load("ViT-B/32")` + `clip.tokenize` (plms.py:24,31) — needs the
                           OpenAI `clip` package and its weights on disk;
       "module:callable"   import `module`, call `callable(device)` -> model or (model, tokenize);
-      path to a .pt file  `clip.load(path)`.
+      path to a .pt file  `clip.load(path)`;
+      "builtin:<weights>" this project's own ViT-B/32 (sta.clip) with a state_dict file, the official TorchScript archive or a
+                          Hugging Face CLIPModel state_dict; "builtin:synthetic" = seeded weights. No `clip` package involved;
+                          the tokeniser comes from `tokenizer_path` (the CLIPTokenizer directory of --clip_tokenizer).
     Raises with the reason when nothing can be loaded — callers do this BEFORE sampling (a trajectory is 51 UNet
     calls; the reference would fail at import time, plms.py:11)."""
     import importlib
+    if spec and spec.startswith("builtin:"):
+        from sta import clip as _clip
+        return _clip.builtin(spec[len("builtin:"):], device, dtype, tokenizer_path)
     if spec and ":" in spec and not os.path.exists(spec):
         mod, fn = spec.split(":", 1)
         got = getattr(importlib.import_module(mod), fn)(device)
@@ -85,6 +140,7 @@ def load_clip_model(spec=None, device="cuda"):
         clip = importlib.import_module("clip")
     except ImportError as e:
         raise RuntimeError("the fidelity loss needs a CLIP model: the OpenAI `clip` package is not installed; pass "
+                           "--clip builtin:PATH (this project's ViT-B/32 with CLIP weights from PATH, plus --clip_tokenizer), "
                            "--clip module:callable (returns an object with encode_image/encode_text, optionally a "
                            "tokenizer), or --opt_epochs 0 for fixed blend weights") from e
     model, _ = clip.load(spec or "ViT-B/32", device=device)
@@ -137,7 +193,7 @@ class _CallRecompute(torch.autograd.Function):
 class PLMSSampler(object):
     def __init__(self, model, schedule="linear", loss_model=None, opt_epochs=3, lr=0.005, weight_init=5.0,
                  local_loss_weight=5.0, use_graph=True, save_images=True, outdir="result_outputs/", loss_scale=None, keep_calls=None,
-                 **kwargs):
+                 batched_loss=True, **kwargs):
         """`loss_scale`: the fidelity loss is multiplied by it before backward and W.grad divided by it before the Adam step.
         None = 1 for bf16 / fp32 models; for an fp16 model the power of two that brings the scaled loss to [2^15, 2^16)
         (2^12 for the synthetic CLIP stand-in's loss of ~11; the same gradients whatever the loss model's own scale is:
@@ -149,6 +205,7 @@ class PLMSSampler(object):
         representable (the reference relies on CUDA autocast with fp32 parameters and no scaler, scripts/txt2img-gpt.py:301)."""
         super().__init__()
         self.loss_scale = loss_scale
+        self.batched_loss = batched_loss  # False: view-by-view loss calls even where the loss model offers forward_batch (tests, tools)
         self.keep_calls = keep_calls      # per-call recomputation: how many trailing calls keep their activations (None = sized to HBM)
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
@@ -278,7 +335,11 @@ class PLMSSampler(object):
                     if self.model.first_stage_model is not None:
                         x_img = torch.clamp((self.model.decode_first_stage(img) + 1.0) / 2.0, min=0.0, max=1.0)   # :249-250
                     if track:
-                        loss = sum(self._fidelity_loss(x_img[i].float(), texts[i], boxes[i], names[i]) for i in range(b))
+                        lm = self.clip_loss_model
+                        if self.batched_loss and getattr(lm, "batch_ready", None) is not None and lm.batch_ready(x_img):
+                            loss = lm.forward_batch(x_img, texts, boxes, names, self.local_loss_weight)
+                        else:
+                            loss = sum(self._fidelity_loss(x_img[i].float(), texts[i], boxes[i], names[i]) for i in range(b))
                         optimizer.zero_grad()
                         scale = self._loss_scale(float(loss.detach())) * scale_backoff
                         (loss * scale if scale != 1.0 else loss).backward()

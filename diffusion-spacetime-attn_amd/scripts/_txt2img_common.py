@@ -57,8 +57,11 @@ def build_parser(default_dataset):
                    help="fp16 = the reference's autocast type and the one within 1e-3 on the attention maps (DESIGN.md section 2)")
     p.add_argument("--clip", type=str, default=None,
                    help="fidelity-loss model for --opt_epochs > 0: 'module:callable' (called with the device, returns a model with "
-                        "encode_image/encode_text or (model, tokenize)), a CLIP .pt path, or 'synthetic' (frozen stand-in, for "
-                        "timing the gradient path). Default: clip.load('ViT-B/32') as the reference (plms.py:24)")
+                        "encode_image/encode_text or (model, tokenize)), a CLIP .pt path, 'synthetic' (frozen stand-in, for "
+                        "timing the gradient path), or 'builtin:PATH' = this project's own CLIP ViT-B/32 (sta.clip) with the weights of "
+                        "PATH (a state_dict file, the official TorchScript archive or a Hugging Face CLIPModel state_dict; needs "
+                        "--clip_tokenizer; 'builtin:synthetic' = seeded weights). Default: clip.load('ViT-B/32') as the reference "
+                        "(plms.py:24)")
     p.add_argument("--fp8", action="store_true",
                    help="store the Linear weights of the transformer blocks as OCP e4m3 with per-channel scales (BASELINE configs[4]): half "
                         "the weight memory; their GEMMs become hipBLASLt's row-scaled e4m3 GEMMs behind a per-row activation quantiser, "
@@ -75,12 +78,60 @@ def build_parser(default_dataset):
     return p
 
 
+def builtin_clip(opt):
+    """What follows `builtin:` in --clip when the fidelity loss will be evaluated (opt_epochs > 1), else None."""
+    if opt.opt_epochs > 1 and opt.clip and opt.clip.startswith("builtin:"):
+        return opt.clip[len("builtin:"):]
+    return None
+
+
+def check_clip_option(opt, side=None):
+    """--clip builtin:...: refusals that need no GPU, no model and no tokenizer. `side` = (H, W) of the decoded image if known."""
+    spec = builtin_clip(opt)
+    if spec is None:
+        return
+    if spec != "synthetic" and not os.path.isfile(spec):
+        raise SystemExit("--clip builtin:%s: no such weights file" % spec)
+    if spec != "synthetic" and not opt.clip_tokenizer:
+        raise SystemExit("--clip builtin:%s needs --clip_tokenizer (the directory with the CLIP vocabulary files)" % spec)
+    if opt.clip_tokenizer and not os.path.isdir(opt.clip_tokenizer):
+        raise SystemExit("--clip_tokenizer %s: no such directory" % opt.clip_tokenizer)
+    if side is not None:
+        from sta.clip import check_view_shapes
+        try:
+            check_view_shapes(*side)
+        except ValueError as e:
+            raise SystemExit("--clip %s: %s" % (opt.clip, e))
+
+
+def loss_tokenizer(opt):
+    """The tokeniser of the built-in loss model, made before any model is: the CLIPTokenizer of --clip_tokenizer, or the hashing
+    stand-in for builtin:synthetic without one."""
+    from sta import clip
+    if opt.clip_tokenizer:
+        return clip.tokenizer(opt.clip_tokenizer)
+    return clip.hash_tokenize
+
+
+def check_loss_texts(tokenize, items):
+    """Every string the loss will tokenise — each prompt and each "A photo of <object>" — through `tokenize` now: clip.tokenize
+    refuses more than 75 tokens, and it would do so after the first 51-call trajectory. items: (prompt, object names)."""
+    from sta.clip import loss_strings
+    for prompt, names in items:
+        for text in loss_strings(prompt, names):
+            try:
+                tokenize([text])
+            except RuntimeError as e:
+                raise SystemExit("the fidelity loss cannot tokenise a text of this run: %s" % e)
+
+
 def check_options(opt):
     """Refusals that need no GPU (raised before anything is built)."""
     if opt.mxfp8 and opt.fp8:
         raise SystemExit("--mxfp8 and --fp8 are exclusive")
     if opt.mxfp8 and opt.opt_epochs > 0:
         raise SystemExit("--mxfp8 is an inference option: use --opt_epochs 0")
+    check_clip_option(opt, (opt.H, opt.W))
 
 
 def sampler_choice(opt):
@@ -126,6 +177,10 @@ def run(kind, default_dataset):
     ckpt = opt.ckpt if (os.path.exists(opt.ckpt) and not opt.synthetic) else None
     if ckpt is None and not opt.synthetic:
         raise SystemExit("checkpoint %s not found (pass --synthetic to run with synthetic weights)" % opt.ckpt)
+    loss_tokenize = None
+    if builtin_clip(opt) is not None:
+        loss_tokenize = loss_tokenizer(opt)
+        check_loss_texts(loss_tokenize, [(p, list((datasets.layout_for(layouts, p, i) or {}).keys())) for i, p in enumerate(prompts)])
     loss_model = None
     if opt.opt_epochs > 1:        # the sampler evaluates the loss only when an epoch is tracked (opt_epochs > 1); fail here, not after the first 51-call trajectory
         from ldm.models.diffusion.plms import DCLIPLoss, load_clip_model
@@ -134,7 +189,8 @@ def run(kind, default_dataset):
             loss_model = DCLIPLoss(SyntheticCLIP().to(dev))
         else:
             try:
-                loss_model = DCLIPLoss(*load_clip_model(opt.clip, dev))
+                clip_model, tokenize = load_clip_model(opt.clip, dev, dtype=dtype, tokenizer_path=opt.clip_tokenizer)
+                loss_model = DCLIPLoss(clip_model, loss_tokenize or tokenize)
             except Exception as e:
                 raise SystemExit("--opt_epochs %d: %s" % (opt.opt_epochs, e))
     model = build_sd_v1(dev, dtype, ckpt=ckpt if rank == 0 else None, init_weights=(rank == 0), use_checkpoint=opt.opt_epochs > 1,

@@ -83,6 +83,7 @@ def check_options(opt):
         raise SystemExit("t_enc = int(strength * ddim_steps) = %d must be in 1 .. %d" % (t_enc, opt.ddim_steps - 1))
     if not opt.init_img:
         raise SystemExit("--init-img is required")
+    _txt2img_common.check_clip_option(opt)
     return t_enc
 
 
@@ -159,16 +160,22 @@ def main(argv=None):
     paths = image_paths(opt.init_img, len(prompts))
     images = {p: load_img(p) for p in dict.fromkeys(paths)}
     size = check_images(images)
+    _txt2img_common.check_clip_option(opt, (size, size))
+    from sta import datasets
+    layouts = datasets.load_layouts(opt.layout) if opt.layout else None
+    loss_tokenize = None
+    if _txt2img_common.builtin_clip(opt) is not None:
+        loss_tokenize = _txt2img_common.loss_tokenizer(opt)
+        _txt2img_common.check_loss_texts(loss_tokenize, [(p, list((datasets.layout_for(layouts, p, i) or {}).keys()))
+                                                         for i, p in enumerate(prompts)])
     if not torch.cuda.is_available():
         raise SystemExit("a GPU is required (the fused cross-attention has no CPU path)")
     from ldm.models.diffusion.ddim import DDIMSampler
-    from sta import datasets
     from sta.pipeline import build_sd_v1, conditionings, use_shipped_miopen_db
 
     dev = torch.device("cuda", 0)
     dtype = torch.bfloat16 if opt.dtype == "bf16" else torch.float16
     use_shipped_miopen_db(0)
-    layouts = datasets.load_layouts(opt.layout) if opt.layout else None
     ckpt = opt.ckpt if (os.path.exists(opt.ckpt) and not opt.synthetic) else None
     if ckpt is None and not opt.synthetic:
         raise SystemExit("checkpoint %s not found (pass --synthetic to run with synthetic weights)" % opt.ckpt)
@@ -180,7 +187,8 @@ def main(argv=None):
             loss_model = DCLIPLoss(SyntheticCLIP().to(dev))
         else:
             try:
-                loss_model = DCLIPLoss(*load_clip_model(opt.clip, dev))
+                clip_model, tokenize = load_clip_model(opt.clip, dev, dtype=dtype, tokenizer_path=opt.clip_tokenizer)
+                loss_model = DCLIPLoss(clip_model, loss_tokenize or tokenize)
             except Exception as e:
                 raise SystemExit("--opt_epochs %d: %s" % (opt.opt_epochs, e))
     model = build_sd_v1(dev, dtype, ckpt=ckpt, use_checkpoint=opt.opt_epochs > 1, clip_tokenizer=opt.clip_tokenizer,

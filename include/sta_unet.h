@@ -266,6 +266,28 @@ int sta_sampler_step(const void* eps, const float* x, const float* m_prev, const
 int sta_sampler_step_bwd(const float* g_xn, const float* g_m, float* g_x, void* g_eps, float* g_mprev, long b, long n, float scale,
                          float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, int dtype, void* stream);
 
+/*
+ * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
+ * of its patch-embedding GEMM, and the gradient of the image from the gradient of those rows.
+ *   img:   [B][3][H][W] fp32 in [0, 1] (the clamped decoder output);
+ *   boxes: [n_views][5] int32 (image, y1, y2, x1, x2) in DEVICE memory, boxes_host the same table in HOST memory (the rules below are
+ *          checked on it before the launch; the kernels read the device copy and clamp what they read into the image);
+ *   out:   [n_views][49][3072] dtype, 16-byte aligned: row = patch (py, px) of the 7 x 7 grid, column = (c, dy, dx), the column order of
+ *          visual.conv1.weight.view(width, 3072). View pixel (c, Y, X) is row (Y / 32) 7 + X / 32, column c 1024 + (Y % 32) 32 + X % 32.
+ * A view whose box is the whole image is the GLOBAL view, AvgPool2d(p)(Upsample(scale_factor=7, nearest)(x)) with p = 7 H / 224 (16 at
+ * 512^2, the reference's constant, plms.py:36-44): integer overlap weights over p^2, fp32. Any other box is a CROP view:
+ * F.interpolate(x[:, y1:y2, x1:x2], (224, 224), mode="bilinear", align_corners=False), source index clamped inside the box. The result is
+ * rounded to dtype once.
+ * sta_clip_views_bwd: dout [n_views][49][3072] dtype -> dimg [B][3][H][W] fp32, every element written (no memset, no atomics: a gather,
+ * bitwise reproducible). boxes must be grouped by image, in image order.
+ * Rules (STA_E_UNSUP / STA_E_ARG with text): H == W, H % 32 == 0, 256 <= H <= 1024 (below 224 the pool window is narrower than an upsampled
+ * pixel and a source pixel would feed more than 2 x 2 global outputs); every box inside the image and at least 2 x 2; n_views 49 3072 < 2^31.
+ */
+int sta_clip_views(const float* img, const int* boxes, const int* boxes_host, void* out, int B, int H, int W, int n_views, int out_dtype,
+                   void* stream);
+int sta_clip_views_bwd(const void* dout, const int* boxes, const int* boxes_host, float* dimg, int B, int H, int W, int n_views, int dtype,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
