@@ -137,6 +137,16 @@ class CrossAttention(nn.Module):
             return self._self_attention_hip_mx(x)
         if not isinstance(self.to_q, nn.Linear):
             return self._self_attention_hip_fp8(x)
+        c = self.to_q.weight.shape[0]
+        qk = F.linear(x, self._wqk_cat())                             # [B, N, 2C]
+        b, n, _ = x.shape
+        vt = torch.mm(self.to_v.weight, x.reshape(b * n, c).t()).view(c, b, n).permute(1, 0, 2)    # [B, C, N] view of [C, B*N]
+        o = _ops.self_attention(qk[..., :c], qk[..., c:], vt, self.heads, _ops.LN2, sfrag=pre_to_out_sfrag)
+        return o if pre_to_out_sfrag else self.to_out(o)
+
+
+    def _wqk_cat(self):
+        """[Wq * scale * log2 e; Wk], rebuilt only when a weight tensor changes."""
         wq, wk = self.to_q.weight, self.to_k.weight
         key = (wq.data_ptr(), wq._version, wk.data_ptr(), wk._version)
         if getattr(self, "_wqk_key", None) != key:
@@ -144,13 +154,16 @@ class CrossAttention(nn.Module):
             # kernel's exponent is a bare exp2 of the MFMA result (sta_selfattn.hip, PRE)
             wq2 = (wq.detach().float() * (self.scale * 1.4426950408889634)).to(wq.dtype)
             self._wqk, self._wqk_key = torch.cat([wq2, wk.detach()]), key
-        c = wq.shape[0]
-        qk = F.linear(x, self._wqk)                                   # [B, N, 2C]
-        b, n, _ = x.shape
-        vt = torch.mm(self.to_v.weight, x.reshape(b * n, c).t()).view(c, b, n).permute(1, 0, 2)    # [B, C, N] view of [C, B*N]
-        o = _ops.self_attention(qk[..., :c], qk[..., c:], vt, self.heads, _ops.LN2, sfrag=pre_to_out_sfrag)
-        return o if pre_to_out_sfrag else self.to_out(o)
+        return self._wqk
 
+    def _ln_qkv_fragments(self):
+        """[Wq'; Wk; Wv] as sta_ln_qkv streams it (csrc/sta_lnqkv.hip), repacked only when a weight tensor changes."""
+        wv = self.to_v.weight
+        wqk = self._wqk_cat()
+        key = (self._wqk_key, wv.data_ptr(), wv._version, wv.dtype)
+        if getattr(self, "_wqkv_frag_key", None) != key:
+            self._wqkv_frag, self._wqkv_frag_key = _fused.pack_ln_qkv_weight(wqk, wv), key
+        return self._wqkv_frag
 
     def _self_attention_hip_fp8(self, x):
         """The same with e4m3 weights (sta.fp8, BASELINE configs[4]): x is quantised ONCE per call (sta_quant_rows_fp8) and
@@ -299,7 +312,16 @@ class BasicTransformerBlock(nn.Module):
         if _fused.usable(x):
             # inference: every residual add runs inside the LayerNorm pass that consumes it (sta_add_layernorm)
             n1, n2, n3 = self.norm1, self.norm2, self.norm3
-            s, y = _fused.add_layernorm(x, None, in_bias, n1.weight, n1.bias, n1.eps, store_sum=in_bias is not None)
+            a1 = self.attn1
+            big = _fused.rowgemm_worthwhile(x)      # enough rows for the persistent row-GEMM passes to fill the chip
+            sfrag = big and _ops.self_attention_sfrag_supported(x, a1.heads) and isinstance(a1.to_q, nn.Linear) and isinstance(a1.to_out[0], nn.Linear)
+            # level 0: norm1 and the q|k / V^T projections of attn1 are ONE pass (csrc/sta_lnqkv.hip) — norm1's output never reaches HBM
+            lnqkv = sfrag and _fused.LN_QKV and all(isinstance(m, nn.Linear) and m.bias is None for m in (a1.to_q, a1.to_k, a1.to_v)) \
+                and _fused.ln_qkv_supported(x)
+            if lnqkv:
+                s, qk, vt = _fused.ln_qkv(x, in_bias, n1.weight, n1.bias, n1.eps, a1._ln_qkv_fragments(), store_sum=in_bias is not None)
+            else:
+                s, y = _fused.add_layernorm(x, None, in_bias, n1.weight, n1.bias, n1.eps, store_sum=in_bias is not None)
             x = x if s is None else s
             fused_q = cache.packed_proj is not None and not self.keep_maps
             # the GEGLU projection of the feed-forward as one pass over norm3's output in query-fragment order (csrc/sta_ffgemm.hip)
@@ -308,12 +330,14 @@ class BasicTransformerBlock(nn.Module):
             # norm2's output has ONE consumer when to_q runs inside the attention kernel: the pass then writes it in the MFMA
             # operand order that kernel loads (query-fragment order, 1-KiB coalesced loads) instead of row-major
             qfrag = fused_q and cache.qfrag
-            a1 = self.attn1
-            big = _fused.rowgemm_worthwhile(x)      # enough rows for the persistent row-GEMM passes to fill the chip
-            if big and _ops.self_attention_sfrag_supported(y, a1.heads) and isinstance(a1.to_q, nn.Linear) and isinstance(a1.to_out[0], nn.Linear):
+            if sfrag:
                 # level 0: the self-attention kernel leaves its output in out-fragment order and attn1.to_out + the residual + norm2
                 # are ONE pass over it (csrc/sta_rowgemm.hip) — to_out's result never reaches HBM, y leaves in the order its consumer wants
-                o = a1._self_attention_hip(y, pre_to_out_sfrag=True)
+                if lnqkv:
+                    b, n, ch = x.shape
+                    o = _ops.self_attention(qk[..., :ch], qk[..., ch:], vt.view(ch, b, n).permute(1, 0, 2), a1.heads, _ops.LN2, sfrag=True)
+                else:
+                    o = a1._self_attention_hip(y, pre_to_out_sfrag=True)
                 x, y = _fused.to_out_add_layernorm_ofrag(x, o, self._wo1_fragments(), a1.to_out[0].bias, n2.weight, n2.bias, n2.eps, a1.heads, y_qfrag=qfrag)
             else:
                 x, y = _fused.add_layernorm(x, a1(y), None, n2.weight, n2.bias, n2.eps, qfrag=qfrag)

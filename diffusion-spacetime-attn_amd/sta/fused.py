@@ -264,6 +264,43 @@ def ff_out_res_hfrag(x, h_frag, w_packed, bias):
     return out
 
 
+LN_QKV = True           # level 0: norm1 + the q|k and V^T projections of attn1 as one pass (csrc/sta_lnqkv.hip); False: sta_add_layernorm + two library GEMMs
+
+
+def ln_qkv_supported(x):
+    """Shapes sta_ln_qkv takes: C = 320, a multiple of 16 rows, the [rows, 2C] q|k output addressable by one launch."""
+    C = x.shape[-1]
+    return (x.numel() // C) % 16 == 0 and rows_addressable(x, width=2 * C) and bool(lib.load().sta_ln_qkv_packed_w_bytes(C))
+
+
+def pack_ln_qkv_weight(wqk, wv):
+    """[Wq * scale * log2 e; Wk] [2C, C] and Wv [C, C] -> the fragment image sta_ln_qkv streams through LDS (uint8 tensor); once per model."""
+    C = wv.shape[0]
+    L = lib.load()
+    n = L.sta_ln_qkv_packed_w_bytes(C)
+    if n == 0 or tuple(wqk.shape) != (2 * C, C) or tuple(wv.shape) != (C, C) or not wv.is_cuda or wqk.dtype != wv.dtype:
+        raise ValueError("fused norm1 + q/k/v projection: CUDA weights [640, 320] and [320, 320] of one dtype; got %s %s" % (tuple(wqk.shape), tuple(wv.shape)))
+    wqk, wv = wqk.detach().contiguous(), wv.detach().contiguous()
+    buf = torch.empty(n, dtype=torch.uint8, device=wv.device)
+    lib.check(L.sta_ln_qkv_pack_w(wqk.data_ptr(), wv.data_ptr(), buf.data_ptr(), C, _DT[wv.dtype], _stream()), "sta_ln_qkv_pack_w")
+    return buf
+
+
+def ln_qkv(x, bias, ln_weight, ln_bias, eps, w_packed, store_sum=True, y_dbg=None):
+    """s = x + bias; y = LayerNorm(s); returns (s, qk, vt): qk [.., 2C] = y [Wq'; Wk]^T row-major, vt [C, rows] = Wv y^T — what
+    sta.ops.self_attention reads as qk[..., :C], qk[..., C:], vt.view(C, B, N).permute(1, 0, 2). y never reaches HBM unless a test
+    hands in `y_dbg` (a tensor like x), which then receives it row-major, bit-identical to add_layernorm's. s is None if store_sum is False."""
+    C = x.shape[-1]
+    R = x.numel() // C
+    x = x.contiguous()
+    s = torch.empty_like(x) if store_sum else None
+    qk = torch.empty(*x.shape[:-1], 2 * C, dtype=x.dtype, device=x.device)
+    vt = torch.empty((C, R), dtype=x.dtype, device=x.device)
+    lib.check(lib.load().sta_ln_qkv(x.data_ptr(), _ptr(bias), ln_weight.data_ptr(), ln_bias.data_ptr(), w_packed.data_ptr(), _ptr(s), _ptr(y_dbg),
+                                    qk.data_ptr(), vt.data_ptr(), R, C, float(eps), _DT[x.dtype], _stream()), "sta_ln_qkv")
+    return s, qk, vt
+
+
 GN_STATS_FROM_PRODUCER = True   # convolutions / row GEMMs accumulate the consumer GroupNorm's statistics in their epilogue (no statistics pass)
 CONV_MIN_ITEMS = 64     # (tile, channel part) work items below which the library convolution is the faster one (a launch feeds 256 CUs:
                         # at one prompt per step the 16 x 16 / 8 x 8 levels have 16 items and lose 2 - 3 x: tools/conv_bench.py --batch 2)

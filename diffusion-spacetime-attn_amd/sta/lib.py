@@ -16,7 +16,7 @@ REPO_ROOT = os.path.dirname(PKG_ROOT)
 CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 LIB_PATH = os.path.join(CSRC, "libsta_xattn.so")
-SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip", "sta_xattn_proj.hip", "sta_xattn_proj3.hip", "sta_rowgemm.hip", "sta_ffgemm.hip", "sta_conv.hip", "sta_gemm.hip", "sta_selfattn.hip", "sta_selfattn_bwd.hip", "sta_unet.hip", "sta_unet_bwd.hip", "sta_fp8.hip", "sta_mxfp8.hip", "sta_sampler.hip", "sta_encode.hip", "sta_clip.hip")]
+SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip", "sta_xattn_proj.hip", "sta_xattn_proj3.hip", "sta_rowgemm.hip", "sta_ffgemm.hip", "sta_lnqkv.hip", "sta_conv.hip", "sta_gemm.hip", "sta_selfattn.hip", "sta_selfattn_bwd.hip", "sta_unet.hip", "sta_unet_bwd.hip", "sta_fp8.hip", "sta_mxfp8.hip", "sta_sampler.hip", "sta_encode.hip", "sta_clip.hip")]
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -80,6 +80,9 @@ SYMBOLS = {
     "sta_ff_out_packed_w_bytes": (_sz, [_i, _i]),
     "sta_ff_out_pack_w": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sta_ff_out_res_hfrag": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp]),
+    "sta_ln_qkv_packed_w_bytes": (_sz, [_i]),
+    "sta_ln_qkv_pack_w": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "sta_ln_qkv": (_i, [_vp] * 9 + [_l, _i, _f, _i, _vp]),
     "sta_conv3x3_nhwc_supported": (_i, [_i, _i, _i, _i, _i]),
     "sta_conv3x3_packed_w_bytes": (_sz, [_i, _i]),
     "sta_conv3x3_pack_w": (_i, [_vp, _l, _l, _l, _l, _vp, _i, _i, _i, _vp]),

@@ -86,6 +86,22 @@ int sta_ff_out_res_hfrag(const void* h_frag, const void* packed_w, const void* b
                          int inner, int dtype, void* stream);
 
 /*
+ * The front end of the block's self-attention in one pass (csrc/sta_lnqkv.hip):
+ *     s = x + bias;  y = LayerNorm(s) * gamma + beta;  q|k = y [Wq'; Wk]^T;  V^T = Wv y^T
+ * instead of sta_add_layernorm + two library GEMMs that read y back: y never exists in HBM. bias (may be NULL) and s (may be
+ * NULL) as in sta_add_layernorm (s is stored in the activation type and normalised as stored); y is bit-identical to
+ * sta_add_layernorm's and is written row-major to y_dbg if that is not NULL (tests; NULL in the product).
+ *   wqk: [2C][C], rows 0 .. C-1 = Wq already multiplied by softmax scale * log2 e, rows C .. = Wk;  wv: [C][C];  no biases.
+ *   Re-laid out once per model by sta_ln_qkv_pack_w (sta_ln_qkv_packed_w_bytes bytes; 0 = unsupported: C = 320 only).
+ *   qk: [R][2C] row-major (columns 0 .. C-1 = q, C .. 2C-1 = k);  vt: [C][R], vt[c][r] = (y Wv^T)[r][c] — the layouts
+ *   sta_selfattn_fwd* reads (vt_row_stride = R, vt_batch_stride = N).  R % 16 == 0, R * 2C * 2 bytes < 4 GiB, fp32 accumulation.
+ */
+size_t sta_ln_qkv_packed_w_bytes(int C);
+int sta_ln_qkv_pack_w(const void* wqk, const void* wv, void* packed, int C, int dtype, void* stream);
+int sta_ln_qkv(const void* x, const void* bias, const void* gamma, const void* beta, const void* packed_w, void* s, void* y_dbg,
+               void* qk, void* vt, long R, int C, float eps, int dtype, void* stream);
+
+/*
  * The 3x3, stride-1, padding-1 convolutions of the UNet trunk on NHWC activations as an implicit GEMM on the MFMAs
  * (ResBlock in_layers / out_layers, openaimodel.py:163-275; Upsample.conv :107-120; csrc/sta_conv.hip):
  *     out = conv(x) + bias + res            (`skip_connection(x) + out_layers(h)` of ResBlock._forward in the epilogue)
