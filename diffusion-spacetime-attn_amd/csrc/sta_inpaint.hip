@@ -1,0 +1,326 @@
+// sta_inpaint.hip — layout-guided inpainting: the sampler step with the next call's re-noising blend, its backward, the blend alone
+// (first call) and the pixel-space paste of the original with its backward (gfx950). C-ABI in include/sta_unet.h.
+// Conventions of sta_sampler.hip: every lane owns 8 consecutive elements of one image, 16-byte loads and stores, fp32 arithmetic,
+// grid-stride loop under the same grid cap, coefficients computed on the host. The mask is [b][hw] fp32, broadcast over the channels:
+// with hw % 8 == 0 a lane's 8 elements never straddle a channel, so its 8 mask values are two 16-byte loads at (8 col) % hw.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "sta_xattn.h"
+#include "sta_unet.h"
+#include "sta_internal.h"
+
+namespace {
+
+template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
+typedef float F4 __attribute__((ext_vector_type(4)));
+
+struct StepCoef {
+  float scale, sigma_t, alpha_t;
+  float c_x, c_m, c_p, c_e, c_n;
+};
+
+__device__ __forceinline__ void load8(const float* p, float* v) {
+  const F4 a = *(const F4*)p, b = *(const F4*)(p + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[e] = a[e];
+    v[4 + e] = b[e];
+  }
+}
+
+__device__ __forceinline__ void store8(float* p, const float* v) {
+  F4 a, b;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    a[e] = v[e];
+    b[e] = v[4 + e];
+  }
+  *(F4*)p = a;
+  *(F4*)(p + 4) = b;
+}
+
+// keep (q_a x0 + q_b n) + (1 - keep) x; keep == 0 hands x through untouched (bit-equal to the unmasked step, signed zeros included)
+__device__ __forceinline__ float blend1(float kp, float x0, float n, float x, float q_a, float q_b) {
+  const float q = q_a * x0 + q_b * n;
+  return kp == 0.f ? x : kp * q + (1.0f - kp) * x;
+}
+
+// sta_sampler_step's arithmetic for call i (same expressions, same order), then the blend of call i + 1 on x_next.
+template <typename T>
+__global__ __launch_bounds__(256) void sampler_step_masked_kernel(const T* __restrict__ eps, const float* __restrict__ x,
+                                                                  const float* __restrict__ m_prev, const float* __restrict__ noise,
+                                                                  const float* __restrict__ x0, const float* __restrict__ keep,
+                                                                  const float* __restrict__ qnoise, float* __restrict__ x_next,
+                                                                  float* __restrict__ m, T* __restrict__ xin, long nvec, long rowvec,
+                                                                  long hw, StepCoef c, float q_a, float q_b) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const long img = v / rowvec, col = v - img * rowvec;
+    const V8 eu = ((const V8*)eps)[2 * img * rowvec + col];
+    const V8 ec = ((const V8*)eps)[(2 * img + 1) * rowvec + col];
+    float xv[8], mp[8], nz[8], xn[8], mv[8], z0[8], kp[8], qn[8];
+    load8(x + 8 * v, xv);
+    if (m_prev) load8(m_prev + 8 * v, mp);
+    if (noise) load8(noise + 8 * v, nz);
+    load8(x0 + 8 * v, z0);
+    load8(qnoise + 8 * v, qn);
+    load8(keep + img * hw + (8 * col) % hw, kp);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float u = (float)eu[k];
+      const float e = u + c.scale * ((float)ec[k] - u);
+      mv[k] = (xv[k] - c.sigma_t * e) / c.alpha_t;
+      float t = c.c_x * xv[k] + c.c_m * mv[k] + c.c_e * e;
+      if (m_prev) t += c.c_p * mp[k];
+      if (noise) t += c.c_n * nz[k];
+      xn[k] = blend1(kp[k], z0[k], qn[k], t, q_a, q_b);
+    }
+    store8(x_next + 8 * v, xn);
+    store8(m + 8 * v, mv);
+    if (xin) {
+      V8 o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = (T)xn[k];
+      ((V8*)xin)[2 * img * rowvec + col] = o;
+      ((V8*)xin)[(2 * img + 1) * rowvec + col] = o;
+    }
+  }
+}
+
+// sta_sampler_step_bwd with the incoming g_xn (the gradient of the BLENDED state) scaled by (1 - keep): x0, keep and the blend noise
+// are constants of the graph.
+template <typename T>
+__global__ __launch_bounds__(256) void sampler_step_masked_bwd_kernel(const float* __restrict__ g_xn, const float* __restrict__ g_m,
+                                                                      const float* __restrict__ keep, float* __restrict__ g_x,
+                                                                      T* __restrict__ g_eps, float* __restrict__ g_mprev, long nvec,
+                                                                      long rowvec, long hw, StepCoef c) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  const float inv_a = 1.0f / c.alpha_t;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const long img = v / rowvec, col = v - img * rowvec;
+    float gn[8], gm[8], gx[8], gp[8], kp[8];
+    load8(g_xn + 8 * v, gn);
+    if (g_m) load8(g_m + 8 * v, gm);
+    load8(keep + img * hw + (8 * col) % hw, kp);
+    V8 gu, gc;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float g = (1.0f - kp[k]) * gn[k];
+      const float Gm = (g_m ? gm[k] : 0.f) + c.c_m * g;
+      gx[k] = c.c_x * g + Gm * inv_a;
+      const float ge = c.c_e * g - c.sigma_t * inv_a * Gm;
+      gu[k] = (T)((1.0f - c.scale) * ge);
+      gc[k] = (T)(c.scale * ge);
+      gp[k] = c.c_p * g;
+    }
+    store8(g_x + 8 * v, gx);
+    ((V8*)g_eps)[2 * img * rowvec + col] = gu;
+    ((V8*)g_eps)[(2 * img + 1) * rowvec + col] = gc;
+    if (g_mprev) store8(g_mprev + 8 * v, gp);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void latent_blend_kernel(const float* __restrict__ x, const float* __restrict__ x0,
+                                                           const float* __restrict__ keep, const float* __restrict__ noise,
+                                                           float* __restrict__ x_out, T* __restrict__ xin, long nvec, long rowvec, long hw,
+                                                           float q_a, float q_b) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const long img = v / rowvec, col = v - img * rowvec;
+    float xv[8], z0[8], kp[8], qn[8], xo[8];
+    load8(x + 8 * v, xv);
+    load8(x0 + 8 * v, z0);
+    load8(noise + 8 * v, qn);
+    load8(keep + img * hw + (8 * col) % hw, kp);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) xo[k] = blend1(kp[k], z0[k], qn[k], xv[k], q_a, q_b);
+    store8(x_out + 8 * v, xo);
+    if (xin) {
+      V8 o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = (T)xo[k];
+      ((V8*)xin)[2 * img * rowvec + col] = o;
+      ((V8*)xin)[(2 * img + 1) * rowvec + col] = o;
+    }
+  }
+}
+
+// out = keep_px orig + (1 - keep_px) clamp((dec + 1) / 2, 0, 1), rounded to T once. rowvec = 3 HW / 8 lanes per image.
+template <typename T>
+__global__ __launch_bounds__(256) void image_composite_kernel(const T* __restrict__ dec, const float* __restrict__ orig,
+                                                              const float* __restrict__ keep_px, T* __restrict__ out, long nvec,
+                                                              long rowvec, long hw) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const long img = v / rowvec, col = v - img * rowvec;
+    const V8 d = ((const V8*)dec)[v];
+    float og[8], kp[8];
+    load8(orig + 8 * v, og);
+    load8(keep_px + img * hw + (8 * col) % hw, kp);
+    V8 o;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float g = fminf(fmaxf(((float)d[k] + 1.0f) * 0.5f, 0.0f), 1.0f);
+      o[k] = (T)(kp[k] * og[k] + (1.0f - kp[k]) * g);
+    }
+    ((V8*)out)[v] = o;
+  }
+}
+
+// g_dec = 0.5 (1 - keep_px) g where -1 <= dec <= 1 (inclusive, torch.clamp's gradient), 0 elsewhere.
+template <typename T>
+__global__ __launch_bounds__(256) void image_composite_bwd_kernel(const T* __restrict__ g, const T* __restrict__ dec,
+                                                                  const float* __restrict__ keep_px, T* __restrict__ g_dec, long nvec,
+                                                                  long rowvec, long hw) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const long img = v / rowvec, col = v - img * rowvec;
+    const V8 d = ((const V8*)dec)[v], gv = ((const V8*)g)[v];
+    float kp[8];
+    load8(keep_px + img * hw + (8 * col) % hw, kp);
+    V8 o;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float dv = (float)d[k];
+      const bool inside = dv >= -1.0f && dv <= 1.0f;
+      o[k] = (T)(inside ? 0.5f * (1.0f - kp[k]) * (float)gv[k] : 0.0f);
+    }
+    ((V8*)g_dec)[v] = o;
+  }
+}
+
+bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
+
+int launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : sta_fail(STA_E_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+}
+
+unsigned grid_for(long nvec) {
+  long blocks = (nvec + 255) / 256;
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  return (unsigned)blocks;
+}
+
+// b images of n elements, masks of hw: n a whole number of hw-sized channels, hw % 8 == 0
+int check_sizes(const char* what, long b, long n, long hw) {
+  if (b <= 0 || n <= 0 || hw <= 0 || hw % 8 || n % hw)
+    return sta_fail(STA_E_ARG, "%s: b=%ld n=%ld hw=%ld (need hw %% 8 == 0 and n a multiple of hw)", what, b, n, hw);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sta_sampler_step_masked(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0, const float* keep,
+                            const float* qnoise, float* x_next, float* m, void* xin, long b, long n, long hw, float scale, float sigma_t,
+                            float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype,
+                            void* stream) {
+  g_sta_err[0] = 0;
+  if (!eps || !x || !x_next || !m) return sta_fail(STA_E_ARG, "null pointer");
+  if (!x0 || !keep || !qnoise) return sta_fail(STA_E_ARG, "sampler_step_masked: x0, keep and qnoise are required (null pointer)");
+  if (check_sizes("sampler_step_masked", b, n, hw)) return STA_E_ARG;
+  if (!aligned16(eps) || !aligned16(x) || !aligned16(m_prev) || !aligned16(noise) || !aligned16(x0) || !aligned16(keep) ||
+      !aligned16(qnoise) || !aligned16(x_next) || !aligned16(m) || !aligned16(xin))
+    return sta_fail(STA_E_ARG, "sampler_step_masked: every tensor must be 16-byte aligned");
+  if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_masked: alpha_t == 0");
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
+  const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
+  const long rowvec = n / 8, nvec = b * rowvec;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == STA_BF16)
+    hipLaunchKernelGGL(sampler_step_masked_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const __bf16*)eps, x, m_prev, noise, x0,
+                       keep, qnoise, x_next, m, (__bf16*)xin, nvec, rowvec, hw, c, q_a, q_b);
+  else
+    hipLaunchKernelGGL(sampler_step_masked_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const _Float16*)eps, x, m_prev, noise,
+                       x0, keep, qnoise, x_next, m, (_Float16*)xin, nvec, rowvec, hw, c, q_a, q_b);
+  return launched("sampler_step_masked");
+}
+
+int sta_sampler_step_masked_bwd(const float* g_xn, const float* g_m, const float* keep, float* g_x, void* g_eps, float* g_mprev, long b,
+                                long n, long hw, float scale, float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e,
+                                int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!g_xn || !g_x || !g_eps) return sta_fail(STA_E_ARG, "null pointer");
+  if (!keep) return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: keep is required (null pointer)");
+  if (check_sizes("sampler_step_masked_bwd", b, n, hw)) return STA_E_ARG;
+  if (!aligned16(g_xn) || !aligned16(g_m) || !aligned16(keep) || !aligned16(g_x) || !aligned16(g_eps) || !aligned16(g_mprev))
+    return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: every tensor must be 16-byte aligned");
+  if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: alpha_t == 0");
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
+  const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, 0.f};
+  const long rowvec = n / 8, nvec = b * rowvec;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == STA_BF16)
+    hipLaunchKernelGGL(sampler_step_masked_bwd_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, g_xn, g_m, keep, g_x, (__bf16*)g_eps,
+                       g_mprev, nvec, rowvec, hw, c);
+  else
+    hipLaunchKernelGGL(sampler_step_masked_bwd_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, g_xn, g_m, keep, g_x,
+                       (_Float16*)g_eps, g_mprev, nvec, rowvec, hw, c);
+  return launched("sampler_step_masked_bwd");
+}
+
+int sta_latent_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long b, long n, long hw,
+                     float q_a, float q_b, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!x || !x0 || !keep || !noise || !x_out) return sta_fail(STA_E_ARG, "latent_blend: null pointer");
+  if (check_sizes("latent_blend", b, n, hw)) return STA_E_ARG;
+  if (!aligned16(x) || !aligned16(x0) || !aligned16(keep) || !aligned16(noise) || !aligned16(x_out) || !aligned16(xin))
+    return sta_fail(STA_E_ARG, "latent_blend: every tensor must be 16-byte aligned");
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
+  const long rowvec = n / 8, nvec = b * rowvec;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == STA_BF16)
+    hipLaunchKernelGGL(latent_blend_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, x, x0, keep, noise, x_out, (__bf16*)xin, nvec,
+                       rowvec, hw, q_a, q_b);
+  else
+    hipLaunchKernelGGL(latent_blend_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, x, x0, keep, noise, x_out, (_Float16*)xin, nvec,
+                       rowvec, hw, q_a, q_b);
+  return launched("latent_blend");
+}
+
+int sta_image_composite(const void* dec, const float* orig, const float* keep_px, void* out, long b, long hw, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!dec || !orig || !keep_px || !out) return sta_fail(STA_E_ARG, "image_composite: null pointer");
+  if (check_sizes("image_composite", b, 3 * hw, hw)) return STA_E_ARG;
+  if (!aligned16(dec) || !aligned16(orig) || !aligned16(keep_px) || !aligned16(out))
+    return sta_fail(STA_E_ARG, "image_composite: every tensor must be 16-byte aligned");
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
+  const long rowvec = 3 * hw / 8, nvec = b * rowvec;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == STA_BF16)
+    hipLaunchKernelGGL(image_composite_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const __bf16*)dec, orig, keep_px, (__bf16*)out,
+                       nvec, rowvec, hw);
+  else
+    hipLaunchKernelGGL(image_composite_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const _Float16*)dec, orig, keep_px,
+                       (_Float16*)out, nvec, rowvec, hw);
+  return launched("image_composite");
+}
+
+int sta_image_composite_bwd(const void* g, const void* dec, const float* keep_px, void* g_dec, long b, long hw, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!g || !dec || !keep_px || !g_dec) return sta_fail(STA_E_ARG, "image_composite_bwd: null pointer");
+  if (check_sizes("image_composite_bwd", b, 3 * hw, hw)) return STA_E_ARG;
+  if (!aligned16(g) || !aligned16(dec) || !aligned16(keep_px) || !aligned16(g_dec))
+    return sta_fail(STA_E_ARG, "image_composite_bwd: every tensor must be 16-byte aligned");
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
+  const long rowvec = 3 * hw / 8, nvec = b * rowvec;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == STA_BF16)
+    hipLaunchKernelGGL(image_composite_bwd_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const __bf16*)g, (const __bf16*)dec,
+                       keep_px, (__bf16*)g_dec, nvec, rowvec, hw);
+  else
+    hipLaunchKernelGGL(image_composite_bwd_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const _Float16*)g, (const _Float16*)dec,
+                       keep_px, (_Float16*)g_dec, nvec, rowvec, hw);
+  return launched("image_composite_bwd");
+}
+
+}  // extern "C"

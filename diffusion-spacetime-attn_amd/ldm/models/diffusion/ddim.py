@@ -9,6 +9,10 @@ W[K, S]. The step after each call is one sta_sampler_step launch (sta.solver).
 Noise (eta > 0): by default torch.randn on the device after each call, in the reference's order (noise_like, ddim.py:199).
 `noise=` replaces it: a list of pre-drawn tensors (index = call of the trajectory or decode) or a callable (i, shape, device) -> tensor.
 
+Inpainting (reference ddim.py:144-147): `mask=` (1 = keep the original) / `x0=` on sample, sample_batch, decode and decode_batch re-noise
+the kept region from x0 before every UNet call, fused into the step launch (SolverSamplerBase); `mask_noise=` is the hook for that
+noise, of the same shape as `noise=`. The blend draw of a call comes before its eta draw, as in the reference's loop.
+
 img2img (reference ddim.py:207-245, scripts/img2img.py): `stochastic_encode(x0, t)` noises a latent to DDIM table index t, and
 `decode(x, cond, t_start, ...)` runs the last t_start DDIM timesteps on the spatial-temporal UNet, with the keywords `sample()` takes.
 Weight columns are tied to timesteps: call j of a t_start-call decode runs at the timestep of call S - t_start + j of a full S-call
@@ -27,8 +31,8 @@ from sta import solver
 class DDIMSampler(SolverSamplerBase):
     t_dtype = torch.long
 
-    def __init__(self, model, schedule="linear", noise=None, **kwargs):
-        super().__init__(model, schedule=schedule, **kwargs)
+    def __init__(self, model, schedule="linear", noise=None, mask_noise=None, **kwargs):
+        super().__init__(model, schedule=schedule, mask_noise=mask_noise, **kwargs)
         self.noise = noise
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=True):
@@ -42,6 +46,9 @@ class DDIMSampler(SolverSamplerBase):
 
     def _coef(self, i, scale):
         return solver.ddim_coefs(self.tables, i, scale)
+
+    def _blend_coefs(self, i):
+        return solver.blend_coefs(self.model.alphas_cumprod, int(self.tables["t_in"][i]))     # q_sample at the call's integer timestep
 
     def _noise(self, i, x):
         if self.noise is None:
@@ -98,23 +105,28 @@ class DDIMSampler(SolverSamplerBase):
         return S - int(t_start)
 
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None, use_original_steps=False,
-               text_index=0, curr_text="", bboxs_curr=None, seed=0, prompt_idx=0, object_names=None, local_conditionings=None, xin=None):
+               text_index=0, curr_text="", bboxs_curr=None, seed=0, prompt_idx=0, object_names=None, local_conditionings=None, xin=None,
+               mask=None, x0=None, image=None, mask_px=None):
         """The last t_start DDIM timesteps from x_latent (reference ddim.py:223-245), on the spatial-temporal UNet with the blend
         weights and the per-prompt keywords of `sample()`; `opt_epochs` optimises W through the same epoch loop (every epoch restarts
-        from x_latent). xin: the first call's 16-bit input pair (encode_step), GPU fixed-weight decodes only. Returns the latent."""
+        from x_latent). xin: the first call's 16-bit input pair (encode_step), GPU fixed-weight decodes only. Returns the latent.
+        mask= / x0= (image= / mask_px=): inpainting, as `sample()`; the first decode call is blended too (a given xin is then replaced by
+        the blended state's pair)."""
         start = self._decode_start(t_start, use_original_steps)
         self._start, self._xin0 = start, xin
         try:
+            self._set_inpaint(mask, x0, image, mask_px, batch=x_latent.shape[0])
             self.plms_sampling(cond, tuple(x_latent.shape), x_T=x_latent.float(), unconditional_guidance_scale=unconditional_guidance_scale,
                                unconditional_conditioning=unconditional_conditioning, text_index=text_index, curr_text=curr_text,
                                bboxs_curr=bboxs_curr, seed=seed, prompt_idx=prompt_idx, object_names=object_names,
                                local_conditionings=local_conditionings)
         finally:
-            self._start, self._xin0 = 0, None
+            self._start, self._xin0, self._inpaint = 0, None, None
         return self.last_result["x0"]
 
     def decode_batch(self, x_latents, conditionings, unconditional_conditionings, bboxs, object_names, local_conditionings, t_start,
-                     curr_texts=None, unconditional_guidance_scale=7.5, seed=1, prompt_indices=None, xin=None):
+                     curr_texts=None, unconditional_guidance_scale=7.5, seed=1, prompt_indices=None, xin=None, mask=None, x0=None,
+                     image=None, mask_px=None):
         """`decode` for I prompts in ONE CFG batch of 2I per UNet call (the counterpart of `sample_batch`): per-image lists, every image
         keeps its own latent, W[i] and Adam state, so image i equals `decode(...)` on prompt i alone."""
         start = self._decode_start(t_start, False)
@@ -124,11 +136,12 @@ class DDIMSampler(SolverSamplerBase):
             else unconditional_conditionings.expand(I, -1, -1)
         self._start, self._xin0 = start, xin
         try:
+            self._set_inpaint(mask, x0, image, mask_px, batch=I)
             self.plms_sampling(cond, tuple(x_latents.shape), x_T=x_latents.float(), unconditional_guidance_scale=unconditional_guidance_scale,
                                unconditional_conditioning=uncond, text_index=0,
                                curr_text=list(curr_texts) if curr_texts is not None else [""] * I, bboxs_curr=list(bboxs), seed=seed,
                                prompt_idx=list(prompt_indices) if prompt_indices is not None else list(range(I)),
                                object_names=list(object_names), local_conditionings=list(local_conditionings), batched=True)
         finally:
-            self._start, self._xin0 = 0, None
+            self._start, self._xin0, self._inpaint = 0, None, None
         return self.last_result["x0"]

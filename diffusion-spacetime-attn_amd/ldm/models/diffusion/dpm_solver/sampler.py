@@ -9,6 +9,8 @@ never ran on the spatial-temporal UNet. Here the same solver drives apply_model_
   * the step after each call — CFG combine, data prediction, update, next input — is one sta_sampler_step launch (sta.solver).
 `--ddim_eta` is ignored, as in the reference. Weight optimisation, loss scaling, graphs: as PLMSSampler.
 """
+import numpy as np
+
 from ldm.models.diffusion.plms import SolverSamplerBase
 from sta import solver
 
@@ -21,3 +23,8 @@ class DPMSolverSampler(SolverSamplerBase):
 
     def _coef(self, i, scale):
         return solver.dpm_coefs(self.tables, i, scale)
+
+    def _blend_coefs(self, i):
+        """Inpainting: the marginal of the call's continuous time, x = alpha(t_i) x0 + sigma(t_i) n (float32 schedule values). The
+        reference never combined its mask path with this solver; the blend is DDIM's, at the solver's own noise level."""
+        return float(np.float32(self.tables["alpha_t"][i])), float(np.float32(self.tables["sigma_t"][i]))

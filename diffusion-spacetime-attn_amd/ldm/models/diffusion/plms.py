@@ -332,7 +332,11 @@ class PLMSSampler(object):
                                            time_range, W if batched else W[0], block_boxes, text_index,
                                            graph=self.use_graph and (not track or by_call), call_recompute=by_call)
                     x_img = None
-                    if self.model.first_stage_model is not None:
+                    if self.model.first_stage_model is not None and self._paste() is not None:
+                        # inpainting with a pixel-space pair: the result (and what the loss sees) is the original outside the mask
+                        from sta import solver as _solver
+                        x_img = _solver.image_composite(self.model.decode_first_stage(img), *self._paste())
+                    elif self.model.first_stage_model is not None:
                         x_img = torch.clamp((self.model.decode_first_stage(img) + 1.0) / 2.0, min=0.0, max=1.0)   # :249-250
                     if track:
                         lm = self.clip_loss_model
@@ -360,7 +364,7 @@ class PLMSSampler(object):
                               W=(W if batched else W[0]).detach().clone())
                 if self.save_images and x_img is not None:
                     for i in range(b):
-                        self._save(x_img[i], epochs - 1, seed, pidx[i])
+                        self._save(x_img[i], epochs - 1, seed, pidx[i], index=i)
         self.last_result = result
         return None
 
@@ -383,9 +387,16 @@ class PLMSSampler(object):
             loss = loss + self.local_loss_weight * lm.forward_3(image[:, y1:y2, x1:x2], "A photo of " + obj)   # :268-273
         return loss.sum()
 
-    def _save(self, image, epoch, seed, prompt_idx):
+    def _paste(self):
+        """(orig [b, 3, H, W] in [0, 1], keep_px [b, 1, H, W]) of an inpainting call with a pixel-space pair, else None."""
+        return None
+
+    def _to_u8(self, image, index=0):
+        return (255.0 * image.detach().float().cpu().numpy().transpose(1, 2, 0)).astype(np.uint8)
+
+    def _save(self, image, epoch, seed, prompt_idx, index=0):
         from PIL import Image
-        arr = (255.0 * image.detach().float().cpu().numpy().transpose(1, 2, 0)).astype(np.uint8)
+        arr = self._to_u8(image, index)
         os.makedirs(self.outdir, exist_ok=True)
         Image.fromarray(arr).save(os.path.join(self.outdir, "final%d_s%d_index_%d.png" % (epoch, seed, prompt_idx)))
 
@@ -521,15 +532,100 @@ class SolverSamplerBase(PLMSSampler):
     Call i uses column i of W[K, S]. With fixed weights on the GPU the kernel also writes the next call's 16-bit input pair, so
     nothing but the (graph-replayed) UNet call and that one launch runs per step; tracked epochs differentiate through
     sta.solver.SolverStepFn (backward = sta_sampler_step_bwd), per-call recomputation included.
+    Inpainting (`mask=` / `x0=`): sta_latent_blend re-noises the kept region before the first call, and the step of calls
+    start .. S - 2 is sta_sampler_step_masked, which blends for the NEXT call in the same launch (tracked: SolverStepMaskedFn); the
+    last call takes the plain step. Draw order: blend draw of call i, eta draw of call i, blend draw of call i + 1, ...
     A trajectory may start at call `_start` > 0 (DDIMSampler.decode: img2img): calls _start .. S - 1 run, with columns _start .. S - 1,
     and `_xin0` (if set) is the first call's 16-bit input pair, written by the fused encode step."""
     t_dtype = torch.float32
     tables = None
     _start = 0
     _xin0 = None
+    _inpaint = None          # dict(x0, keep, image, keep_px) while a masked call runs (set like _start / _xin0, cleared in `finally`)
+    mask_noise = None        # the blend noise n_i: None (torch.randn on the device), a list indexed by call, or callable (i, shape, device)
+
+    def __init__(self, model, schedule="linear", mask_noise=None, **kwargs):
+        super().__init__(model, schedule=schedule, **kwargs)
+        self.mask_noise = mask_noise
 
     def _first_call(self):
         return self._start
+
+    # ------------------------------------------------------------------------------------------------ inpainting
+    def _set_inpaint(self, mask, x0, image=None, mask_px=None, batch=None):
+        """Checks and keeps the inpaint state of one call. mask: keep [b, 1, h, w] in [0, 1], 1 = keep the original (the reference's
+        convention, ddim.py:147); x0 [b, 4, h, w]: the clean latent; image / mask_px: the original [b, 3, H, W] in [0, 1] and its keep
+        mask [b, 1, H, W] for the pixel-space paste. Per-image lists are concatenated."""
+        cat = lambda v: torch.cat([t for t in v]) if isinstance(v, (list, tuple)) else v
+        mask, x0, image, mask_px = cat(mask), cat(x0), cat(image), cat(mask_px)
+        if mask is None and x0 is None and image is None and mask_px is None:
+            return False
+        if mask is None or x0 is None:
+            raise ValueError("inpainting needs both mask= and x0= (reference ddim.py:145: assert x0 is not None)")
+        if (image is None) != (mask_px is None):
+            raise ValueError("the pixel-space paste needs both image= and mask_px=")
+        dev = self.model.device
+        mask, x0 = mask.detach().to(dev, torch.float32), x0.detach().to(dev, torch.float32)
+        if mask.dim() != 4 or mask.shape[1] != 1 or x0.dim() != 4 or mask.shape[0] != x0.shape[0] or mask.shape[-2:] != x0.shape[-2:]:
+            raise ValueError("mask %s must be [b, 1, h, w] for x0 %s" % (tuple(mask.shape), tuple(x0.shape)))
+        if batch is not None and x0.shape[0] != batch:
+            raise ValueError("x0 holds %d latents for a batch of %d" % (x0.shape[0], batch))
+        if float(mask.min()) < 0.0 or float(mask.max()) > 1.0:
+            raise ValueError("mask values must lie in [0, 1]")
+        if image is not None:
+            image, mask_px = image.detach().to(dev, torch.float32), mask_px.detach().to(dev, torch.float32)
+            if image.dim() != 4 or image.shape[0] != x0.shape[0] or tuple(mask_px.shape) != (image.shape[0], 1) + tuple(image.shape[-2:]):
+                raise ValueError("image %s / mask_px %s must be [b, 3, H, W] / [b, 1, H, W]" % (tuple(image.shape), tuple(mask_px.shape)))
+        self._inpaint = dict(x0=x0, keep=mask, image=image, keep_px=mask_px)
+        return True
+
+    def _paste(self):
+        inp = self._inpaint
+        return None if inp is None or inp["image"] is None else (inp["image"], inp["keep_px"])
+
+    def _to_u8(self, image, index=0):
+        """The saved pixels: where keep_px == 1 exactly the original's 8-bit values (a 16-bit composite does not round-trip them)."""
+        arr = super()._to_u8(image, index)
+        if self._paste() is not None:
+            orig, keep_px = self._paste()
+            kept = (keep_px[index, 0] == 1.0).cpu().numpy()
+            o8 = np.rint(255.0 * orig[index].float().cpu().numpy().transpose(1, 2, 0)).astype(np.uint8)
+            arr[kept] = o8[kept]
+        return arr
+
+    def _blend_coefs(self, i):
+        """(q_a, q_b) of q_sample at call i: the state the call's UNet input carries is q_a x0 + q_b n."""
+        raise NotImplementedError
+
+    def _mask_noise(self, j, x):
+        if self.mask_noise is None:
+            return torch.randn(x.shape, device=x.device)
+        if callable(self.mask_noise):
+            return self.mask_noise(j, tuple(x.shape), x.device)
+        return self.mask_noise[j].to(x.device)
+
+    def _blend(self, i, x):
+        from sta import solver
+        inp = self._inpaint
+        q_a, q_b = self._blend_coefs(i)
+        return solver.Blend(inp["x0"], inp["keep"], self._mask_noise(i - self._start, x), q_a, q_b)
+
+    def sample(self, S, batch_size, shape, conditioning=None, mask=None, x0=None, image=None, mask_px=None, **kwargs):
+        """PLMSSampler.sample's keywords; with mask= / x0= the kept region (mask == 1) is re-noised from x0 before every UNet call
+        (reference ddim.py:144-147), with image= / mask_px= the original is pasted over the decoded image (sta_image_composite)."""
+        try:
+            self._set_inpaint(mask, x0, image, mask_px, batch=batch_size)
+            return super().sample(S, batch_size, shape, conditioning=conditioning, **kwargs)
+        finally:
+            self._inpaint = None
+
+    def sample_batch(self, S, shape, conditionings, *args, mask=None, x0=None, image=None, mask_px=None, **kwargs):
+        """PLMSSampler.sample_batch with per-image masks and latents (lists of [1, ...] tensors, or stacked)."""
+        try:
+            self._set_inpaint(mask, x0, image, mask_px, batch=len(conditionings))
+            return super().sample_batch(S, shape, conditionings, *args, **kwargs)
+        finally:
+            self._inpaint = None
 
     def _time_range(self):
         return self.tables["t_in"]
@@ -553,15 +649,21 @@ class SolverSamplerBase(PLMSSampler):
                                    n_calls=S - start, raw=True)
         wdtype = next(self.model.model.parameters()).dtype
         fast = img.is_cuda and not grad
+        masked = self._inpaint is not None
         x, m_prev = img, None
         xin = None
-        if fast:
+        if masked:           # the blend of the first call (also when decoding from an encoded latent, as the reference does)
+            x, xin = solver.latent_blend(x, self._blend(start, x), dtype=wdtype, want_xin=fast)
+        elif fast:
             xin = self._xin0 if self._xin0 is not None else solver._pair(img).to(wdtype)
         for i in range(start, S):
             t_val = float(time_range[i]) if self.t_dtype.is_floating_point else int(time_range[i])
             t = torch.full((b,), t_val, device=device, dtype=self.t_dtype)
             out = eps_fn(x if xin is None else xin, t, W[..., i])
             c = self._coef(i, scale)
-            noise = self._noise(i - start, x) if c.c_n else None
-            x, m_prev, xin = solver.solver_step(out, x, m_prev, noise, c, dtype=wdtype, want_xin=fast and i + 1 < S)
+            noise = self._noise(i - start, x) if c.c_n else None           # the eta draw of call i, then the blend draw of call i + 1
+            if masked and i + 1 < S:
+                x, m_prev, xin = solver.solver_step_masked(out, x, m_prev, noise, c, self._blend(i + 1, x), dtype=wdtype, want_xin=fast)
+            else:            # no blend after the last step (the reference has none either)
+                x, m_prev, xin = solver.solver_step(out, x, m_prev, noise, c, dtype=wdtype, want_xin=fast and i + 1 < S)
         return x

@@ -16,7 +16,7 @@ REPO_ROOT = os.path.dirname(PKG_ROOT)
 CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 LIB_PATH = os.path.join(CSRC, "libsta_xattn.so")
-SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip", "sta_xattn_proj.hip", "sta_xattn_proj3.hip", "sta_rowgemm.hip", "sta_ffgemm.hip", "sta_lnqkv.hip", "sta_conv.hip", "sta_gemm.hip", "sta_selfattn.hip", "sta_selfattn_bwd.hip", "sta_unet.hip", "sta_unet_bwd.hip", "sta_fp8.hip", "sta_mxfp8.hip", "sta_sampler.hip", "sta_encode.hip", "sta_clip.hip")]
+SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip", "sta_xattn_proj.hip", "sta_xattn_proj3.hip", "sta_rowgemm.hip", "sta_ffgemm.hip", "sta_lnqkv.hip", "sta_conv.hip", "sta_gemm.hip", "sta_selfattn.hip", "sta_selfattn_bwd.hip", "sta_unet.hip", "sta_unet_bwd.hip", "sta_fp8.hip", "sta_mxfp8.hip", "sta_sampler.hip", "sta_encode.hip", "sta_clip.hip", "sta_inpaint.hip")]
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -115,6 +115,11 @@ SYMBOLS = {
     "sta_vae_encode_step": (_i, [_vp] * 8 + [_l, _l, _f, _f, _f, _i, _vp]),
     "sta_clip_views": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
     "sta_clip_views_bwd": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    "sta_sampler_step_masked": (_i, [_vp] * 10 + [_l, _l, _l] + [_f] * 10 + [_i, _vp]),
+    "sta_sampler_step_masked_bwd": (_i, [_vp] * 6 + [_l, _l, _l] + [_f] * 7 + [_i, _vp]),
+    "sta_latent_blend": (_i, [_vp] * 6 + [_l, _l, _l, _f, _f, _i, _vp]),
+    "sta_image_composite": (_i, [_vp] * 4 + [_l, _l, _i, _vp]),
+    "sta_image_composite_bwd": (_i, [_vp] * 4 + [_l, _l, _i, _vp]),
 }
 
 

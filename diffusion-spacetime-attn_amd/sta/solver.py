@@ -15,6 +15,13 @@ The coefficients are computed here as the reference computes them:
 
 `solver_step` runs the HIP kernel for CUDA tensors and a torch restatement of the same formula for CPU tensors (the CPU golden
 tests); under autograd on CUDA it is `SolverStepFn`, whose backward is sta_sampler_step_bwd.
+
+Inpainting (csrc/sta_inpaint.hip): before UNet call i at integer timestep t_i the kept region is re-noised,
+    x <- keep (q_a x0 + q_b n_i) + (1 - keep) x,   q_a = sqrt(acp[t_i]), q_b = sqrt(1 - acp[t_i])   (reference ddim.py:144-147),
+with keep [b, 1, h, w] in [0, 1] (1 = keep the original), x0 and n_i constants of the graph. A `Blend` carries one call's
+(x0, keep, noise, q_a, q_b). `latent_blend` is the blend alone (first call); `solver_step_masked` is the step of call i followed by the
+blend of call i + 1 in the same launch (sta_sampler_step_masked; `SolverStepMaskedFn` under autograd, backward =
+sta_sampler_step_masked_bwd). `image_composite` pastes the original image over the decoded one in pixel space (sta_image_composite).
 """
 from collections import namedtuple
 
@@ -24,6 +31,7 @@ import torch
 from sta import lib
 
 StepCoef = namedtuple("StepCoef", "scale sigma_t alpha_t c_x c_m c_p c_e c_n")
+Blend = namedtuple("Blend", "x0 keep noise q_a q_b")
 _DT = {torch.bfloat16: lib.STA_BF16, torch.float16: lib.STA_F16}
 
 
@@ -210,3 +218,169 @@ def solver_step(eps, x, m_prev, noise, c, dtype=None, want_xin=False):
         return x_next, m, (_pair(x_next.detach()).to(dtype or eps.dtype) if want_xin else None)
     e16, xc, mp, nz = _prep(eps, x, m_prev, noise, c, dtype)
     return _launch_fwd(e16, xc, mp, nz, c, want_xin)
+
+
+# ---------------------------------------------------------------------------------------------------- inpainting
+def blend_coefs(alphas_cumprod, t):
+    """(sqrt(acp[t]), sqrt(1 - acp[t])) of q_sample at integer timestep t: float32 square roots of the float32 schedule, as
+    DDIMSampler._encode_coefs(use_original_steps=True)."""
+    f32 = np.float32
+    a = f32(torch.as_tensor(alphas_cumprod).detach().to("cpu", torch.float32)[int(t)].item())
+    return float(np.sqrt(a)), float(np.sqrt(f32(f32(1.0) - a)))
+
+
+def blend_reference(x, bl):
+    """The blend in torch (any device, arithmetic in x's dtype). Differentiable in x: (1 - keep) of the gradient flows back."""
+    keep = bl.keep.to(x.dtype)
+    return keep * (bl.q_a * bl.x0.to(x.dtype) + bl.q_b * bl.noise.to(x.dtype)) + (1.0 - keep) * x
+
+
+def step_reference_masked(eps, x, m_prev, noise, c, bl):
+    """step_reference for call i, then the blend of call i + 1 on x_next -> (blended x_next, m). Differentiable."""
+    x_next, m = step_reference(eps, x, m_prev, noise, c)
+    return blend_reference(x_next, bl), m
+
+
+def _prep_blend(x, bl):
+    b, hw = x.shape[0], x.shape[-2] * x.shape[-1]
+    if bl.x0 is None or bl.keep is None or bl.noise is None:
+        raise ValueError("a blend needs x0, keep and noise")
+    if tuple(bl.x0.shape) != tuple(x.shape) or tuple(bl.noise.shape) != tuple(x.shape):
+        raise ValueError("x0 %s / blend noise %s must have the state's shape %s" % (tuple(bl.x0.shape), tuple(bl.noise.shape), tuple(x.shape)))
+    if tuple(bl.keep.shape) != (b, 1) + tuple(x.shape[-2:]):
+        raise ValueError("keep %s must be [b, 1, h, w] of the state %s" % (tuple(bl.keep.shape), tuple(x.shape)))
+    f = lambda t: t.detach().to(x.device, torch.float32).contiguous()
+    return f(bl.x0), f(bl.keep), f(bl.noise), hw
+
+
+def latent_blend(x, bl, dtype=None, want_xin=False):
+    """The blend of the first call -> (x', xin). CUDA: sta_latent_blend (dtype: the UNet's 16-bit type of xin); CPU: blend_reference.
+    No backward: the start latent is a constant."""
+    if not x.is_cuda:
+        xb = blend_reference(x, bl)
+        return xb, (_pair(xb).to(dtype) if want_xin else None)
+    if x.dtype != torch.float32:
+        raise TypeError("sampler state x must be float32, got %s" % x.dtype)
+    if dtype not in _DT:
+        raise TypeError("sta_latent_blend writes a 16-bit input pair (dtype %s)" % dtype)
+    x0, keep, qn, hw = _prep_blend(x, bl)
+    xc = x.detach().contiguous()
+    b, n = xc.shape[0], xc[0].numel()
+    out = torch.empty_like(xc)
+    xin = torch.empty((2 * b, *xc.shape[1:]), dtype=dtype, device=x.device) if want_xin else None
+    lib.check(lib.load().sta_latent_blend(xc.data_ptr(), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(), out.data_ptr(),
+                                          0 if xin is None else xin.data_ptr(), b, n, hw, bl.q_a, bl.q_b, _DT[dtype],
+                                          torch.cuda.current_stream(x.device).cuda_stream), "sta_latent_blend")
+    return out, xin
+
+
+def _launch_fwd_masked(eps16, x, m_prev, noise, c, blend, want_xin):
+    x0, keep, qn, hw, q_a, q_b = blend
+    b, n = x.shape[0], x[0].numel()
+    x_next, m = torch.empty_like(x), torch.empty_like(x)
+    xin = torch.empty((2 * b, *x.shape[1:]), dtype=eps16.dtype, device=x.device) if want_xin else None
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    lib.check(lib.load().sta_sampler_step_masked(eps16.data_ptr(), x.data_ptr(), ptr(m_prev if c.c_p else None),
+                                                 ptr(noise if c.c_n else None), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(),
+                                                 x_next.data_ptr(), m.data_ptr(), ptr(xin), b, n, hw, c.scale, c.sigma_t, c.alpha_t, c.c_x,
+                                                 c.c_m, c.c_p, c.c_e, c.c_n, q_a, q_b, _DT[eps16.dtype],
+                                                 torch.cuda.current_stream(x.device).cuda_stream), "sta_sampler_step_masked")
+    return x_next, m, xin
+
+
+class SolverStepMaskedFn(torch.autograd.Function):
+    """(blended x_next, m) = masked step(eps, x, m_prev) on the HIP kernels; backward = sta_sampler_step_masked_bwd: (1 - keep) of the
+    gradient of the blended state flows on, x0 / keep / the noises get none."""
+
+    @staticmethod
+    def forward(ctx, eps, x, m_prev, noise, c, bl, dtype):
+        e16, xc, mp, nz = _prep(eps, x, m_prev, noise, c, dtype)
+        x0, keep, qn, hw = _prep_blend(xc, bl)
+        x_next, m, _ = _launch_fwd_masked(e16, xc, mp, nz, c, (x0, keep, qn, hw, bl.q_a, bl.q_b), False)
+        ctx.c, ctx.dt, ctx.eps_dtype, ctx.has_mprev, ctx.hw = c, e16.dtype, eps.dtype, m_prev is not None, hw
+        ctx.save_for_backward(keep)
+        return x_next, m
+
+    @staticmethod
+    def backward(ctx, g_xn, g_m):
+        c = ctx.c
+        keep, = ctx.saved_tensors
+        g_xn = g_xn.to(torch.float32).contiguous()
+        g_m = None if g_m is None else g_m.to(torch.float32).contiguous()
+        b, n = g_xn.shape[0], g_xn[0].numel()
+        g_x = torch.empty_like(g_xn)
+        g_eps = torch.empty((2 * b, *g_xn.shape[1:]), dtype=ctx.dt, device=g_xn.device)
+        g_mp = torch.empty_like(g_xn) if ctx.has_mprev and ctx.needs_input_grad[2] else None
+        lib.check(lib.load().sta_sampler_step_masked_bwd(g_xn.data_ptr(), 0 if g_m is None else g_m.data_ptr(), keep.data_ptr(),
+                                                         g_x.data_ptr(), g_eps.data_ptr(), 0 if g_mp is None else g_mp.data_ptr(), b, n,
+                                                         ctx.hw, c.scale, c.sigma_t, c.alpha_t, c.c_x, c.c_m, c.c_p, c.c_e, _DT[ctx.dt],
+                                                         torch.cuda.current_stream(g_xn.device).cuda_stream),
+                  "sta_sampler_step_masked_bwd")
+        return g_eps.to(ctx.eps_dtype), g_x, g_mp, None, None, None, None
+
+
+def solver_step_masked(eps, x, m_prev, noise, c, bl, dtype=None, want_xin=False):
+    """solver_step for call i with the blend `bl` of call i + 1 applied to x_next -> (blended x_next, m, xin of the blended state).
+    Same dispatch as solver_step: CPU: step_reference_masked; CUDA under autograd: SolverStepMaskedFn; otherwise the raw launch."""
+    if not x.is_cuda:
+        x_next, m = step_reference_masked(eps, x, m_prev, noise, c, bl)
+        xin = _pair(x_next).to(dtype or eps.dtype) if want_xin else None
+        return x_next, m, xin
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (eps, x, m_prev)):
+        x_next, m = SolverStepMaskedFn.apply(eps, x, m_prev, noise, c, bl, dtype)
+        return x_next, m, (_pair(x_next.detach()).to(dtype or eps.dtype) if want_xin else None)
+    e16, xc, mp, nz = _prep(eps, x, m_prev, noise, c, dtype)
+    x0, keep, qn, hw = _prep_blend(xc, bl)
+    return _launch_fwd_masked(e16, xc, mp, nz, c, (x0, keep, qn, hw, bl.q_a, bl.q_b), want_xin)
+
+
+def image_composite_reference(dec, orig, keep_px):
+    """keep_px orig + (1 - keep_px) clamp((dec + 1) / 2, 0, 1) in torch, in dec's dtype. Differentiable in dec."""
+    gen = torch.clamp((dec + 1.0) / 2.0, min=0.0, max=1.0)
+    kp = keep_px.to(dec.dtype)
+    return kp * orig.to(dec.dtype) + (1.0 - kp) * gen
+
+
+def _composite_args(dec, orig, keep_px):
+    if dec.dtype not in _DT:
+        raise TypeError("sta_image_composite takes the decoder's 16-bit output, got %s" % dec.dtype)
+    b, ch, hgt, wid = dec.shape
+    if ch != 3 or tuple(orig.shape) != tuple(dec.shape) or tuple(keep_px.shape) != (b, 1, hgt, wid):
+        raise ValueError("composite: dec %s, orig %s, keep_px %s (need [b, 3, H, W] twice and [b, 1, H, W])"
+                         % (tuple(dec.shape), tuple(orig.shape), tuple(keep_px.shape)))
+    return b, hgt * wid
+
+
+class ImageCompositeFn(torch.autograd.Function):
+    """out = keep_px orig + (1 - keep_px) clamp((dec + 1) / 2, 0, 1) (sta_image_composite); backward = sta_image_composite_bwd."""
+
+    @staticmethod
+    def forward(ctx, dec, orig, keep_px):
+        b, hw = _composite_args(dec, orig, keep_px)
+        d = dec.detach().contiguous()
+        og = orig.detach().to(dec.device, torch.float32).contiguous()
+        kp = keep_px.detach().to(dec.device, torch.float32).contiguous()
+        out = torch.empty_like(d)
+        lib.check(lib.load().sta_image_composite(d.data_ptr(), og.data_ptr(), kp.data_ptr(), out.data_ptr(), b, hw, _DT[d.dtype],
+                                                 torch.cuda.current_stream(d.device).cuda_stream), "sta_image_composite")
+        ctx.save_for_backward(d, kp)
+        ctx.dims = (b, hw)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        d, kp = ctx.saved_tensors
+        b, hw = ctx.dims
+        g = g.to(d.dtype).contiguous()
+        g_dec = torch.empty_like(d)
+        lib.check(lib.load().sta_image_composite_bwd(g.data_ptr(), d.data_ptr(), kp.data_ptr(), g_dec.data_ptr(), b, hw, _DT[d.dtype],
+                                                     torch.cuda.current_stream(d.device).cuda_stream), "sta_image_composite_bwd")
+        return g_dec, None, None
+
+
+def image_composite(dec, orig, keep_px):
+    """The inpainting result in pixel space: the original where keep_px == 1, the decoded image (dec in [-1, 1] -> [0, 1], clamped) where
+    it is 0, in dec's dtype. CUDA: the HIP kernel, with its backward under autograd; CPU: image_composite_reference."""
+    if not dec.is_cuda:
+        return image_composite_reference(dec, orig, keep_px)
+    return ImageCompositeFn.apply(dec, orig, keep_px)

@@ -283,6 +283,35 @@ int sta_sampler_step_bwd(const float* g_xn, const float* g_m, float* g_x, void* 
                          float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, int dtype, void* stream);
 
 /*
+ * Layout-guided inpainting (csrc/sta_inpaint.hip). Before UNet call i at integer timestep t_i the kept region is re-noised
+ * (reference ddim.py:144-147, plms.py:232-235):
+ *     x <- keep (q_a x0 + q_b n_i) + (1 - keep) x,   q_a = sqrt(acp[t_i]), q_b = sqrt(1 - acp[t_i]) (float32 roots, host)
+ *   keep: [b][hw] fp32 in [0, 1], 1 = keep the original, broadcast over the n / hw channels;  x0, qnoise: [b][n] fp32, constants.
+ * sta_sampler_step_masked: everything sta_sampler_step does for call i, then the blend OF CALL i + 1 (q_a, q_b of t_{i+1}, qnoise =
+ *   n_{i+1}) on x_next: writes the blended x_next, the unchanged m and xin = the 16-bit pair of the blended state. Where keep == 0 the
+ *   result is bit-equal to sta_sampler_step's. The last call of a trajectory takes sta_sampler_step (no blend after the last step).
+ * sta_sampler_step_masked_bwd: sta_sampler_step_bwd with g_xn (the gradient of the blended state) multiplied by (1 - keep).
+ * sta_latent_blend: the blend alone (first call): x, x0, keep, noise -> x_out [b][n] fp32 and xin (NULL = not written). No backward:
+ *   the start latent is a constant.
+ * sta_image_composite: out = keep_px orig + (1 - keep_px) clamp((dec + 1) / 2, 0, 1) over [b][3][hw]; dec, out: dtype; orig [b][3][hw],
+ *   keep_px [b][hw]: fp32; fp32 arithmetic, rounded to dtype once.
+ * sta_image_composite_bwd: g_dec = 0.5 (1 - keep_px) g where -1 <= dec <= 1 (inclusive, as torch.clamp's gradient), else 0; g, g_dec: dtype.
+ * Rules (STA_E_ARG with text, nothing launched): hw % 8 == 0 and n % hw == 0 (a lane's 8 elements then never straddle a channel: its mask
+ * values are 32 contiguous bytes at (8 col) % hw); every pointer 16-byte aligned; x0, keep, qnoise / noise non-NULL; alpha_t != 0.
+ */
+int sta_sampler_step_masked(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0, const float* keep,
+                            const float* qnoise, float* x_next, float* m, void* xin, long b, long n, long hw, float scale, float sigma_t,
+                            float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype,
+                            void* stream);
+int sta_sampler_step_masked_bwd(const float* g_xn, const float* g_m, const float* keep, float* g_x, void* g_eps, float* g_mprev, long b,
+                                long n, long hw, float scale, float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e,
+                                int dtype, void* stream);
+int sta_latent_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long b, long n, long hw,
+                     float q_a, float q_b, int dtype, void* stream);
+int sta_image_composite(const void* dec, const float* orig, const float* keep_px, void* out, long b, long hw, int dtype, void* stream);
+int sta_image_composite_bwd(const void* g, const void* dec, const float* keep_px, void* g_dec, long b, long hw, int dtype, void* stream);
+
+/*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
  * of its patch-embedding GEMM, and the gradient of the image from the gradient of those rows.
  *   img:   [B][3][H][W] fp32 in [0, 1] (the clamped decoder output);
