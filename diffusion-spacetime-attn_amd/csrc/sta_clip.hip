@@ -186,11 +186,6 @@ __global__ __launch_bounds__(256) void clip_views_bwd_kernel(const T* __restrict
   for (int c = 0; c < 3; ++c) o[(long)c * H * W] = g[c];
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sta_fail(STA_E_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-}
-
 // The shape rules of both entry points (include/sta_unet.h). `grouped`: the backward also needs the views of an image adjacent.
 int check_views(const char* what, const int* boxes_host, int B, int H, int W, int n_views, int dtype, bool grouped) {
   if (B <= 0 || n_views <= 0) return sta_fail(STA_E_ARG, "%s: B=%d n_views=%d", what, B, n_views);
@@ -219,12 +214,10 @@ int sta_clip_views(const float* img, const int* boxes, const int* boxes_host, vo
   if (((uintptr_t)out & 15) != 0) return sta_fail(STA_E_ARG, "clip_views: out must be 16-byte aligned");
   if (const int rc = check_views("clip_views", boxes_host, B, H, W, n_views, out_dtype, false)) return rc;
   const dim3 grid((ROWS * (COLS / 8) + 255) / 256, n_views);
-  hipStream_t st = (hipStream_t)stream;
-  if (out_dtype == STA_BF16)
-    hipLaunchKernelGGL(clip_views_kernel<__bf16>, grid, dim3(256), 0, st, img, boxes, (__bf16*)out, B, H, W, H / 32);
-  else
-    hipLaunchKernelGGL(clip_views_kernel<_Float16>, grid, dim3(256), 0, st, img, boxes, (_Float16*)out, B, H, W, H / 32);
-  return launched("clip_views");
+  return sta_by_dtype(out_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<clip_views_kernel<T>>("clip_views", grid, dim3(256), 0, (hipStream_t)stream, img, boxes, (T*)out, B, H, W, H / 32);
+  });
 }
 
 int sta_clip_views_bwd(const void* dout, const int* boxes, const int* boxes_host, float* dimg, int B, int H, int W, int n_views, int dtype,
@@ -233,12 +226,11 @@ int sta_clip_views_bwd(const void* dout, const int* boxes, const int* boxes_host
   if (!dout || !boxes || !boxes_host || !dimg) return sta_fail(STA_E_ARG, "null pointer");
   if (const int rc = check_views("clip_views_bwd", boxes_host, B, H, W, n_views, dtype, true)) return rc;
   const dim3 grid(H * W / 256, B);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(clip_views_bwd_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16*)dout, boxes, dimg, H, W, n_views, H / 32);
-  else
-    hipLaunchKernelGGL(clip_views_bwd_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16*)dout, boxes, dimg, H, W, n_views, H / 32);
-  return launched("clip_views_bwd");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<clip_views_bwd_kernel<T>>("clip_views_bwd", grid, dim3(256), 0, (hipStream_t)stream, (const T*)dout, boxes, dimg, H, W,
+                                                n_views, H / 32);
+  });
 }
 
 }  // extern "C"

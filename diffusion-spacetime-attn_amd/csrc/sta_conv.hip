@@ -371,6 +371,11 @@ int conv_geo(int H, int W) {                  // tile geometry of an H x W image
   return -1;
 }
 
+template <typename T, int GEO, int NTW>
+int conv_launch(const CV& p, unsigned grid, hipStream_t st) {
+  return sta_launch_lds<conv3x3_nhwc_kernel<T, GEO, NTW>>("conv3x3_nhwc launch", cv_lds(NTW, GEO), dim3(grid), dim3(64 * CV_NW), cv_lds(NTW, GEO), st, p);
+}
+
 }  // namespace
 
 extern "C" {
@@ -398,14 +403,13 @@ int sta_conv3x3_pack_w(const void* w, long so, long si, long sy, long sx, void* 
   if (!w || !packed) return sta_fail(STA_E_ARG, "null pointer");
   if (sta_conv3x3_packed_w_bytes(Cin, Cout) == 0)
     return sta_fail(STA_E_UNSUP, "conv3x3: Cin %% 64 == 0 and Cout %% 160 == 0 or Cout %% 128 == 0 (Cin=%d Cout=%d)", Cin, Cout);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
   const int nkc = Cin / 32, nt = cv_nt(conv_ntw(Cout));
   const unsigned nfr = (unsigned)(Cout / (16 * nt)) * nkc * 9 * nt;
-  if (dtype == STA_BF16) hipLaunchKernelGGL(pack_conv_w_kernel<__bf16>, dim3(nfr), dim3(64), 0, st, (const __bf16*)w, so, si, sy, sx, (__bf16*)packed, nkc, nt);
-  else hipLaunchKernelGGL(pack_conv_w_kernel<_Float16>, dim3(nfr), dim3(64), 0, st, (const _Float16*)w, so, si, sy, sx, (_Float16*)packed, nkc, nt);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_conv_w launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_conv_w_kernel<T>>("pack_conv_w launch", dim3(nfr), dim3(64), 0, st, (const T*)w, so, si, sy, sx, (T*)packed, nkc, nt);
+  });
 }
 
 int sta_conv3x3_nhwc(const void* x, const void* packed_w, const void* zeros, const void* bias, const void* res, void* out, float* stats, int B,
@@ -428,24 +432,12 @@ int sta_conv3x3_nhwc(const void* x, const void* packed_w, const void* zeros, con
   p.xcd_map = tiles % 8 == 0;
   const unsigned grid = (unsigned)(p.items < 256 ? p.items : 256);
   hipStream_t st = (hipStream_t)stream;
-  static StaLdsAttr attr[12];
-#define STA_CONV_LAUNCH(T, GEO, NTW, A)                                                                                            \
-  do {                                                                                                                             \
-    if (!attr[A].ensure((const void*)conv3x3_nhwc_kernel<T, GEO, NTW>, cv_lds(NTW, GEO)))                                          \
-      return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(conv3x3) failed");                                                        \
-    hipLaunchKernelGGL((conv3x3_nhwc_kernel<T, GEO, NTW>), dim3(grid), dim3(64 * CV_NW), cv_lds(NTW, GEO), st, p);                 \
-  } while (0)
-#define STA_CONV_GEOM(T, A)                                                                                                        \
-  do {                                                                                                                             \
-    if (geo == 0) { if (ntw == 5) STA_CONV_LAUNCH(T, 0, 5, A); else STA_CONV_LAUNCH(T, 0, 4, A + 1); }                             \
-    else if (geo == 1) { if (ntw == 5) STA_CONV_LAUNCH(T, 1, 5, A + 2); else STA_CONV_LAUNCH(T, 1, 4, A + 3); }                    \
-    else { if (ntw == 5) STA_CONV_LAUNCH(T, 2, 5, A + 4); else STA_CONV_LAUNCH(T, 2, 4, A + 5); }                                  \
-  } while (0)
-  if (dtype == STA_BF16) STA_CONV_GEOM(__bf16, 0); else STA_CONV_GEOM(_Float16, 6);
-#undef STA_CONV_GEOM
-#undef STA_CONV_LAUNCH
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "conv3x3_nhwc launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (geo == 0) return ntw == 5 ? conv_launch<T, 0, 5>(p, grid, st) : conv_launch<T, 0, 4>(p, grid, st);
+    if (geo == 1) return ntw == 5 ? conv_launch<T, 1, 5>(p, grid, st) : conv_launch<T, 1, 4>(p, grid, st);
+    return ntw == 5 ? conv_launch<T, 2, 5>(p, grid, st) : conv_launch<T, 2, 4>(p, grid, st);
+  });
 }
 
 }  // extern "C"

@@ -255,11 +255,6 @@ __global__ __launch_bounds__(256) void vae_encode_step_kernel(const T* __restric
   }
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-}
-
 }  // namespace
 
 extern "C" {
@@ -286,22 +281,15 @@ int sta_conv3x3_s2_nhwc(const void* x, const void* packed_w, const void* zeros, 
   if (!x || !packed_w || !zeros || !out) return sta_fail(STA_E_ARG, "null pointer");
   if (!sta_conv3x3_s2_nhwc_supported(B, H, W, Cin, Cout))
     return sta_fail(STA_E_UNSUP, "conv3x3_s2_nhwc: unsupported geometry B=%d H=%d W=%d Cin=%d Cout=%d", B, H, W, Cin, Cout);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   S2 p{(const char*)x, (const char*)packed_w, (const char*)zeros, out, bias, stats, B, H, W, Cin, Cout, H / 2, W / 2, Cout / S2_PART,
        (W / 2) / S2_TC, 0, 0};
   p.tiles_per_img = ((H / 2) / S2_TR) * p.tiles_x;
   p.stats_slots = 2 * p.tiles_per_img;
   const unsigned grid = (unsigned)((long)B * p.tiles_per_img * p.parts);
-  hipStream_t st = (hipStream_t)stream;
-  static StaLdsAttr attr[2];
-  if (dtype == STA_BF16) {
-    if (!attr[0].ensure((const void*)conv3x3_s2_nhwc_kernel<__bf16>, S2_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(conv3x3_s2) failed");
-    hipLaunchKernelGGL(conv3x3_s2_nhwc_kernel<__bf16>, dim3(grid), dim3(64 * S2_NW), S2_LDS, st, p);
-  } else {
-    if (!attr[1].ensure((const void*)conv3x3_s2_nhwc_kernel<_Float16>, S2_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(conv3x3_s2) failed");
-    hipLaunchKernelGGL(conv3x3_s2_nhwc_kernel<_Float16>, dim3(grid), dim3(64 * S2_NW), S2_LDS, st, p);
-  }
-  return launched("conv3x3_s2_nhwc");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    return sta_launch_lds<conv3x3_s2_nhwc_kernel<decltype(tag)>>("conv3x3_s2_nhwc", S2_LDS, dim3(grid), dim3(64 * S2_NW), S2_LDS,
+                                                                 (hipStream_t)stream, p);
+  });
 }
 
 int sta_vae_encode_step(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x, float* z0,
@@ -310,18 +298,14 @@ int sta_vae_encode_step(const void* h, const float* quant_w, const float* quant_
   if (!h || !quant_w || !quant_b || !n_post || !n_enc || !x) return sta_fail(STA_E_ARG, "null pointer");
   if (B <= 0 || hw <= 0) return sta_fail(STA_E_ARG, "vae_encode_step: B=%ld hw=%ld", B, hw);
   if (((uintptr_t)h & 15) != 0) return sta_fail(STA_E_ARG, "vae_encode_step: h must be 16-byte aligned");
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const long npx = B * hw;
   long blocks = (npx + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(vae_encode_step_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const __bf16*)h, quant_w, quant_b, n_post, n_enc,
-                       x, z0, (__bf16*)xin, npx, hw, scale_factor, sqrt_a, sqrt_1ma);
-  else
-    hipLaunchKernelGGL(vae_encode_step_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st, (const _Float16*)h, quant_w, quant_b, n_post,
-                       n_enc, x, z0, (_Float16*)xin, npx, hw, scale_factor, sqrt_a, sqrt_1ma);
-  return launched("vae_encode_step");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<vae_encode_step_kernel<T>>("vae_encode_step", dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h, quant_w,
+                                                 quant_b, n_post, n_enc, x, z0, (T*)xin, npx, hw, scale_factor, sqrt_a, sqrt_1ma);
+  });
 }
 
 }  // extern "C"

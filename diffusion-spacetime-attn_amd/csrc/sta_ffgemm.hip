@@ -320,13 +320,12 @@ int sta_ff_out_pack_w(const void* w, void* packed, int C, int inner, int dtype, 
   g_sta_err[0] = 0;
   if (!w || !packed) return sta_fail(STA_E_ARG, "null pointer");
   if (sta_ff_out_packed_w_bytes(C, inner) == 0) return sta_fail(STA_E_UNSUP, "fused feed-forward output: C = 320, inner = 1280 only (C=%d inner=%d)", C, inner);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
   const unsigned nfr = F2_NKC * F2_NCH * F2_CH_FR;
-  if (dtype == STA_BF16) hipLaunchKernelGGL(pack_w2_kernel<__bf16>, dim3(nfr), dim3(64), 0, st, (const __bf16*)w, (__bf16*)packed);
-  else hipLaunchKernelGGL(pack_w2_kernel<_Float16>, dim3(nfr), dim3(64), 0, st, (const _Float16*)w, (_Float16*)packed);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_w2 launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_w2_kernel<T>>("pack_w2 launch", dim3(nfr), dim3(64), 0, st, (const T*)w, (T*)packed);
+  });
 }
 
 int sta_ff_out_res_hfrag(const void* h_frag, const void* packed_w, const void* bias, const void* x, void* out, long R, int C, int inner,
@@ -336,21 +335,13 @@ int sta_ff_out_res_hfrag(const void* h_frag, const void* packed_w, const void* b
   if (sta_ff_out_packed_w_bytes(C, inner) == 0) return sta_fail(STA_E_UNSUP, "fused feed-forward output: C = 320, inner = 1280 only (C=%d inner=%d)", C, inner);
   if (R <= 0 || R % 16) return sta_fail(STA_E_ARG, "ff_out_res_hfrag: R=%ld (need a positive multiple of 16 rows)", R);
   if ((size_t)R * inner * 2 >= 0xfffffff0ull) return sta_fail(STA_E_UNSUP, "activations must stay below 4 GiB (R=%ld)", R);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   F2 p{(const char*)h_frag, (const char*)packed_w, bias, x, out, R};
   const long nblk = (R + 16 * FF_NW - 1) / (16 * FF_NW);
   const unsigned grid = (unsigned)(nblk < 256 ? nblk : 256);
   hipStream_t st = (hipStream_t)stream;
-  static StaLdsAttr attr_b, attr_h;
-  if (dtype == STA_BF16) {
-    if (!attr_b.ensure((const void*)ff_out_res_hfrag_kernel<__bf16>, F2_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(ff_out) failed");
-    hipLaunchKernelGGL(ff_out_res_hfrag_kernel<__bf16>, dim3(grid), dim3(64 * FF_NW), F2_LDS, st, p);
-  } else {
-    if (!attr_h.ensure((const void*)ff_out_res_hfrag_kernel<_Float16>, F2_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(ff_out) failed");
-    hipLaunchKernelGGL(ff_out_res_hfrag_kernel<_Float16>, dim3(grid), dim3(64 * FF_NW), F2_LDS, st, p);
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "ff_out_res_hfrag launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    return sta_launch_lds<ff_out_res_hfrag_kernel<decltype(tag)>>("ff_out_res_hfrag launch", F2_LDS, dim3(grid), dim3(64 * FF_NW), F2_LDS, st, p);
+  });
 }
 
 size_t sta_ff_geglu_packed_w_bytes(int C, int inner) {
@@ -361,12 +352,11 @@ int sta_ff_geglu_pack_w(const void* w, void* packed, int C, int inner, int dtype
   g_sta_err[0] = 0;
   if (!w || !packed) return sta_fail(STA_E_ARG, "null pointer");
   if (sta_ff_geglu_packed_w_bytes(C, inner) == 0) return sta_fail(STA_E_UNSUP, "fused GEGLU projection: C = 320, inner = 1280 only (C=%d inner=%d)", C, inner);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16) hipLaunchKernelGGL(pack_w1_kernel<__bf16>, dim3(FF_NSC * FF_SC_FR), dim3(64), 0, st, (const __bf16*)w, (__bf16*)packed);
-  else hipLaunchKernelGGL(pack_w1_kernel<_Float16>, dim3(FF_NSC * FF_SC_FR), dim3(64), 0, st, (const _Float16*)w, (_Float16*)packed);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_w1 launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_w1_kernel<T>>("pack_w1 launch", dim3(FF_NSC * FF_SC_FR), dim3(64), 0, st, (const T*)w, (T*)packed);
+  });
 }
 
 int sta_ff_geglu_qfrag(const void* y_qfrag, const void* packed_w, const void* bias, void* h, long R, int C, int inner, int h_frag,
@@ -376,21 +366,13 @@ int sta_ff_geglu_qfrag(const void* y_qfrag, const void* packed_w, const void* bi
   if (sta_ff_geglu_packed_w_bytes(C, inner) == 0) return sta_fail(STA_E_UNSUP, "fused GEGLU projection: C = 320, inner = 1280 only (C=%d inner=%d)", C, inner);
   if (R <= 0 || R % 16) return sta_fail(STA_E_ARG, "ff_geglu_qfrag: R=%ld (need a positive multiple of 16 rows)", R);
   if ((size_t)R * inner * 2 >= 0xfffffff0ull) return sta_fail(STA_E_UNSUP, "activations must stay below 4 GiB (R=%ld)", R);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   FF p{(const char*)y_qfrag, (const char*)packed_w, bias, h, R, h_frag ? 1 : 0};
   const long nblk = (R + 32 * FF_NW - 1) / (32 * FF_NW);
   const unsigned grid = (unsigned)(nblk < 256 ? nblk : 256);
   hipStream_t st = (hipStream_t)stream;
-  static StaLdsAttr attr_b, attr_h;
-  if (dtype == STA_BF16) {
-    if (!attr_b.ensure((const void*)ff_geglu_qfrag_kernel<__bf16>, FF_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(ff_geglu) failed");
-    hipLaunchKernelGGL(ff_geglu_qfrag_kernel<__bf16>, dim3(grid), dim3(64 * FF_NW), FF_LDS, st, p);
-  } else {
-    if (!attr_h.ensure((const void*)ff_geglu_qfrag_kernel<_Float16>, FF_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(ff_geglu) failed");
-    hipLaunchKernelGGL(ff_geglu_qfrag_kernel<_Float16>, dim3(grid), dim3(64 * FF_NW), FF_LDS, st, p);
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "ff_geglu_qfrag launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    return sta_launch_lds<ff_geglu_qfrag_kernel<decltype(tag)>>("ff_geglu_qfrag launch", FF_LDS, dim3(grid), dim3(64 * FF_NW), FF_LDS, st, p);
+  });
 }
 
 }  // extern "C"

@@ -16,8 +16,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 constexpr int MAXIT = 10;                    // 64 lanes x 8 elements x 10 = 5120 channels per row at most
 constexpr float E4M3_MAX = 448.0f;
@@ -71,13 +69,9 @@ extern "C" int sta_quant_rows_fp8(const void* x, void* xq, float* scale, long ro
   if (!x || !xq || !scale) return sta_fail(STA_E_ARG, "null pointer");
   if (rows <= 0 || C <= 0) return sta_fail(STA_E_ARG, "rows=%ld C=%d", rows, C);
   if (C % 8 || C > 64 * 8 * MAXIT) return sta_fail(STA_E_UNSUP, "C=%d unsupported (C %% 8 == 0, C <= %d)", C, 64 * 8 * MAXIT);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(quant_rows_fp8_kernel<bf16x8>, grid, dim3(256), 0, st, (const bf16x8*)x, (u32x2*)xq, scale, rows, C / 8);
-  else
-    hipLaunchKernelGGL(quant_rows_fp8_kernel<f16x8>, grid, dim3(256), 0, st, (const f16x8*)x, (u32x2*)xq, scale, rows, C / 8);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "quant_rows_fp8 launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    typedef decltype(tag) V8 __attribute__((ext_vector_type(8)));
+    return sta_launch<quant_rows_fp8_kernel<V8>>("quant_rows_fp8 launch", dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                                                 (const V8*)x, (u32x2*)xq, scale, rows, C / 8);
+  });
 }

@@ -309,14 +309,13 @@ int sta_linear_rows_pack_w(const void* w, long sn, long sk, void* packed, int K,
   g_sta_err[0] = 0;
   if (!w || !packed) return sta_fail(STA_E_ARG, "null pointer");
   if (sta_linear_rows_packed_w_bytes(K, N) == 0) return sta_fail(STA_E_UNSUP, "linear_rows: K %% 64 == 0 and N %% 160 == 0 or N %% 128 == 0 (K=%d N=%d)", K, N);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
   const int nsteps = K / 64, nt = gm_nt(gemm_ntw(N));
   const unsigned nfr = (unsigned)(N / (16 * nt)) * nsteps * 2 * nt;
-  if (dtype == STA_BF16) hipLaunchKernelGGL(pack_gemm_w_kernel<__bf16>, dim3(nfr), dim3(64), 0, st, (const __bf16*)w, sn, sk, (__bf16*)packed, nsteps, nt);
-  else hipLaunchKernelGGL(pack_gemm_w_kernel<_Float16>, dim3(nfr), dim3(64), 0, st, (const _Float16*)w, sn, sk, (_Float16*)packed, nsteps, nt);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_gemm_w launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_gemm_w_kernel<T>>("pack_gemm_w launch", dim3(nfr), dim3(64), 0, st, (const T*)w, sn, sk, (T*)packed, nsteps, nt);
+  });
 }
 
 static int linear_rows_impl(const void* x, const void* xb, int Ka, const void* packed_w, const void* zeros, const void* bias, const void* res,
@@ -335,17 +334,12 @@ static int linear_rows_impl(const void* x, const void* xb, int Ka, const void* p
   p.xcd_map = p.tiles % 8 == 0;
   const unsigned grid = (unsigned)(p.items < 256 ? p.items : 256);
   hipStream_t st = (hipStream_t)stream;
-  static StaLdsAttr attr[4];
-#define STA_GEMM_LAUNCH(T, NTW, A)                                                                                                 \
-  do {                                                                                                                             \
-    if (!attr[A].ensure((const void*)gemm_rows_kernel<T, NTW>, gm_lds(NTW))) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(linear_rows) failed"); \
-    hipLaunchKernelGGL((gemm_rows_kernel<T, NTW>), dim3(grid), dim3(64 * GM_NW), gm_lds(NTW), st, p);                              \
-  } while (0)
-  if (dtype == STA_BF16) { if (ntw == 5) STA_GEMM_LAUNCH(__bf16, 5, 0); else STA_GEMM_LAUNCH(__bf16, 4, 1); }
-  else { if (ntw == 5) STA_GEMM_LAUNCH(_Float16, 5, 2); else STA_GEMM_LAUNCH(_Float16, 4, 3); }
-#undef STA_GEMM_LAUNCH
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "linear_rows launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const char* const what = "linear_rows launch";
+    if (ntw == 5) return sta_launch_lds<gemm_rows_kernel<T, 5>>(what, gm_lds(5), dim3(grid), dim3(64 * GM_NW), gm_lds(5), st, p);
+    return sta_launch_lds<gemm_rows_kernel<T, 4>>(what, gm_lds(4), dim3(grid), dim3(64 * GM_NW), gm_lds(4), st, p);
+  });
 }
 
 int sta_linear_rows(const void* x, const void* packed_w, const void* zeros, const void* bias, const void* res, void* out, long R, int K, int N,

@@ -196,19 +196,6 @@ __global__ __launch_bounds__(256) void image_composite_bwd_kernel(const T* __res
   }
 }
 
-bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sta_fail(STA_E_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-}
-
-unsigned grid_for(long nvec) {
-  long blocks = (nvec + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  return (unsigned)blocks;
-}
-
 // b images of n elements, masks of hw: n a whole number of hw-sized channels, hw % 8 == 0
 int check_sizes(const char* what, long b, long n, long hw) {
   if (b <= 0 || n <= 0 || hw <= 0 || hw % 8 || n % hw)
@@ -228,21 +215,17 @@ int sta_sampler_step_masked(const void* eps, const float* x, const float* m_prev
   if (!eps || !x || !x_next || !m) return sta_fail(STA_E_ARG, "null pointer");
   if (!x0 || !keep || !qnoise) return sta_fail(STA_E_ARG, "sampler_step_masked: x0, keep and qnoise are required (null pointer)");
   if (check_sizes("sampler_step_masked", b, n, hw)) return STA_E_ARG;
-  if (!aligned16(eps) || !aligned16(x) || !aligned16(m_prev) || !aligned16(noise) || !aligned16(x0) || !aligned16(keep) ||
-      !aligned16(qnoise) || !aligned16(x_next) || !aligned16(m) || !aligned16(xin))
+  if (!sta_aligned16(eps) || !sta_aligned16(x) || !sta_aligned16(m_prev) || !sta_aligned16(noise) || !sta_aligned16(x0) || !sta_aligned16(keep) ||
+      !sta_aligned16(qnoise) || !sta_aligned16(x_next) || !sta_aligned16(m) || !sta_aligned16(xin))
     return sta_fail(STA_E_ARG, "sampler_step_masked: every tensor must be 16-byte aligned");
   if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_masked: alpha_t == 0");
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
   const long rowvec = n / 8, nvec = b * rowvec;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(sampler_step_masked_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const __bf16*)eps, x, m_prev, noise, x0,
-                       keep, qnoise, x_next, m, (__bf16*)xin, nvec, rowvec, hw, c, q_a, q_b);
-  else
-    hipLaunchKernelGGL(sampler_step_masked_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const _Float16*)eps, x, m_prev, noise,
-                       x0, keep, qnoise, x_next, m, (_Float16*)xin, nvec, rowvec, hw, c, q_a, q_b);
-  return launched("sampler_step_masked");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<sampler_step_masked_kernel<T>>("sampler_step_masked", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)eps, x, m_prev, noise,
+                                                     x0, keep, qnoise, x_next, m, (T*)xin, nvec, rowvec, hw, c, q_a, q_b);
+  });
 }
 
 int sta_sampler_step_masked_bwd(const float* g_xn, const float* g_m, const float* keep, float* g_x, void* g_eps, float* g_mprev, long b,
@@ -252,20 +235,16 @@ int sta_sampler_step_masked_bwd(const float* g_xn, const float* g_m, const float
   if (!g_xn || !g_x || !g_eps) return sta_fail(STA_E_ARG, "null pointer");
   if (!keep) return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: keep is required (null pointer)");
   if (check_sizes("sampler_step_masked_bwd", b, n, hw)) return STA_E_ARG;
-  if (!aligned16(g_xn) || !aligned16(g_m) || !aligned16(keep) || !aligned16(g_x) || !aligned16(g_eps) || !aligned16(g_mprev))
+  if (!sta_aligned16(g_xn) || !sta_aligned16(g_m) || !sta_aligned16(keep) || !sta_aligned16(g_x) || !sta_aligned16(g_eps) || !sta_aligned16(g_mprev))
     return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: every tensor must be 16-byte aligned");
   if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: alpha_t == 0");
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, 0.f};
   const long rowvec = n / 8, nvec = b * rowvec;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(sampler_step_masked_bwd_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, g_xn, g_m, keep, g_x, (__bf16*)g_eps,
-                       g_mprev, nvec, rowvec, hw, c);
-  else
-    hipLaunchKernelGGL(sampler_step_masked_bwd_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, g_xn, g_m, keep, g_x,
-                       (_Float16*)g_eps, g_mprev, nvec, rowvec, hw, c);
-  return launched("sampler_step_masked_bwd");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<sampler_step_masked_bwd_kernel<T>>("sampler_step_masked_bwd", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, g_xn,
+                                                         g_m, keep, g_x, (T*)g_eps, g_mprev, nvec, rowvec, hw, c);
+  });
 }
 
 int sta_latent_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long b, long n, long hw,
@@ -273,54 +252,42 @@ int sta_latent_blend(const float* x, const float* x0, const float* keep, const f
   g_sta_err[0] = 0;
   if (!x || !x0 || !keep || !noise || !x_out) return sta_fail(STA_E_ARG, "latent_blend: null pointer");
   if (check_sizes("latent_blend", b, n, hw)) return STA_E_ARG;
-  if (!aligned16(x) || !aligned16(x0) || !aligned16(keep) || !aligned16(noise) || !aligned16(x_out) || !aligned16(xin))
+  if (!sta_aligned16(x) || !sta_aligned16(x0) || !sta_aligned16(keep) || !sta_aligned16(noise) || !sta_aligned16(x_out) || !sta_aligned16(xin))
     return sta_fail(STA_E_ARG, "latent_blend: every tensor must be 16-byte aligned");
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const long rowvec = n / 8, nvec = b * rowvec;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(latent_blend_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, x, x0, keep, noise, x_out, (__bf16*)xin, nvec,
-                       rowvec, hw, q_a, q_b);
-  else
-    hipLaunchKernelGGL(latent_blend_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, x, x0, keep, noise, x_out, (_Float16*)xin, nvec,
-                       rowvec, hw, q_a, q_b);
-  return launched("latent_blend");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<latent_blend_kernel<T>>("latent_blend", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, x, x0, keep, noise, x_out, (T*)xin, nvec,
+                                              rowvec, hw, q_a, q_b);
+  });
 }
 
 int sta_image_composite(const void* dec, const float* orig, const float* keep_px, void* out, long b, long hw, int dtype, void* stream) {
   g_sta_err[0] = 0;
   if (!dec || !orig || !keep_px || !out) return sta_fail(STA_E_ARG, "image_composite: null pointer");
   if (check_sizes("image_composite", b, 3 * hw, hw)) return STA_E_ARG;
-  if (!aligned16(dec) || !aligned16(orig) || !aligned16(keep_px) || !aligned16(out))
+  if (!sta_aligned16(dec) || !sta_aligned16(orig) || !sta_aligned16(keep_px) || !sta_aligned16(out))
     return sta_fail(STA_E_ARG, "image_composite: every tensor must be 16-byte aligned");
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const long rowvec = 3 * hw / 8, nvec = b * rowvec;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(image_composite_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const __bf16*)dec, orig, keep_px, (__bf16*)out,
-                       nvec, rowvec, hw);
-  else
-    hipLaunchKernelGGL(image_composite_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const _Float16*)dec, orig, keep_px,
-                       (_Float16*)out, nvec, rowvec, hw);
-  return launched("image_composite");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<image_composite_kernel<T>>("image_composite", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)dec, orig, keep_px,
+                                                 (T*)out, nvec, rowvec, hw);
+  });
 }
 
 int sta_image_composite_bwd(const void* g, const void* dec, const float* keep_px, void* g_dec, long b, long hw, int dtype, void* stream) {
   g_sta_err[0] = 0;
   if (!g || !dec || !keep_px || !g_dec) return sta_fail(STA_E_ARG, "image_composite_bwd: null pointer");
   if (check_sizes("image_composite_bwd", b, 3 * hw, hw)) return STA_E_ARG;
-  if (!aligned16(g) || !aligned16(dec) || !aligned16(keep_px) || !aligned16(g_dec))
+  if (!sta_aligned16(g) || !sta_aligned16(dec) || !sta_aligned16(keep_px) || !sta_aligned16(g_dec))
     return sta_fail(STA_E_ARG, "image_composite_bwd: every tensor must be 16-byte aligned");
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const long rowvec = 3 * hw / 8, nvec = b * rowvec;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(image_composite_bwd_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const __bf16*)g, (const __bf16*)dec,
-                       keep_px, (__bf16*)g_dec, nvec, rowvec, hw);
-  else
-    hipLaunchKernelGGL(image_composite_bwd_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const _Float16*)g, (const _Float16*)dec,
-                       keep_px, (_Float16*)g_dec, nvec, rowvec, hw);
-  return launched("image_composite_bwd");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<image_composite_bwd_kernel<T>>("image_composite_bwd", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)g,
+                                                     (const T*)dec, keep_px, (T*)g_dec, nvec, rowvec, hw);
+  });
 }
 
 }  // extern "C"

@@ -266,13 +266,12 @@ int sta_ln_qkv_pack_w(const void* wqk, const void* wv, void* packed, int C, int 
   g_sta_err[0] = 0;
   if (!wqk || !wv || !packed) return sta_fail(STA_E_ARG, "null pointer");
   if (sta_ln_qkv_packed_w_bytes(C) == 0) return sta_fail(STA_E_UNSUP, "fused norm1 + q/k/v projection: C = 320 only (C=%d)", C);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   hipStream_t st = (hipStream_t)stream;
   const unsigned nfr = LQ_NSC * LQ_SC_FR;
-  if (dtype == STA_BF16) hipLaunchKernelGGL(pack_wqkv_kernel<__bf16>, dim3(nfr), dim3(64), 0, st, (const __bf16*)wqk, (const __bf16*)wv, (__bf16*)packed);
-  else hipLaunchKernelGGL(pack_wqkv_kernel<_Float16>, dim3(nfr), dim3(64), 0, st, (const _Float16*)wqk, (const _Float16*)wv, (_Float16*)packed);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_wqkv launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_wqkv_kernel<T>>("pack_wqkv launch", dim3(nfr), dim3(64), 0, st, (const T*)wqk, (const T*)wv, (T*)packed);
+  });
 }
 
 int sta_ln_qkv(const void* x, const void* bias, const void* gamma, const void* beta, const void* packed_w, void* s, void* y_dbg,
@@ -282,21 +281,13 @@ int sta_ln_qkv(const void* x, const void* bias, const void* gamma, const void* b
   if (sta_ln_qkv_packed_w_bytes(C) == 0) return sta_fail(STA_E_UNSUP, "fused norm1 + q/k/v projection: C = 320 only (C=%d)", C);
   if (R <= 0 || R % 16) return sta_fail(STA_E_ARG, "ln_qkv: R=%ld (need a positive multiple of 16 rows)", R);
   if ((size_t)R * 2 * C * 2 >= 0xfffffff0ull) return sta_fail(STA_E_UNSUP, "ln_qkv: the q|k output must stay below 4 GiB (R=%ld)", R);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   LQ p{x, bias, gamma, beta, (const char*)packed_w, s, y_dbg, qk, vt, R, C, eps};
   const long nblk = (R + 32 * LQ_NW - 1) / (32 * LQ_NW);
   const unsigned grid = (unsigned)(nblk < 256 ? nblk : 256);
   hipStream_t st = (hipStream_t)stream;
-  static StaLdsAttr attr_b, attr_h;
-  if (dtype == STA_BF16) {
-    if (!attr_b.ensure((const void*)ln_qkv_kernel<__bf16>, LQ_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(ln_qkv) failed");
-    hipLaunchKernelGGL(ln_qkv_kernel<__bf16>, dim3(grid), dim3(64 * LQ_NW), LQ_LDS, st, p);
-  } else {
-    if (!attr_h.ensure((const void*)ln_qkv_kernel<_Float16>, LQ_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(ln_qkv) failed");
-    hipLaunchKernelGGL(ln_qkv_kernel<_Float16>, dim3(grid), dim3(64 * LQ_NW), LQ_LDS, st, p);
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "ln_qkv launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    return sta_launch_lds<ln_qkv_kernel<decltype(tag)>>("ln_qkv launch", LQ_LDS, dim3(grid), dim3(64 * LQ_NW), LQ_LDS, st, p);
+  });
 }
 
 }  // extern "C"

@@ -322,20 +322,21 @@ __global__ __launch_bounds__(256, 2) void mx8_gemm_kernel(const uint8_t* __restr
 }
 
 template <typename T, int FL>
-void launch_gemm(const void* p, const void* ps, const void* q, const void* qs, void* out, void* out_s, const void* bias,
+int launch_gemm(const void* p, const void* ps, const void* q, const void* qs, void* out, void* out_s, const void* bias,
                  const float* col_scale, long M, int N, int K, long ldo, hipStream_t st) {
   const int ntiles = (N + TN - 1) / TN;
   const long nb = (M + TM - 1) / TM * ntiles;
-  hipLaunchKernelGGL((mx8_gemm_kernel<T, FL>), dim3((unsigned)nb), dim3(256), 0, st, (const uint8_t*)p, (const uint8_t*)ps,
-                     (const uint8_t*)q, (const uint8_t*)qs, out, (uint8_t*)out_s, (const T*)bias, col_scale, M, N, K, ldo, ntiles);
+  return sta_launch<mx8_gemm_kernel<T, FL>>("mx8_gemm launch", dim3((unsigned)nb), dim3(256), 0, st, (const uint8_t*)p, (const uint8_t*)ps,
+                                            (const uint8_t*)q, (const uint8_t*)qs, out, (uint8_t*)out_s, (const T*)bias, col_scale, M, N, K, ldo,
+                                            ntiles);
 }
 
 template <typename T>
-void launch_gemm_flags(int flags, const void* p, const void* ps, const void* q, const void* qs, void* out, void* out_s, const void* bias,
+int launch_gemm_flags(int flags, const void* p, const void* ps, const void* q, const void* qs, void* out, void* out_s, const void* bias,
                        const float* col_scale, long M, int N, int K, long ldo, hipStream_t st) {
-  if (flags == 0) launch_gemm<T, 0>(p, ps, q, qs, out, out_s, bias, col_scale, M, N, K, ldo, st);
-  else if (flags == STA_MX8_GEGLU) launch_gemm<T, STA_MX8_GEGLU>(p, ps, q, qs, out, out_s, bias, col_scale, M, N, K, ldo, st);
-  else launch_gemm<T, GL_ALL>(p, ps, q, qs, out, out_s, bias, col_scale, M, N, K, ldo, st);
+  if (flags == 0) return launch_gemm<T, 0>(p, ps, q, qs, out, out_s, bias, col_scale, M, N, K, ldo, st);
+  if (flags == STA_MX8_GEGLU) return launch_gemm<T, STA_MX8_GEGLU>(p, ps, q, qs, out, out_s, bias, col_scale, M, N, K, ldo, st);
+  return launch_gemm<T, GL_ALL>(p, ps, q, qs, out, out_s, bias, col_scale, M, N, K, ldo, st);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -351,13 +352,11 @@ extern "C" int sta_mx8_quant_rows(const void* x, void* xq, void* xs, long rows, 
   if (!aligned16(x) || !aligned16(xq)) return sta_fail(STA_E_ARG, "x and xq must be 16-byte aligned");
   const long nblk = rows * (long)(K / 32);
   const dim3 grid((unsigned)((nblk + 255) / 256));
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(mx8_quant_kernel<__bf16>, grid, dim3(256), 0, st, (const bf16x8*)x, (u32x4*)xq, (uint8_t*)xs, nblk);
-  else
-    hipLaunchKernelGGL(mx8_quant_kernel<_Float16>, grid, dim3(256), 0, st, (const f16x8*)x, (u32x4*)xq, (uint8_t*)xs, nblk);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "mx8_quant_rows launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<mx8_quant_kernel<T>>("mx8_quant_rows launch", grid, dim3(256), 0, (hipStream_t)stream, (const typename Vec<T>::v8*)x,
+                                           (u32x4*)xq, (uint8_t*)xs, nblk);
+  });
 }
 
 extern "C" int sta_mx8_gemm(const void* p, const void* ps, const void* q, const void* qs, void* out, void* out_scale, const void* bias,
@@ -379,9 +378,7 @@ extern "C" int sta_mx8_gemm(const void* p, const void* ps, const void* q, const 
     if (ldo < N) return sta_fail(STA_E_ARG, "ldo=%ld < N=%d", ldo, N);
   }
   if (!aligned16(out)) return sta_fail(STA_E_ARG, "out must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16) launch_gemm_flags<__bf16>(flags, p, ps, q, qs, out, out_scale, bias, col_scale, M, N, K, ldo, st);
-  else launch_gemm_flags<_Float16>(flags, p, ps, q, qs, out, out_scale, bias, col_scale, M, N, K, ldo, st);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "mx8_gemm launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    return launch_gemm_flags<decltype(tag)>(flags, p, ps, q, qs, out, out_scale, bias, col_scale, M, N, K, ldo, (hipStream_t)stream);
+  });
 }

@@ -229,10 +229,10 @@ int sta_to_out_ln_pack_wo(const void* wo, void* packed, int C, int heads, int ki
   if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   if (kind != 0 && kind != 1) return sta_fail(STA_E_ARG, "fragment kind %d (0: cross-attention out fragments, 1: self-attention out fragments)", kind);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16) hipLaunchKernelGGL(pack_wo_ofrag_kernel<__bf16>, dim3(RG_NRT * RG_NKS), dim3(64), 0, st, (const __bf16*)wo, (__bf16*)packed, kind);
-  else hipLaunchKernelGGL(pack_wo_ofrag_kernel<_Float16>, dim3(RG_NRT * RG_NKS), dim3(64), 0, st, (const _Float16*)wo, (_Float16*)packed, kind);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_wo_ofrag launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_wo_ofrag_kernel<T>>("pack_wo_ofrag launch", dim3(RG_NRT * RG_NKS), dim3(64), 0, st, (const T*)wo, (T*)packed, kind);
+  });
 }
 
 int sta_to_out_ln_ofrag(const void* blended_ofrag, const void* packed_wo, const void* bias, const void* x, const void* gamma,
@@ -242,21 +242,13 @@ int sta_to_out_ln_ofrag(const void* blended_ofrag, const void* packed_wo, const 
   if (sta_to_out_ln_packed_wo_bytes(C, heads) == 0) return sta_fail(STA_E_UNSUP, "to_out + LayerNorm in out-fragment order: C = 320 with 8 heads only (C=%d heads=%d)", C, heads);
   if (R <= 0 || R % 16) return sta_fail(STA_E_ARG, "to_out_ln_ofrag: R=%ld (need a positive multiple of 16 rows)", R);
   if ((size_t)R * C * 2 >= 0xfffffff0ull) return sta_fail(STA_E_UNSUP, "activations must stay below 4 GiB (R=%ld)", R);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   RG p{(const char*)blended_ofrag, (const char*)packed_wo, bias, gamma, beta, x, s, y, R, eps, y_qfrag ? 1 : 0};
   const long nblk = (R + 16 * RG_NW - 1) / (16 * RG_NW);
   const unsigned grid = (unsigned)(nblk < 256 ? nblk : 256);       // one persistent workgroup per CU
   hipStream_t st = (hipStream_t)stream;
-  static StaLdsAttr attr_b, attr_h;
-  if (dtype == STA_BF16) {
-    if (!attr_b.ensure((const void*)to_out_ln_ofrag_kernel<__bf16>, RG_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(to_out_ln) failed");
-    hipLaunchKernelGGL(to_out_ln_ofrag_kernel<__bf16>, dim3(grid), dim3(64 * RG_NW), RG_LDS, st, p);
-  } else {
-    if (!attr_h.ensure((const void*)to_out_ln_ofrag_kernel<_Float16>, RG_LDS)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(to_out_ln) failed");
-    hipLaunchKernelGGL(to_out_ln_ofrag_kernel<_Float16>, dim3(grid), dim3(64 * RG_NW), RG_LDS, st, p);
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "to_out_ln_ofrag launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    return sta_launch_lds<to_out_ln_ofrag_kernel<decltype(tag)>>("to_out_ln_ofrag launch", RG_LDS, dim3(grid), dim3(64 * RG_NW), RG_LDS, st, p);
+  });
 }
 
 }  // extern "C"

@@ -113,19 +113,6 @@ __global__ __launch_bounds__(256) void sampler_step_bwd_kernel(const float* __re
   }
 }
 
-bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : sta_fail(STA_E_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-}
-
-unsigned grid_for(long nvec) {
-  long blocks = (nvec + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  return (unsigned)blocks;
-}
-
 }  // namespace
 
 extern "C" {
@@ -136,20 +123,16 @@ int sta_sampler_step(const void* eps, const float* x, const float* m_prev, const
   g_sta_err[0] = 0;
   if (!eps || !x || !x_next || !m) return sta_fail(STA_E_ARG, "null pointer");
   if (b <= 0 || n <= 0 || n % 8) return sta_fail(STA_E_ARG, "sampler_step: b=%ld n=%ld (need n %% 8 == 0)", b, n);
-  if (!aligned16(eps) || !aligned16(x) || !aligned16(m_prev) || !aligned16(noise) || !aligned16(x_next) || !aligned16(m) || !aligned16(xin))
+  if (!sta_aligned16(eps) || !sta_aligned16(x) || !sta_aligned16(m_prev) || !sta_aligned16(noise) || !sta_aligned16(x_next) || !sta_aligned16(m) || !sta_aligned16(xin))
     return sta_fail(STA_E_ARG, "sampler_step: every tensor must be 16-byte aligned");
   if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step: alpha_t == 0");
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
   const long rowvec = n / 8, nvec = b * rowvec;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(sampler_step_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const __bf16*)eps, x, m_prev, noise, x_next, m,
-                       (__bf16*)xin, nvec, rowvec, c);
-  else
-    hipLaunchKernelGGL(sampler_step_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, (const _Float16*)eps, x, m_prev, noise, x_next,
-                       m, (_Float16*)xin, nvec, rowvec, c);
-  return launched("sampler_step");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<sampler_step_kernel<T>>("sampler_step", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)eps, x,
+                                              m_prev, noise, x_next, m, (T*)xin, nvec, rowvec, c);
+  });
 }
 
 int sta_sampler_step_bwd(const float* g_xn, const float* g_m, float* g_x, void* g_eps, float* g_mprev, long b, long n, float scale,
@@ -157,20 +140,16 @@ int sta_sampler_step_bwd(const float* g_xn, const float* g_m, float* g_x, void* 
   g_sta_err[0] = 0;
   if (!g_xn || !g_x || !g_eps) return sta_fail(STA_E_ARG, "null pointer");
   if (b <= 0 || n <= 0 || n % 8) return sta_fail(STA_E_ARG, "sampler_step_bwd: b=%ld n=%ld (need n %% 8 == 0)", b, n);
-  if (!aligned16(g_xn) || !aligned16(g_m) || !aligned16(g_x) || !aligned16(g_eps) || !aligned16(g_mprev))
+  if (!sta_aligned16(g_xn) || !sta_aligned16(g_m) || !sta_aligned16(g_x) || !sta_aligned16(g_eps) || !sta_aligned16(g_mprev))
     return sta_fail(STA_E_ARG, "sampler_step_bwd: every tensor must be 16-byte aligned");
   if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_bwd: alpha_t == 0");
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, 0.f};
   const long rowvec = n / 8, nvec = b * rowvec;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(sampler_step_bwd_kernel<__bf16>, dim3(grid_for(nvec)), dim3(256), 0, st, g_xn, g_m, g_x, (__bf16*)g_eps, g_mprev, nvec,
-                       rowvec, c);
-  else
-    hipLaunchKernelGGL(sampler_step_bwd_kernel<_Float16>, dim3(grid_for(nvec)), dim3(256), 0, st, g_xn, g_m, g_x, (_Float16*)g_eps, g_mprev,
-                       nvec, rowvec, c);
-  return launched("sampler_step_bwd");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<sampler_step_bwd_kernel<T>>("sampler_step_bwd", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, g_xn, g_m,
+                                                  g_x, (T*)g_eps, g_mprev, nvec, rowvec, c);
+  });
 }
 
 }  // extern "C"

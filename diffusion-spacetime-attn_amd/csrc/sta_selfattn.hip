@@ -770,20 +770,16 @@ __global__ __launch_bounds__(64 * NW, 2) void selfattn_fwd_pipe_kernel(const SPa
 template <typename T, int NW, int QT>
 int launch_sa_pipe(const SParams& p, hipStream_t st) {
   constexpr int lds = 4 * ((11 + NW - 1) / NW * NW) * FRAG;
-  static StaLdsAttr attr, attr_opt;
-  if (!attr.ensure((const void*)selfattn_fwd_pipe_kernel<T, NW, QT>, lds)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(selfattn pipe) failed");
+  const char* const what = "selfattn pipe launch";
+  if (const int rc = sta_raise_lds<selfattn_fwd_pipe_kernel<T, NW, QT>>(what, lds)) return rc;
   const int tiles = (p.N + 16 * QT * NW - 1) / (16 * QT * NW);
-  {
-    if (p.optimistic) {
-      // the optimistic loop (no running maximum behind a tile's first block: a tenth of the loop's instructions less), then the
-      // standard loop for the workgroups it flagged — with ordinary logits every workgroup of the second launch returns at once
-      if (!attr_opt.ensure((const void*)selfattn_fwd_pipe_kernel<T, NW, QT, true>, lds)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(selfattn pipe) failed");
-      hipLaunchKernelGGL((selfattn_fwd_pipe_kernel<T, NW, QT, true>), dim3(tiles * p.H, p.B), dim3(64 * NW), lds, st, p);
-    }
+  const dim3 grid(tiles * p.H, p.B), block(64 * NW);
+  if (p.optimistic) {
+    // the optimistic loop (no running maximum behind a tile's first block: a tenth of the loop's instructions less), then the
+    // standard loop for the workgroups it flagged — with ordinary logits every workgroup of the second launch returns at once
+    if (const int rc = sta_launch_lds<selfattn_fwd_pipe_kernel<T, NW, QT, true>>(what, lds, grid, block, lds, st, p)) return rc;
   }
-  hipLaunchKernelGGL((selfattn_fwd_pipe_kernel<T, NW, QT>), dim3(tiles * p.H, p.B), dim3(64 * NW), lds, st, p);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "selfattn pipe launch: %s", hipGetErrorString(e));
+  return sta_launch<selfattn_fwd_pipe_kernel<T, NW, QT>>(what, grid, block, lds, st, p);
 }
 
 #ifdef STA_EXPERIMENT_SELFATTN32
@@ -793,12 +789,8 @@ int launch_sa_pipe(const SParams& p, hipStream_t st) {
 template <typename T, int NKS, int NDT, int QT, bool SUMROW, bool PRE, int NW>
 int launch_sa_geom(const SParams& p, hipStream_t st) {
   constexpr int lds = 3 * (((4 * NKS + 2 * NDT) + NW - 1) / NW * NW) * FRAG;
-  static StaLdsAttr attr;
-  if (!attr.ensure((const void*)selfattn_fwd_kernel<T, NKS, NDT, QT, SUMROW, PRE, NW>, lds)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(selfattn) failed");
   const int tiles = (p.N + 16 * NW * QT - 1) / (16 * NW * QT);
-  hipLaunchKernelGGL((selfattn_fwd_kernel<T, NKS, NDT, QT, SUMROW, PRE, NW>), dim3(tiles * p.H, p.B), dim3(64 * NW), lds, st, p);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "selfattn launch: %s", hipGetErrorString(e));
+  return sta_launch_lds<selfattn_fwd_kernel<T, NKS, NDT, QT, SUMROW, PRE, NW>>("selfattn launch", lds, dim3(tiles * p.H, p.B), dim3(64 * NW), lds, st, p);
 }
 
 template <typename T, int NKS, int NDT, bool SUMROW, bool PRE>
@@ -889,8 +881,7 @@ static int selfattn_fwd_any(const void* q, const void* k, const void* vt, void* 
   SParams p{q, k, vt, out, B, N, C, heads, d, ldq, ldk, vt_row_stride, vt_batch_stride, sl2e, lse, sfrag, flags, flags ? 1 : 0};
   if (flags && !sta_selfattn_optimistic_supported(N, C, heads, scale, dtype))
     return sta_fail(STA_E_UNSUP, "optimistic self-attention: d = 40 with 8 heads, N %% 64 == 0, q in log2 units (scale = ln 2)");
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == STA_BF16 ? dispatch_sa<__bf16>(p, st) : dispatch_sa<_Float16>(p, st);
+  return sta_by_dtype(dtype, [&](auto tag) { return dispatch_sa<decltype(tag)>(p, (hipStream_t)stream); });
 }
 
 extern "C" int sta_selfattn_fwd(const void* q, const void* k, const void* vt, void* out, int B, int N, int C,

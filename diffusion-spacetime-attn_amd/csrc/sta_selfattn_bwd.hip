@@ -444,17 +444,16 @@ int launch_sb(const SBParams& p, hipStream_t st) {
   constexpr int lds_q = 2 * NW * ((2 * 4 * NKS + 2 * NDT + NW - 1) / NW) * FRAG;
   constexpr int bb_kv = NW * ((2 * 4 * NKS + 4 * NDT + 1 + NW - 1) / NW) * FRAG;
   constexpr int lds_kv = (2 * bb_kv <= 160 * 1024 ? 2 : 1) * bb_kv;
-  static StaLdsAttr attr_q, attr_kv;
-  if (!attr_q.ensure((const void*)selfattn_bwd_dq_kernel<T, NKS, NDT, QT, NW, PRE>, lds_q) ||
-      !attr_kv.ensure((const void*)selfattn_bwd_dkv_kernel<T, NKS, NDT, QT, NW>, lds_kv))
-    return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(selfattn backward) failed");
+  constexpr auto dq = selfattn_bwd_dq_kernel<T, NKS, NDT, QT, NW, PRE>;
+  constexpr auto dkv = selfattn_bwd_dkv_kernel<T, NKS, NDT, QT, NW>;
+  const char* const what = "selfattn backward launch";
+  int rc = sta_raise_lds<dq>(what, lds_q);
+  if (!rc) rc = sta_raise_lds<dkv>(what, lds_kv);
   const long total = (long)p.B * p.N * p.H;
-  hipLaunchKernelGGL((selfattn_delta_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);
+  if (!rc) rc = sta_launch<selfattn_delta_kernel<T>>(what, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);
   const int tiles = (p.N + 16 * NW * QT - 1) / (16 * NW * QT);
-  hipLaunchKernelGGL((selfattn_bwd_dkv_kernel<T, NKS, NDT, QT, NW>), dim3(tiles * p.H, p.B), dim3(64 * NW), lds_kv, st, p);
-  hipLaunchKernelGGL((selfattn_bwd_dq_kernel<T, NKS, NDT, QT, NW, PRE>), dim3(tiles * p.H, p.B), dim3(64 * NW), lds_q, st, p);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "selfattn backward launch: %s", hipGetErrorString(e));
+  if (!rc) rc = sta_launch<dkv>(what, dim3(tiles * p.H, p.B), dim3(64 * NW), lds_kv, st, p);
+  return rc ? rc : sta_launch<dq>(what, dim3(tiles * p.H, p.B), dim3(64 * NW), lds_q, st, p);
 }
 
 template <typename T>
@@ -493,10 +492,8 @@ extern "C" int sta_selfattn_bwd(const void* q, const void* k, const void* v, con
   const int d = C / heads;
   if (N % 64 || d % 8 || d > 160 || ld < C || ldg < C || ld % 8 || ldg % 4)
     return sta_fail(STA_E_UNSUP, "self-attention backward needs N %% 64 == 0, d %% 8 == 0, d <= 160, row strides >= C (N=%d d=%d)", N, d);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   float sl2e = scale * 1.4426950408889634f;
   if (fabsf(sl2e - 1.0f) < 1e-6f) sl2e = 1.0f;       // scale = ln 2: q in log2 units — the same snap as the forward that wrote `lse`
   SBParams p{q, k, v, qt, kt, doutt, dout, out, lse, delta, dq, dk, dv, B, N, C, heads, d, ld, ldg, sl2e, scale};
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == STA_BF16 ? dispatch_sb<__bf16>(p, st) : dispatch_sb<_Float16>(p, st);
+  return sta_by_dtype(dtype, [&](auto tag) { return dispatch_sb<decltype(tag)>(p, (hipStream_t)stream); });
 }

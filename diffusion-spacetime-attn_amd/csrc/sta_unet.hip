@@ -638,26 +638,19 @@ __global__ __launch_bounds__(256) void add_bias_nchw_kernel(const T* __restrict_
   }
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "%s launch: %s", what, hipGetErrorString(e));
-}
-
 template <typename T>
 int gn_dispatch(const void* x, const float* add, const void* gamma, const void* beta, void* y, int B, int C, int HW,
                 int G, float eps, int silu, hipStream_t st) {
   const long nvec = (long)(C / G) * HW / 8;
   const dim3 grid(B * G);
-#define STA_GN(NT, NV, CACHED)                                                                                     \
-  hipLaunchKernelGGL((gn_silu_kernel<T, NT, NV, CACHED>), grid, dim3(NT), 0, st, (const T*)x, add, (const T*)gamma, \
-                     (const T*)beta, (T*)y, C, HW, G, eps, silu)
-  if (nvec <= 256 * 2) STA_GN(256, 2, true);
-  else if (nvec <= 256 * 8) STA_GN(256, 8, true);
-  else if (nvec <= 1024 * 4) STA_GN(1024, 4, true);
-  else if (nvec <= 1024 * 8) STA_GN(1024, 8, true);
-  else STA_GN(1024, 1, false);
-#undef STA_GN
-  return launched("groupnorm_silu");
+  const char* const what = "groupnorm_silu launch";
+  const T *xt = (const T*)x, *g = (const T*)gamma, *b = (const T*)beta;
+  T* yt = (T*)y;
+  if (nvec <= 256 * 2) return sta_launch<gn_silu_kernel<T, 256, 2, true>>(what, grid, dim3(256), 0, st, xt, add, g, b, yt, C, HW, G, eps, silu);
+  if (nvec <= 256 * 8) return sta_launch<gn_silu_kernel<T, 256, 8, true>>(what, grid, dim3(256), 0, st, xt, add, g, b, yt, C, HW, G, eps, silu);
+  if (nvec <= 1024 * 4) return sta_launch<gn_silu_kernel<T, 1024, 4, true>>(what, grid, dim3(1024), 0, st, xt, add, g, b, yt, C, HW, G, eps, silu);
+  if (nvec <= 1024 * 8) return sta_launch<gn_silu_kernel<T, 1024, 8, true>>(what, grid, dim3(1024), 0, st, xt, add, g, b, yt, C, HW, G, eps, silu);
+  return sta_launch<gn_silu_kernel<T, 1024, 1, false>>(what, grid, dim3(1024), 0, st, xt, add, g, b, yt, C, HW, G, eps, silu);
 }
 
 }  // namespace
@@ -670,26 +663,23 @@ int sta_groupnorm_silu(const void* x, const float* add, const void* gamma, const
   if (!x || !gamma || !beta || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (B <= 0 || C <= 0 || HW <= 0 || G <= 0 || C % G || HW % 8)
     return sta_fail(STA_E_ARG, "groupnorm: B=%d C=%d HW=%d G=%d (need C %% G == 0, HW %% 8 == 0)", B, C, HW, G);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == STA_BF16 ? gn_dispatch<__bf16>(x, add, gamma, beta, y, B, C, HW, G, eps, silu, st)
-                           : gn_dispatch<_Float16>(x, add, gamma, beta, y, B, C, HW, G, eps, silu, st);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    return gn_dispatch<decltype(tag)>(x, add, gamma, beta, y, B, C, HW, G, eps, silu, (hipStream_t)stream);
+  });
 }
 
 int sta_geglu(const void* x, void* y, long R, int D, int dtype, void* stream) {
   g_sta_err[0] = 0;
   if (!x || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (R <= 0 || D <= 0 || D % 8) return sta_fail(STA_E_ARG, "geglu: R=%ld D=%d (need D %% 8 == 0)", R, D);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const long nvec = R * (D / 8);
   long blocks = (nvec + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(geglu_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const __bf16*)x, (__bf16*)y, nvec, D / 8);
-  else
-    hipLaunchKernelGGL(geglu_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st, (const _Float16*)x, (_Float16*)y, nvec, D / 8);
-  return launched("geglu");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<geglu_kernel<T>>("geglu launch", dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, (T*)y, nvec, D / 8);
+  });
 }
 
 int sta_add_layernorm(const void* x, const void* f, const void* bias, const void* gamma, const void* beta, void* s,
@@ -697,16 +687,13 @@ int sta_add_layernorm(const void* x, const void* f, const void* bias, const void
   g_sta_err[0] = 0;
   if (!x || !gamma || !beta || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (R <= 0 || C <= 0 || C % 8 || C > 2048) return sta_fail(STA_E_ARG, "add_layernorm: R=%ld C=%d (need C %% 8 == 0, C <= 2048)", R, C);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const unsigned blocks = (unsigned)((R + 3) / 4);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(add_layernorm_kernel<__bf16>, dim3(blocks), dim3(256), 0, st, (const __bf16*)x, (const __bf16*)f,
-                       (const __bf16*)bias, (const __bf16*)gamma, (const __bf16*)beta, (__bf16*)s, (__bf16*)y, R, C, eps);
-  else
-    hipLaunchKernelGGL(add_layernorm_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, (const _Float16*)x, (const _Float16*)f,
-                       (const _Float16*)bias, (const _Float16*)gamma, (const _Float16*)beta, (_Float16*)s, (_Float16*)y, R, C, eps);
-  return launched("add_layernorm");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<add_layernorm_kernel<T>>("add_layernorm launch", dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)f, (const T*)bias,
+                                               (const T*)gamma, (const T*)beta, (T*)s, (T*)y, R, C, eps);
+  });
 }
 
 int sta_add_layernorm_qfrag(const void* x, const void* f, const void* bias, const void* gamma, const void* beta, void* s,
@@ -715,25 +702,20 @@ int sta_add_layernorm_qfrag(const void* x, const void* f, const void* bias, cons
   if (!x || !gamma || !beta || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (R <= 0 || R % 16 || C <= 0 || C % 32 || C > 1024)
     return sta_fail(STA_E_ARG, "add_layernorm_qfrag: R=%ld C=%d (need R %% 16 == 0, C %% 32 == 0, C <= 1024)", R, C);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const unsigned blocks = (unsigned)(R / 16);
   hipStream_t st = (hipStream_t)stream;
   if (C > 512) {      // two chunks per lane
-    if (dtype == STA_BF16)
-      hipLaunchKernelGGL(add_layernorm_qfrag_wide_kernel<__bf16>, dim3(blocks), dim3(256), 0, st, (const __bf16*)x, (const __bf16*)f,
-                         (const __bf16*)bias, (const __bf16*)gamma, (const __bf16*)beta, (__bf16*)s, (__bf16*)y, R, C, eps);
-    else
-      hipLaunchKernelGGL(add_layernorm_qfrag_wide_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, (const _Float16*)x, (const _Float16*)f,
-                         (const _Float16*)bias, (const _Float16*)gamma, (const _Float16*)beta, (_Float16*)s, (_Float16*)y, R, C, eps);
-    return launched("add_layernorm_qfrag");
+    return sta_by_dtype(dtype, [&](auto tag) {
+      using T = decltype(tag);
+      return sta_launch<add_layernorm_qfrag_wide_kernel<T>>("add_layernorm_qfrag launch", dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)f,
+                                                            (const T*)bias, (const T*)gamma, (const T*)beta, (T*)s, (T*)y, R, C, eps);
+    });
   }
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(add_layernorm_qfrag_kernel<__bf16>, dim3(blocks), dim3(256), 0, st, (const __bf16*)x, (const __bf16*)f,
-                       (const __bf16*)bias, (const __bf16*)gamma, (const __bf16*)beta, (__bf16*)s, (__bf16*)y, R, C, eps);
-  else
-    hipLaunchKernelGGL(add_layernorm_qfrag_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, (const _Float16*)x, (const _Float16*)f,
-                       (const _Float16*)bias, (const _Float16*)gamma, (const _Float16*)beta, (_Float16*)s, (_Float16*)y, R, C, eps);
-  return launched("add_layernorm_qfrag");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<add_layernorm_qfrag_kernel<T>>("add_layernorm_qfrag launch", dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)f,
+                                                     (const T*)bias, (const T*)gamma, (const T*)beta, (T*)s, (T*)y, R, C, eps);
+  });
 }
 
 int sta_add_bias_nchw(const void* a, const void* b, const void* bias, void* y, int B, int C, int HW, int dtype,
@@ -741,18 +723,15 @@ int sta_add_bias_nchw(const void* a, const void* b, const void* bias, void* y, i
   g_sta_err[0] = 0;
   if (!a || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (B <= 0 || C <= 0 || HW <= 0 || HW % 8) return sta_fail(STA_E_ARG, "add_bias: B=%d C=%d HW=%d (need HW %% 8 == 0)", B, C, HW);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const long nvec = (long)B * C * (HW / 8);
   long blocks = (nvec + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(add_bias_nchw_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const __bf16*)a, (const __bf16*)b,
-                       (const __bf16*)bias, (__bf16*)y, nvec, C, HW / 8);
-  else
-    hipLaunchKernelGGL(add_bias_nchw_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st, (const _Float16*)a, (const _Float16*)b,
-                       (const _Float16*)bias, (_Float16*)y, nvec, C, HW / 8);
-  return launched("add_bias_nchw");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<add_bias_nchw_kernel<T>>("add_bias_nchw launch", dim3((unsigned)blocks), dim3(256), 0, st, (const T*)a, (const T*)b,
+                                               (const T*)bias, (T*)y, nvec, C, HW / 8);
+  });
 }
 
 static int gn_nhwc_chunks(int HW) {
@@ -775,21 +754,18 @@ static int groupnorm_silu_nhwc_impl(const void* x, const void* xb, int Ca, const
     return sta_fail(STA_E_ARG, "groupnorm nhwc: B=%d C=%d HW=%d G=%d (need C %% 8 == 0, C/G >= 8 or == 4, C <= %d, G <= %d)", B, C, HW,
                     G, 8 * GN_NT, GN_MAXG);
   if (xb && (Ca <= 0 || Ca >= C || Ca % 8)) return sta_fail(STA_E_ARG, "groupnorm nhwc cat: Ca=%d of C=%d (need 0 < Ca < C, Ca %% 8 == 0)", Ca, C);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const int nchunk = gn_nhwc_chunks(HW), chunk_px = (HW + nchunk - 1) / nchunk;
   const dim3 grid(nchunk, B);
   hipStream_t st = (hipStream_t)stream;
   float* part = (float*)workspace;
-  if (dtype == STA_BF16) {
-    hipLaunchKernelGGL(gn_nhwc_stats_kernel<__bf16>, grid, dim3(GN_NT), 0, st, (const __bf16*)x, (const __bf16*)xb, Ca, add, part, C, HW, G, chunk_px);
-    hipLaunchKernelGGL(gn_nhwc_apply_kernel<__bf16>, grid, dim3(GN_NT), 0, st, (const __bf16*)x, (const __bf16*)xb, Ca, add, (const float*)nullptr, (const float*)nullptr, (const __bf16*)gamma,
-                       (const __bf16*)beta, part, (__bf16*)y, C, HW, G, chunk_px, eps, silu);
-  } else {
-    hipLaunchKernelGGL(gn_nhwc_stats_kernel<_Float16>, grid, dim3(GN_NT), 0, st, (const _Float16*)x, (const _Float16*)xb, Ca, add, part, C, HW, G, chunk_px);
-    hipLaunchKernelGGL(gn_nhwc_apply_kernel<_Float16>, grid, dim3(GN_NT), 0, st, (const _Float16*)x, (const _Float16*)xb, Ca, add, (const float*)nullptr, (const float*)nullptr, (const _Float16*)gamma,
-                       (const _Float16*)beta, part, (_Float16*)y, C, HW, G, chunk_px, eps, silu);
-  }
-  return launched("groupnorm_silu_nhwc");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const char* const what = "groupnorm_silu_nhwc launch";
+    if (const int rc = sta_launch<gn_nhwc_stats_kernel<T>>(what, grid, dim3(GN_NT), 0, st, (const T*)x, (const T*)xb, Ca, add, part, C, HW, G, chunk_px))
+      return rc;
+    return sta_launch<gn_nhwc_apply_kernel<T>>(what, grid, dim3(GN_NT), 0, st, (const T*)x, (const T*)xb, Ca, add, (const float*)nullptr,
+                                               (const float*)nullptr, (const T*)gamma, (const T*)beta, part, (T*)y, C, HW, G, chunk_px, eps, silu);
+  });
 }
 
 int sta_groupnorm_silu_nhwc(const void* x, const float* add, const void* gamma, const void* beta, void* y,
@@ -807,8 +783,8 @@ int sta_stats_finalize(const float* partial, float* stats, int B, int slots, int
   g_sta_err[0] = 0;
   if (!partial || !stats) return sta_fail(STA_E_ARG, "null pointer");
   if (B <= 0 || slots <= 0 || C <= 0 || C % 2) return sta_fail(STA_E_ARG, "stats_finalize: B=%d slots=%d C=%d (C even)", B, slots, C);
-  hipLaunchKernelGGL(stats_finalize_kernel, dim3((2 * C + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, partial, stats, slots, C);
-  return launched("stats_finalize");
+  return sta_launch<stats_finalize_kernel>("stats_finalize launch", dim3((2 * C + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, partial, stats,
+                                           slots, C);
 }
 
 int sta_groupnorm_silu_nhwc_cstats(const void* xa, const void* xb, int Ca, const float* stats_a, const float* stats_b, const float* add,
@@ -820,36 +796,31 @@ int sta_groupnorm_silu_nhwc_cstats(const void* xa, const void* xb, int Ca, const
     return sta_fail(STA_E_ARG, "groupnorm nhwc: B=%d C=%d HW=%d G=%d (need C %% 8 == 0, C/G >= 8 or == 4, C <= %d, G <= %d)", B, C, HW,
                     G, 8 * GN_NT, GN_MAXG);
   if (xb && (Ca <= 0 || Ca >= C || Ca % 8)) return sta_fail(STA_E_ARG, "groupnorm nhwc cat: Ca=%d of C=%d (need 0 < Ca < C, Ca %% 8 == 0)", Ca, C);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const int nchunk = gn_nhwc_chunks(HW), chunk_px = (HW + nchunk - 1) / nchunk;
   const dim3 grid(nchunk, B);
   hipStream_t st = (hipStream_t)stream;
   if (!xb) Ca = C;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(gn_nhwc_apply_kernel<__bf16>, grid, dim3(GN_NT), 0, st, (const __bf16*)xa, (const __bf16*)xb, Ca, add, stats_a, stats_b,
-                       (const __bf16*)gamma, (const __bf16*)beta, (const float*)nullptr, (__bf16*)y, C, HW, G, chunk_px, eps, silu);
-  else
-    hipLaunchKernelGGL(gn_nhwc_apply_kernel<_Float16>, grid, dim3(GN_NT), 0, st, (const _Float16*)xa, (const _Float16*)xb, Ca, add, stats_a, stats_b,
-                       (const _Float16*)gamma, (const _Float16*)beta, (const float*)nullptr, (_Float16*)y, C, HW, G, chunk_px, eps, silu);
-  return launched("groupnorm_silu_nhwc_cstats");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<gn_nhwc_apply_kernel<T>>("groupnorm_silu_nhwc_cstats launch", grid, dim3(GN_NT), 0, st, (const T*)xa, (const T*)xb, Ca, add,
+                                               stats_a, stats_b, (const T*)gamma, (const T*)beta, (const float*)nullptr, (T*)y, C, HW, G, chunk_px,
+                                               eps, silu);
+  });
 }
 
 int sta_add_bias_rows(const void* a, const void* b, const void* bias, void* y, long rows, int C, int dtype, void* stream) {
   g_sta_err[0] = 0;
   if (!a || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (rows <= 0 || C <= 0 || C % 8) return sta_fail(STA_E_ARG, "add_bias_rows: rows=%ld C=%d (need C %% 8 == 0)", rows, C);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const long nvec = rows * (C / 8);
   long blocks = (nvec + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(add_bias_rows_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const __bf16*)a, (const __bf16*)b,
-                       (const __bf16*)bias, (__bf16*)y, nvec, C / 8);
-  else
-    hipLaunchKernelGGL(add_bias_rows_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st, (const _Float16*)a, (const _Float16*)b,
-                       (const _Float16*)bias, (_Float16*)y, nvec, C / 8);
-  return launched("add_bias_rows");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<add_bias_rows_kernel<T>>("add_bias_rows launch", dim3((unsigned)blocks), dim3(256), 0, st, (const T*)a, (const T*)b,
+                                               (const T*)bias, (T*)y, nvec, C / 8);
+  });
 }
 
 }  // extern "C"

@@ -24,11 +24,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "%s launch: %s", what, hipGetErrorString(e));
-}
-
 // --------------------------------------------------------------------------------------------------
 // GroupNorm (+ pre-add) (+ SiLU) backward on NHWC activations, same work split as the forward (sta_unet.hip): a workgroup
 // takes a chunk of pixels of one image and all channels, a thread keeps one 8-channel column.
@@ -257,14 +252,16 @@ int gn_nhwc_chunks_bwd(int HW) {      // must equal gn_nhwc_chunks of sta_unet.h
 }
 
 template <typename T>
-void gn_bwd_launch(const void* x, const float* add, const void* gamma, const void* beta, const float* part, const void* dy,
+int gn_bwd_launch(const void* x, const float* add, const void* gamma, const void* beta, const float* part, const void* dy,
                    float* partb, void* dx, int B, int C, int HW, int G, float eps, int silu, hipStream_t st) {
   const int nchunk = gn_nhwc_chunks_bwd(HW), chunk_px = (HW + nchunk - 1) / nchunk;
   const dim3 grid(nchunk, B);
-  hipLaunchKernelGGL((gn_nhwc_bwd_kernel<T, false>), grid, dim3(GN_NT), 0, st, (const T*)x, add, (const T*)gamma, (const T*)beta, part,
-                     (const T*)dy, partb, (T*)dx, C, HW, G, chunk_px, eps, silu);
-  hipLaunchKernelGGL((gn_nhwc_bwd_kernel<T, true>), grid, dim3(GN_NT), 0, st, (const T*)x, add, (const T*)gamma, (const T*)beta, part,
-                     (const T*)dy, partb, (T*)dx, C, HW, G, chunk_px, eps, silu);
+  const char* const what = "groupnorm_silu_nhwc_bwd launch";
+  if (const int rc = sta_launch<gn_nhwc_bwd_kernel<T, false>>(what, grid, dim3(GN_NT), 0, st, (const T*)x, add, (const T*)gamma, (const T*)beta,
+                                                              part, (const T*)dy, partb, (T*)dx, C, HW, G, chunk_px, eps, silu))
+    return rc;
+  return sta_launch<gn_nhwc_bwd_kernel<T, true>>(what, grid, dim3(GN_NT), 0, st, (const T*)x, add, (const T*)gamma, (const T*)beta, part,
+                                                 (const T*)dy, partb, (T*)dx, C, HW, G, chunk_px, eps, silu);
 }
 
 }  // namespace
@@ -279,31 +276,24 @@ int sta_groupnorm_silu_nhwc_bwd(const void* x, const float* add, const void* gam
   if (B <= 0 || C <= 0 || HW <= 0 || G <= 0 || G > GN_MAXG || C % G || C % 8 || (C / G < 8 && C / G != 4) || C / 8 > GN_NT)
     return sta_fail(STA_E_ARG, "groupnorm nhwc bwd: B=%d C=%d HW=%d G=%d (need C %% 8 == 0, C/G >= 8 or == 4, C <= %d, G <= %d)", B, C, HW,
                     G, 8 * GN_NT, GN_MAXG);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    gn_bwd_launch<__bf16>(x, add, gamma, beta, (const float*)fwd_workspace, dy, (float*)bwd_workspace, dx, B, C, HW, G, eps, silu, st);
-  else
-    gn_bwd_launch<_Float16>(x, add, gamma, beta, (const float*)fwd_workspace, dy, (float*)bwd_workspace, dx, B, C, HW, G, eps, silu, st);
-  return launched("groupnorm_silu_nhwc_bwd");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    return gn_bwd_launch<decltype(tag)>(x, add, gamma, beta, (const float*)fwd_workspace, dy, (float*)bwd_workspace, dx, B, C, HW, G, eps, silu,
+                                        (hipStream_t)stream);
+  });
 }
 
 int sta_geglu_bwd(const void* x, const void* dy, void* dx, long R, int D, int dtype, void* stream) {
   g_sta_err[0] = 0;
   if (!x || !dy || !dx) return sta_fail(STA_E_ARG, "null pointer");
   if (R <= 0 || D <= 0 || D % 8) return sta_fail(STA_E_ARG, "geglu bwd: R=%ld D=%d (need D %% 8 == 0)", R, D);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const long nvec = R * (D / 8);
   long blocks = (nvec + 255) / 256;
   if (blocks > 256 * 32) blocks = 256 * 32;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(geglu_bwd_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, st, (const __bf16*)x, (const __bf16*)dy, (__bf16*)dx,
-                       nvec, D / 8);
-  else
-    hipLaunchKernelGGL(geglu_bwd_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, st, (const _Float16*)x, (const _Float16*)dy,
-                       (_Float16*)dx, nvec, D / 8);
-  return launched("geglu_bwd");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<geglu_bwd_kernel<T>>("geglu_bwd launch", dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+                                           (const T*)dy, (T*)dx, nvec, D / 8);
+  });
 }
 
 int sta_layernorm_bwd(const void* s, const void* gamma, const void* dy, const void* dres, void* ds, long R, int C, float eps, int dtype,
@@ -311,16 +301,12 @@ int sta_layernorm_bwd(const void* s, const void* gamma, const void* dy, const vo
   g_sta_err[0] = 0;
   if (!s || !gamma || !dy || !ds) return sta_fail(STA_E_ARG, "null pointer");
   if (R <= 0 || C <= 0 || C % 8 || C > 2048) return sta_fail(STA_E_ARG, "layernorm bwd: R=%ld C=%d (need C %% 8 == 0, C <= 2048)", R, C);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const unsigned blocks = (unsigned)((R + 3) / 4);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(layernorm_bwd_kernel<__bf16>, dim3(blocks), dim3(256), 0, st, (const __bf16*)s, (const __bf16*)gamma, (const __bf16*)dy,
-                       (const __bf16*)dres, (__bf16*)ds, R, C, eps);
-  else
-    hipLaunchKernelGGL(layernorm_bwd_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, (const _Float16*)s, (const _Float16*)gamma,
-                       (const _Float16*)dy, (const _Float16*)dres, (_Float16*)ds, R, C, eps);
-  return launched("layernorm_bwd");
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<layernorm_bwd_kernel<T>>("layernorm_bwd launch", dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)s,
+                                               (const T*)gamma, (const T*)dy, (const T*)dres, (T*)ds, R, C, eps);
+  });
 }
 
 }  // extern "C"

@@ -546,10 +546,12 @@ int sta_fail(int code, const char* fmt, ...) {
   va_end(ap);
   return code;
 }
+int sta_launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+}
 
 namespace {
-#define g_err g_sta_err
-#define fail sta_fail
 
 // Pixel tiles per wave of the wave-per-context kernel. QT > 1 reuses each fragment for more pixels but
 // measured slower at every level (register pressure: N=1024 d=80 7.2 -> 8.7 us; 8 images 39.8 -> 52.8 us),
@@ -572,12 +574,8 @@ int launch_fwd(const Params& p0, hipStream_t st) {
   p.head_major = (p.H % 8 == 0 && NDT >= 5) ? 1 : 0;
   if (g_sta_opt[STA_OPT_HEAD_MAJOR]) p.head_major = g_sta_opt[STA_OPT_HEAD_MAJOR] == 1 ? 1 : 0;
   const int lds = NSLOT * 16 * QT * (p.d + 4) * (int)sizeof(float);
-  static StaLdsAttr attr;
   constexpr int lds_max = NSLOT * 16 * QT * (16 * NDT + 4) * (int)sizeof(float);
-  if (!attr.ensure((const void*)xattn_fwd_kernel<T, NDT, QT>, lds_max)) return fail(STA_E_LAUNCH, "hipFuncSetAttribute(fwd) failed");
-  hipLaunchKernelGGL((xattn_fwd_kernel<T, NDT, QT>), dim3(p.ntiles * p.H, p.n_img), dim3(256), lds, st, p);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : fail(STA_E_LAUNCH, "fwd launch: %s", hipGetErrorString(e));
+  return sta_launch_lds<xattn_fwd_kernel<T, NDT, QT>>("fwd launch", lds_max, dim3(p.ntiles * p.H, p.n_img), dim3(256), lds, st, p);
 }
 
 template <typename T, int NDT, int QT, int NWV>
@@ -620,19 +618,15 @@ int launch_fwd_staged_cfg(const Params& p0, hipStream_t st) {
   // multi-tile launches carry several images: with the grid-wide XCD-contiguous map an XCD owns whole (image, tile
   // group) units — all 8 heads, so q lines AND the image's K/V fragments are fetched by one L2 only
   if (iters > 1 && !g_sta_opt[STA_OPT_HEAD_MAJOR]) p.head_major = 0;
-  auto launch = [&](auto kernel, StaLdsAttr& attr) {
-    if (!attr.ensure((const void*)kernel, 160 * 1024)) return fail(STA_E_LAUNCH, "hipFuncSetAttribute(fwd staged) failed");
-    hipLaunchKernelGGL(kernel, dim3(p.ntiles * p.H, p.n_img), dim3(64 * NWV), lds, st, p);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? STA_OK : fail(STA_E_LAUNCH, "fwd staged launch: %s", hipGetErrorString(e));
-  };
-  static StaLdsAttr attr1, attrn;
+  const char* const what = "fwd staged launch";
+  const dim3 grid(p.ntiles * p.H, p.n_img), block(64 * NWV);
+  constexpr int LIM = 160 * 1024;
   if constexpr (NDT >= 5) {
-    static StaLdsAttr attr1l, attrnl;
-    if (ll2) return iters == 1 ? launch(xattn_fwd_staged_kernel<T, NDT, QT, NWV, 1, true>, attr1l) : launch(xattn_fwd_staged_kernel<T, NDT, QT, NWV, STAGED_MAXIT, true>, attrnl);
+    if (ll2) return iters == 1 ? sta_launch_lds<xattn_fwd_staged_kernel<T, NDT, QT, NWV, 1, true>>(what, LIM, grid, block, lds, st, p)
+                               : sta_launch_lds<xattn_fwd_staged_kernel<T, NDT, QT, NWV, STAGED_MAXIT, true>>(what, LIM, grid, block, lds, st, p);
   }
-  if (iters == 1) return launch(xattn_fwd_staged_kernel<T, NDT, QT, NWV, 1>, attr1);
-  return launch(xattn_fwd_staged_kernel<T, NDT, QT, NWV, STAGED_MAXIT>, attrn);
+  if (iters == 1) return sta_launch_lds<xattn_fwd_staged_kernel<T, NDT, QT, NWV, 1>>(what, LIM, grid, block, lds, st, p);
+  return sta_launch_lds<xattn_fwd_staged_kernel<T, NDT, QT, NWV, STAGED_MAXIT>>(what, LIM, grid, block, lds, st, p);
 }
 
 // Workgroup shape of the LDS-resident kernel (rocprofv3 durations in profiles/r01_kernel_variants.md).
@@ -713,7 +707,7 @@ int dispatch_fwd(const Params& p, hipStream_t st) {
     case 9: return launch_fwd_qt<T, 9>(p, qt, st);
     case 10: return launch_fwd_qt<T, 10>(p, qt, st);
   }
-  return fail(STA_E_UNSUP, "head dim %d unsupported", p.d);
+  return sta_fail(STA_E_UNSUP, "head dim %d unsupported", p.d);
 }
 
 }  // namespace
@@ -735,13 +729,13 @@ int sta_version(void) { return STA_VERSION; }
 const char* sta_built_with(void) { return STA_BUILT_WITH; }
 
 int sta_set_option(int key, int value) {
-  g_err[0] = 0;
-  if (key < 0 || key >= STA_OPT_COUNT) return fail(STA_E_ARG, "unknown option %d", key);
+  g_sta_err[0] = 0;
+  if (key < 0 || key >= STA_OPT_COUNT) return sta_fail(STA_E_ARG, "unknown option %d", key);
   g_sta_opt[key] = value;
   return STA_OK;
 }
 
-const char* sta_last_error(void) { return g_err; }
+const char* sta_last_error(void) { return g_sta_err; }
 
 size_t sta_xattn_packed_kv_bytes(int n_ctx, int heads, int d) {
   if (n_ctx <= 0 || heads <= 0 || d <= 0 || d % 8 || d > STA_MAX_HEAD_DIM) return 0;
@@ -750,33 +744,26 @@ size_t sta_xattn_packed_kv_bytes(int n_ctx, int heads, int d) {
 
 int sta_xattn_pack_kv(const void* k, const void* v, void* packed, int n_ctx, int M, int C, int heads,
                       int dtype, void* stream) {
-  g_err[0] = 0;
-  if (!k || !v || !packed) return fail(STA_E_ARG, "null pointer");
-  if (n_ctx <= 0) return fail(STA_E_ARG, "n_ctx=%d", n_ctx);
+  g_sta_err[0] = 0;
+  if (!k || !v || !packed) return sta_fail(STA_E_ARG, "null pointer");
+  if (n_ctx <= 0) return sta_fail(STA_E_ARG, "n_ctx=%d", n_ctx);
   if (int rc = check_shape(16, C, heads, M, 0)) return rc;
-  if (dtype != STA_BF16 && dtype != STA_F16) return fail(STA_E_UNSUP, "dtype %d", dtype);
   const int d = C / heads, ndt = (d + 15) / 16;
-  const dim3 grid(all_frags(ndt), n_ctx * heads);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(pack_kv_kernel<__bf16>, grid, dim3(64), 0, st, (const __bf16*)k, (const __bf16*)v,
-                       (__bf16*)packed, n_ctx, M, C, heads, d, ndt);
-  else
-    hipLaunchKernelGGL(pack_kv_kernel<_Float16>, grid, dim3(64), 0, st, (const _Float16*)k,
-                       (const _Float16*)v, (_Float16*)packed, n_ctx, M, C, heads, d, ndt);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : fail(STA_E_LAUNCH, "pack launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_kv_kernel<T>>("pack launch", dim3(all_frags(ndt), n_ctx * heads), dim3(64), 0, (hipStream_t)stream, (const T*)k,
+                                         (const T*)v, (T*)packed, n_ctx, M, C, heads, d, ndt);
+  });
 }
 
 int sta_xattn_fwd(const void* q, const void* packed, const uint8_t* mask, const float* coef, void* out,
                   float* maps, int n_img, int N, int C, int heads, int M, int K, float scale, int dtype,
                   void* stream) {
-  g_err[0] = 0;
-  if (!q || !packed || !out) return fail(STA_E_ARG, "null pointer");
-  if (n_img < 1 || n_img > 65535) return fail(STA_E_ARG, "n_img=%d", n_img);
+  g_sta_err[0] = 0;
+  if (!q || !packed || !out) return sta_fail(STA_E_ARG, "null pointer");
+  if (n_img < 1 || n_img > 65535) return sta_fail(STA_E_ARG, "n_img=%d", n_img);
   if (int rc = check_shape(N, C, heads, M, K)) return rc;
-  if (K > 0 && (!mask || !coef)) return fail(STA_E_ARG, "mask/coef required when K > 0");
-  if (dtype != STA_BF16 && dtype != STA_F16) return fail(STA_E_UNSUP, "dtype %d", dtype);
+  if (K > 0 && (!mask || !coef)) return sta_fail(STA_E_ARG, "mask/coef required when K > 0");
   Params p{};
   p.q = q; p.packed = (const char*)packed; p.mask = mask; p.coef = coef; p.out = out; p.dout = nullptr;
   if (K == 0) {  // the kernel's prologue loads are unconditional: give it readable (ignored) bytes
@@ -785,8 +772,7 @@ int sta_xattn_fwd(const void* q, const void* packed, const uint8_t* mask, const 
   }
   p.aux = maps; p.N = N; p.C = C; p.H = heads; p.d = C / heads; p.M = M; p.K = K; p.n_img = n_img;
   p.scale = scale; p.sl2e = scale * 1.4426950408889634f;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == STA_BF16 ? dispatch_fwd<__bf16>(p, st) : dispatch_fwd<_Float16>(p, st);
+  return sta_by_dtype(dtype, [&](auto tag) { return dispatch_fwd<decltype(tag)>(p, (hipStream_t)stream); });
 }
 
 

@@ -23,8 +23,6 @@
 #include "sta_xattn_dev.h"
 
 namespace {
-#define g_err g_sta_err
-#define fail sta_fail
 
 // --------------------------------------------------------------------------------------------------
 // backward (dq, dcoef)
@@ -378,22 +376,12 @@ int launch_bwd_res(const Params& p0, float* dcoef, hipStream_t st) {
   p.iters = iters;
   p.ntiles = (p.tiles + iters - 1) / iters;                 // workgroups per head
   const int nwg = p.ntiles * p.H;
-  auto launch = [&](auto kernel, StaLdsAttr& attr) {
-    if (!attr.ensure((const void*)kernel, 160 * 1024)) return fail(STA_E_LAUNCH, "hipFuncSetAttribute(bwd resident) failed");
-    hipLaunchKernelGGL(kernel, dim3(nwg, p.n_img), dim3(64 * NWV), lds, st, p);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? STA_OK : fail(STA_E_LAUNCH, "bwd resident launch: %s", hipGetErrorString(e));
-  };
-  static StaLdsAttr attr_fast, attr_any;
-  const int rc = p.M > 16 * (NKT - 1) ? launch(xattn_bwd_res_kernel<T, NDT, NWV, QT, true>, attr_fast)
-                                      : launch(xattn_bwd_res_kernel<T, NDT, NWV, QT, false>, attr_any);
-  if (rc) return rc;
-  if (p.K > 0) {
-    hipLaunchKernelGGL(dcoef_reduce_kernel, dim3(p.K, p.n_img), dim3(256), 0, st, p.aux, dcoef, nwg * NWV);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(STA_E_LAUNCH, "dcoef reduce launch: %s", hipGetErrorString(e));
-  }
-  return STA_OK;
+  const char* const what = "bwd resident launch";
+  const dim3 grid(nwg, p.n_img), block(64 * NWV);
+  const int rc = p.M > 16 * (NKT - 1) ? sta_launch_lds<xattn_bwd_res_kernel<T, NDT, NWV, QT, true>>(what, 160 * 1024, grid, block, lds, st, p)
+                                      : sta_launch_lds<xattn_bwd_res_kernel<T, NDT, NWV, QT, false>>(what, 160 * 1024, grid, block, lds, st, p);
+  if (rc || p.K <= 0) return rc;
+  return sta_launch<dcoef_reduce_kernel>("dcoef reduce launch", dim3(p.K, p.n_img), dim3(256), 0, st, p.aux, dcoef, nwg * NWV);
 }
 
 // The product launches 4 waves x ONE 16-pixel tile per wave, one workgroup per CU. The two wider builds — eight waves (two per SIMD),
@@ -427,7 +415,7 @@ int dispatch_bwd(const Params& p, float* dcoef, hipStream_t st) {
     case 9: return launch_bwd_any<T, 9>(p, dcoef, st);
     case 10: return launch_bwd_any<T, 10>(p, dcoef, st);
   }
-  return fail(STA_E_UNSUP, "head dim %d unsupported", p.d);
+  return sta_fail(STA_E_UNSUP, "head dim %d unsupported", p.d);
 }
 
 }  // namespace
@@ -443,13 +431,13 @@ size_t sta_xattn_bwd_workspace_bytes(int n_img, int N, int heads, int K) {
 int sta_xattn_bwd(const void* q, const void* packed, const uint8_t* mask, const float* coef,
                   const void* dout, void* dq, float* dcoef, void* workspace, int n_img, int N, int C, int heads,
                   int M, int K, float scale, int dtype, void* stream) {
-  g_err[0] = 0;
-  if (!q || !packed || !dout || !dq) return fail(STA_E_ARG, "null pointer");
-  if (n_img < 1 || n_img > 65535) return fail(STA_E_ARG, "n_img=%d", n_img);
+  g_sta_err[0] = 0;
+  if (!q || !packed || !dout || !dq) return sta_fail(STA_E_ARG, "null pointer");
+  if (n_img < 1 || n_img > 65535) return sta_fail(STA_E_ARG, "n_img=%d", n_img);
   if (int rc = check_shape(N, C, heads, M, K)) return rc;
-  if (K > 0 && (!mask || !coef || !dcoef || !workspace)) return fail(STA_E_ARG, "mask/coef/dcoef/workspace required when K > 0");
-  if (dtype != STA_BF16 && dtype != STA_F16) return fail(STA_E_UNSUP, "dtype %d", dtype);
-  if ((size_t)2 * N * C * 2 >= 0xfffffff0ull) return fail(STA_E_UNSUP, "one image of activations must stay below 4 GiB");
+  if (K > 0 && (!mask || !coef || !dcoef || !workspace)) return sta_fail(STA_E_ARG, "mask/coef/dcoef/workspace required when K > 0");
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
+  if ((size_t)2 * N * C * 2 >= 0xfffffff0ull) return sta_fail(STA_E_UNSUP, "one image of activations must stay below 4 GiB");
   Params p{};
   p.q = q; p.packed = (const char*)packed; p.mask = mask; p.coef = coef; p.out = dq; p.dout = dout;
   if (K == 0) {  // unconditional prologue loads: readable (ignored) bytes
@@ -458,8 +446,7 @@ int sta_xattn_bwd(const void* q, const void* packed, const uint8_t* mask, const 
   }
   p.aux = (float*)workspace; p.N = N; p.C = C; p.H = heads; p.d = C / heads; p.M = M; p.K = K; p.n_img = n_img;
   p.scale = scale; p.sl2e = scale * 1.4426950408889634f;
-  hipStream_t st = (hipStream_t)stream;
-  return dtype == STA_BF16 ? dispatch_bwd<__bf16>(p, dcoef, st) : dispatch_bwd<_Float16>(p, dcoef, st);
+  return sta_by_dtype(dtype, [&](auto tag) { return dispatch_bwd<decltype(tag)>(p, dcoef, (hipStream_t)stream); });
 }
 
 }  // extern "C"

@@ -486,11 +486,8 @@ int launch_proj_wqs(PParams p, int n_img, hipStream_t st) {
   if (const int v = g_sta_opt[STA_OPT_STAGED_TILES]) p.iters = v < p.tiles ? v : p.tiles;
   p.W = (p.tiles + p.iters - 1) / p.iters;
   const int lds = (2 * WQS_CH * NDT + 2 * fwd_frags(NDT)) * FRAG;
-  static StaLdsAttr attr;
-  if (!attr.ensure((const void*)xattn_fwd_proj_wqs_kernel<T, NDT, NWV, QT>, 160 * 1024)) return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(fwd proj, streamed Wq) failed");
-  hipLaunchKernelGGL((xattn_fwd_proj_wqs_kernel<T, NDT, NWV, QT>), dim3(p.W * p.H, n_img), dim3(64 * NWV), lds, st, p);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "fwd proj (streamed Wq) launch: %s", hipGetErrorString(e));
+  return sta_launch_lds<xattn_fwd_proj_wqs_kernel<T, NDT, NWV, QT>>("fwd proj (streamed Wq) launch", 160 * 1024, dim3(p.W * p.H, n_img), dim3(64 * NWV),
+                                                                    lds, st, p);
 }
 
 template <typename T, int NDT, int NWV, int RING, bool LL2 = false, bool YFRAG = false>
@@ -505,12 +502,8 @@ int launch_proj_cfg(PParams p, int n_img, int lds, hipStream_t st) {
   p.iters = (int)((p.tiles + wg_per_head - 1) / wg_per_head);
   if (const int v = g_sta_opt[STA_OPT_STAGED_TILES]) p.iters = v < p.tiles ? v : p.tiles;
   p.W = (p.tiles + p.iters - 1) / p.iters;
-  static StaLdsAttr attr;
-  if (!attr.ensure((const void*)xattn_fwd_proj_kernel<T, NDT, NWV, RING, LL2, YFRAG>, 160 * 1024))
-    return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(fwd proj) failed");
-  hipLaunchKernelGGL((xattn_fwd_proj_kernel<T, NDT, NWV, RING, LL2, YFRAG>), dim3(p.W * p.H, n_img), dim3(64 * NWV), lds, st, p);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "fwd proj launch: %s", hipGetErrorString(e));
+  return sta_launch_lds<xattn_fwd_proj_kernel<T, NDT, NWV, RING, LL2, YFRAG>>("fwd proj launch", 160 * 1024, dim3(p.W * p.H, n_img), dim3(64 * NWV), lds,
+                                                                              st, p);
 }
 
 template <typename T, int NDT>
@@ -613,24 +606,18 @@ int sta_xattn_pack_wq(const void* wq, void* packed, int C, int heads, int dtype,
   g_sta_err[0] = 0;
   if (!wq || !packed) return sta_fail(STA_E_ARG, "null pointer");
   if (sta_xattn_packed_wq_bytes(C, heads) == 0) return sta_fail(STA_E_UNSUP, "C=%d heads=%d unsupported", C, heads);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const int d = C / heads, ndt = (d + 15) / 16;
   const dim3 grid(ndt * (C / 32), heads);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(pack_wq_kernel<__bf16>, grid, dim3(64), 0, st, (const __bf16*)wq, (__bf16*)packed, C, d, ndt);
-  else
-    hipLaunchKernelGGL(pack_wq_kernel<_Float16>, grid, dim3(64), 0, st, (const _Float16*)wq, (_Float16*)packed, C, d, ndt);
-  if (sta_p3::shape_ok(C, heads)) {      // the same weights per head PAIR: 2d = 80 output columns = 5 tiles, no padding
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const int rc = sta_launch<pack_wq_kernel<T>>("pack_wq launch", grid, dim3(64), 0, st, (const T*)wq, (T*)packed, C, d, ndt);
+    if (rc || !sta_p3::shape_ok(C, heads)) return rc;
+    // the same weights per head PAIR: 2d = 80 output columns = 5 tiles, no padding
     char* pair = (char*)packed + (size_t)heads * ndt * (C / 32) * FRAG;
     const dim3 g2(sta_p3::NT * (C / 32), heads / 2);
-    if (dtype == STA_BF16)
-      hipLaunchKernelGGL(pack_wq_kernel<__bf16>, g2, dim3(64), 0, st, (const __bf16*)wq, (__bf16*)pair, C, 2 * d, sta_p3::NT);
-    else
-      hipLaunchKernelGGL(pack_wq_kernel<_Float16>, g2, dim3(64), 0, st, (const _Float16*)wq, (_Float16*)pair, C, 2 * d, sta_p3::NT);
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_wq launch: %s", hipGetErrorString(e));
+    return sta_launch<pack_wq_kernel<T>>("pack_wq launch", g2, dim3(64), 0, st, (const T*)wq, (T*)pair, C, 2 * d, sta_p3::NT);
+  });
 }
 
 size_t sta_xattn_packed_kv_proj_bytes(int n_ctx, int heads, int d) {
@@ -648,20 +635,14 @@ int sta_xattn_pack_kv_proj(const void* k, const void* v, void* packed, int n_ctx
   const int d = C / heads, ndt = (d + 15) / 16;
   if (sta_xattn_packed_kv_proj_bytes(n_ctx, heads, d) == 0) return sta_fail(STA_E_UNSUP, "head dim %d unsupported", d);
   if (M <= 0 || M > STA_MAX_KEYS) return sta_fail(STA_E_UNSUP, "M=%d keys unsupported (max %d)", M, STA_MAX_KEYS);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
   const dim3 grid(fwd_frags(ndt), n_ctx * heads);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(pack_kv_proj_kernel<__bf16>, grid, dim3(64), 0, st, (const __bf16*)k, (const __bf16*)v,
-                       (__bf16*)packed, M, C, heads, d, ndt);
-  else
-    hipLaunchKernelGGL(pack_kv_proj_kernel<_Float16>, grid, dim3(64), 0, st, (const _Float16*)k, (const _Float16*)v,
-                       (_Float16*)packed, M, C, heads, d, ndt);
-  if (d == sta_p3::D && heads % 2 == 0 && M <= sta_p3::KR) {
-    if (int rc = sta_p3::pack_kv(k, v, (char*)packed + (size_t)n_ctx * heads * fwd_frags(ndt) * FRAG, n_ctx, M, C, heads, dtype, st)) return rc;
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_kv_proj launch: %s", hipGetErrorString(e));
+  const int rc = sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_kv_proj_kernel<T>>("pack_kv_proj launch", grid, dim3(64), 0, st, (const T*)k, (const T*)v, (T*)packed, M, C, heads, d, ndt);
+  });
+  if (rc || !(d == sta_p3::D && heads % 2 == 0 && M <= sta_p3::KR)) return rc;
+  return sta_p3::pack_kv(k, v, (char*)packed + (size_t)n_ctx * heads * fwd_frags(ndt) * FRAG, n_ctx, M, C, heads, dtype, st);
 }
 
 // does a launch of this shape take the head-pair kernel (sta_xattn_proj3.hip)?
@@ -743,15 +724,16 @@ static int fwd_proj_impl(const void* y, const void* packed_wq, const void* packe
     if (qfrag || ofrag) return sta_fail(STA_E_UNSUP, "the streamed-Wq kernel reads y row-major");
     // STA_OPT_STAGED_QT = 2: four waves x two 16-pixel tiles per wave (one wave per SIMD, each Wq fragment read serves four MFMAs);
     // default: eight waves x one tile
-    if (g_sta_opt[STA_OPT_STAGED_QT] == 2)
-      return dtype == STA_BF16 ? launch_proj_wqs<__bf16, 10, 4, 2>(p, n_img, st) : launch_proj_wqs<_Float16, 10, 4, 2>(p, n_img, st);
-    return dtype == STA_BF16 ? launch_proj_wqs<__bf16, 10, 8, 1>(p, n_img, st) : launch_proj_wqs<_Float16, 10, 8, 1>(p, n_img, st);
+    const bool qt2 = g_sta_opt[STA_OPT_STAGED_QT] == 2;
+    return sta_by_dtype(dtype, [&](auto tag) {
+      return qt2 ? launch_proj_wqs<decltype(tag), 10, 4, 2>(p, n_img, st) : launch_proj_wqs<decltype(tag), 10, 8, 1>(p, n_img, st);
+    });
   }
   if (ll2) {      // SD-v1 level 1: Wq + the two mandatory contexts resident, local contexts from L2
     if (qfrag && N % 16) return sta_fail(STA_E_UNSUP, "query-fragment order needs N %% 16 == 0 (N=%d)", N);
     if (ofrag) return sta_fail(STA_E_UNSUP, "out-fragment order is written by the head-pair kernel only");
-    return dtype == STA_BF16 ? launch_proj_ll2<__bf16>(p, n_img, lds, st, qfrag) : launch_proj_ll2<_Float16>(p, n_img, lds, st, qfrag);
+    return sta_by_dtype(dtype, [&](auto tag) { return launch_proj_ll2<decltype(tag)>(p, n_img, lds, st, qfrag); });
   }
   if (qfrag) return sta_fail(STA_E_UNSUP, "query-fragment order is read by the head-pair and the locals-from-L2 kernels only (sta_xattn_fwd_proj_qfrag_supported)");
-  return dtype == STA_BF16 ? dispatch_proj<__bf16>(p, n_img, lds, st) : dispatch_proj<_Float16>(p, n_img, lds, st);
+  return sta_by_dtype(dtype, [&](auto tag) { return dispatch_proj<decltype(tag)>(p, n_img, lds, st); });
 }

@@ -699,12 +699,7 @@ int launch_p3(P3 p, int n_img, hipStream_t st) {
   if (const int v = g_sta_opt[STA_OPT_STAGED_TILES]) p.iters = v < p.tiles ? v : p.tiles;
   p.W = (p.tiles + p.iters - 1) / p.iters;
   const int lds = lds_bytes(p.C, p.K);
-  static StaLdsAttr attr;
-  if (!attr.ensure((const void*)xattn_fwd_proj_p3_kernel<T, NKC, YL, OF>, 160 * 1024))
-    return sta_fail(STA_E_LAUNCH, "hipFuncSetAttribute(fwd proj p3) failed");
-  hipLaunchKernelGGL((xattn_fwd_proj_p3_kernel<T, NKC, YL, OF>), dim3(p.W * pairs, n_img), dim3(512), lds, st, p);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "fwd proj p3 launch: %s", hipGetErrorString(e));
+  return sta_launch_lds<xattn_fwd_proj_p3_kernel<T, NKC, YL, OF>>("fwd proj p3 launch", 160 * 1024, dim3(p.W * pairs, n_img), dim3(512), lds, st, p);
 }
 
 }  // namespace
@@ -713,12 +708,10 @@ namespace sta_p3 {
 
 int pack_kv(const void* k, const void* v, void* packed, int n_ctx, int M, int C, int heads, int dtype, hipStream_t st) {
   const dim3 grid(n_ctx * heads);
-  if (dtype == STA_BF16)
-    hipLaunchKernelGGL(pack_kv_p3_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16*)k, (const __bf16*)v, (__bf16*)packed, M, C, heads);
-  else
-    hipLaunchKernelGGL(pack_kv_p3_kernel<_Float16>, grid, dim3(256), 0, st, (const _Float16*)k, (const _Float16*)v, (_Float16*)packed, M, C, heads);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? STA_OK : sta_fail(STA_E_LAUNCH, "pack_kv_p3 launch: %s", hipGetErrorString(e));
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<pack_kv_p3_kernel<T>>("pack_kv_p3 launch", grid, dim3(256), 0, st, (const T*)k, (const T*)v, (T*)packed, M, C, heads);
+  });
 }
 
 int forward(const void* y, const void* wq_pair, const void* kv, const uint8_t* mask, const float* coef, void* out, int n_img,
@@ -728,6 +721,8 @@ int forward(const void* y, const void* wq_pair, const void* kv, const uint8_t* m
   p.y = y; p.wq = (const char*)wq_pair; p.kv = (const char*)kv; p.mask = mask; p.coef = coef; p.out = out;
   p.N = N; p.C = C; p.H = heads; p.M = M; p.K = K; p.sl2e = sl2e;
   if (ofrag && !(qfrag && C == 320)) return sta_fail(STA_E_UNSUP, "out-fragment order needs y in query-fragment order and C = 320");
+  // (bf16 / f16 alternate below instead of one sta_by_dtype: that is the order the kernels take in the assembly, and the padded
+  // sites csrc/.isa_lint.log lists for this file are named by line)
   if (qfrag) {      // y in query-fragment order (sta_add_layernorm_qfrag): 1-KiB coalesced loads, no hand-over
     if (N % 16) return sta_fail(STA_E_UNSUP, "query-fragment order needs N %% 16 == 0 (N=%d)", N);
     if (ofrag) {
