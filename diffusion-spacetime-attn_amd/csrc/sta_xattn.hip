@@ -531,6 +531,115 @@ __global__ __launch_bounds__(64 * NWV, NWV == 12 ? 3 : 1) void xattn_fwd_staged_
 }
 
 // --------------------------------------------------------------------------------------------------
+// token maps: where the pixels attend — the head mean of the softmax mass on weighted key sets
+// --------------------------------------------------------------------------------------------------
+// A diagnostic beside the forward (no V side, no blend, no disc mask): readout r names a context and a weight row over
+// its keys, and out[r][p] = mean_h sum_m w[r][m] P_h[p][m]. The maps output of the forward kernel above is the same P
+// written out in full ([K+2][heads][N][M] fp32, 40 MB per image at N = 4096); here only R floats per pixel leave the wave.
+// One wave per (16-pixel tile, work item); a work item is a context and up to MAPS_RB of the readouts that name it,
+// listed by the host (contexts nobody reads start no wave; a context read by more than MAPS_RB readouts is attended once
+// per group). As in the wave-per-context forward the K fragments are MFMA A operands straight from the packed image and a
+// lane owns one pixel: after the softmax it holds keys 16t + 4g + r of pixel lane & 15, so the key weights of a readout are
+// 20 registers per lane, loaded once, and the weighted sum is 20 fmas per head and readout. The lane's partial sums are
+// scaled by the pixel's 1 / denominator and added over the heads IN REGISTERS; one butterfly over the four lane rows per
+// readout ends the wave and lane row 0 writes its 16 pixels. No LDS, no atomics, every output element has one writer and
+// one summation order: results are bit-reproducible and independent of the number of images in the launch.
+constexpr int MAPS_RB = 4;
+struct MapWork {
+  int n;                                   // work items
+  int ctx[STA_MAX_READOUTS];               // context of item i
+  int nr[STA_MAX_READOUTS];                // readouts it carries (1 .. MAPS_RB)
+  unsigned rd[STA_MAX_READOUTS];           // their indices, one byte each
+};
+struct MapParams {
+  const void* q;         // [n_img][2][N][C]
+  const char* packed;    // fragment image, image-major
+  const float* w;        // [n_img][R][M]
+  float* out;            // [n_img][R][N]
+  int N, C, H, d, M, K, R, accumulate;
+  float sl2e, inv_heads;
+  MapWork wk;
+};
+
+template <typename T, int NDT>
+__global__ __launch_bounds__(64) void xattn_token_maps_kernel(const MapParams p) {
+  using V8 = typename Tr<T>::V8;
+  constexpr int NKS = nks_of(NDT);
+  constexpr int NKF = NKT * NKS;
+  const int lane = threadIdx.x, g = lane >> 4, c16 = lane & 15;
+  const int img = blockIdx.y;
+  const int item = blockIdx.x % p.wk.n, tile = blockIdx.x / p.wk.n;
+  const int cc = p.wk.ctx[item], nr = p.wk.nr[item];
+  const unsigned rdp = p.wk.rd[item];
+  const int N = p.N, d = p.d, M = p.M, R = p.R;
+  const int px = tile * 16 + c16;
+
+  // context 0 is attended by the uncond row of q, every other context by the cond row (include/sta_xattn.h)
+  const unsigned row_bytes = (unsigned)p.C * (unsigned)sizeof(T);
+  const size_t plane = (size_t)N * row_bytes;
+  const __amdgpu_buffer_rsrc_t q_srd = make_srd((const char*)p.q + ((size_t)2 * img + (cc == 0 ? 0 : 1)) * plane, (unsigned)plane);
+  const unsigned ctx_bytes = (unsigned)p.H * all_frags(NDT) * FRAG;
+  const __amdgpu_buffer_rsrc_t kv_srd = make_srd(p.packed + ((size_t)img * (p.K + 2) + cc) * ctx_bytes, ctx_bytes);
+
+  // key weights of this item's readouts in the softmax's register order; rows beyond nr and keys >= M weigh nothing
+  // (loads are unconditional on a clamped address, the predicate is applied to the value)
+  float wr[MAPS_RB][NKT][4];
+#pragma unroll
+  for (int j = 0; j < MAPS_RB; ++j) {
+    const float* row = p.w + ((size_t)img * R + ((rdp >> (8 * j)) & 255u)) * M;
+#pragma unroll
+    for (int t = 0; t < NKT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = 16 * t + 4 * g + r;
+        const float x = row[min(key, M - 1)];
+        wr[j][t][r] = (j < nr && key < M) ? x : 0.f;
+      }
+  }
+
+  // pixels >= N and head-dim offsets >= d are pushed out of the descriptor's range -> read as 0
+  const unsigned qbase = px < N ? (unsigned)px * row_bytes + (unsigned)(8 * g) * (unsigned)sizeof(T) : 0xfffffff0u;
+  float acc[MAPS_RB];
+#pragma unroll
+  for (int j = 0; j < MAPS_RB; ++j) acc[j] = 0.f;
+  for (int h = 0; h < p.H; ++h) {
+    V8 qf[NKS], ka[NKF];
+    const unsigned qoff = (unsigned)(h * d) * (unsigned)sizeof(T);
+    const unsigned koff = (unsigned)h * all_frags(NDT) * FRAG;
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) qf[s] = srd_load16<V8>(q_srd, (32 * s + 8 * g < d) ? qbase : 0xfffffff0u, qoff + 64u * s);
+#pragma unroll
+    for (int f = 0; f < NKF; ++f) ka[f] = srd_load16<V8>(kv_srd, lane * 16, koff + f * FRAG);
+    f32x4 st[NKT];
+#pragma unroll
+    for (int t = 0; t < NKT; ++t) {
+      st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < NKS; ++s) st[t] = Tr<T>::mfma(ka[t * NKS + s], qf[s], st[t]);
+    }
+    const float inv = softmax_keys_fast(st, g, M, p.sl2e);
+#pragma unroll
+    for (int j = 0; j < MAPS_RB; ++j) {
+      float s4[NKT];
+#pragma unroll
+      for (int t = 0; t < NKT; ++t)
+        s4[t] = (wr[j][t][0] * st[t][0] + wr[j][t][1] * st[t][1]) + (wr[j][t][2] * st[t][2] + wr[j][t][3] * st[t][3]);
+      acc[j] += (((s4[0] + s4[1]) + (s4[2] + s4[3])) + s4[4]) * inv;
+    }
+  }
+
+#pragma unroll
+  for (int j = 0; j < MAPS_RB; ++j) {
+    // the product and the sum are rounded separately: accumulate = 1 is exactly old + what accumulate = 0 writes
+    const float fresh = __fmul_rn(bfly_sum(acc[j]), p.inv_heads);
+    if (j < nr && g == 0 && px < N) {
+      float* o = p.out + ((size_t)img * R + ((rdp >> (8 * j)) & 255u)) * N + px;
+      *o = p.accumulate ? __fadd_rn(*o, fresh) : fresh;
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------------
 }  // namespace
@@ -773,6 +882,58 @@ int sta_xattn_fwd(const void* q, const void* packed, const uint8_t* mask, const 
   p.aux = maps; p.N = N; p.C = C; p.H = heads; p.d = C / heads; p.M = M; p.K = K; p.n_img = n_img;
   p.scale = scale; p.sl2e = scale * 1.4426950408889634f;
   return sta_by_dtype(dtype, [&](auto tag) { return dispatch_fwd<decltype(tag)>(p, (hipStream_t)stream); });
+}
+
+int sta_xattn_token_maps(const void* q, const void* packed, const int32_t* sel_ctx, const float* w, float* out, int n_img,
+                         int N, int C, int heads, int M, int K, int R, float scale, int accumulate, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!q || !packed || !sel_ctx || !w || !out) return sta_fail(STA_E_ARG, "null pointer");
+  if ((((uintptr_t)q | (uintptr_t)packed) & 15) || (((uintptr_t)w | (uintptr_t)out) & 3))
+    return sta_fail(STA_E_ARG, "misaligned pointer (q, packed: 16 bytes; w, out: 4 bytes)");
+  if (n_img < 1 || n_img > 65535) return sta_fail(STA_E_ARG, "n_img=%d", n_img);
+  if (int rc = check_shape(N, C, heads, M, K)) return rc;
+  if (R < 1 || R > STA_MAX_READOUTS) return sta_fail(STA_E_ARG, "R=%d readouts (1..%d)", R, STA_MAX_READOUTS);
+  for (int r = 0; r < R; ++r)
+    if (sel_ctx[r] < 0 || sel_ctx[r] >= K + 2) return sta_fail(STA_E_ARG, "sel_ctx[%d]=%d names no context (K+2=%d)", r, (int)sel_ctx[r], K + 2);
+  if (accumulate != 0 && accumulate != 1) return sta_fail(STA_E_ARG, "accumulate=%d", accumulate);
+  const int d = C / heads, ndt = (d + 15) / 16;
+  // what one buffer descriptor of the kernel spans: a [N][C] plane of q, the fragments of one context
+  if ((size_t)N * C * 2 >= (1ull << 32) || (size_t)heads * all_frags(ndt) * FRAG >= (1ull << 32))
+    return sta_fail(STA_E_UNSUP, "N=%d C=%d heads=%d beyond a 4 GiB buffer range", N, C, heads);
+  MapParams p{};
+  p.q = q; p.packed = (const char*)packed; p.w = w; p.out = out;
+  p.N = N; p.C = C; p.H = heads; p.d = d; p.M = M; p.K = K; p.R = R; p.accumulate = accumulate;
+  p.sl2e = scale * 1.4426950408889634f; p.inv_heads = 1.0f / (float)heads;
+  // work items in context order: a context's readouts in groups of MAPS_RB
+  for (int c = 0; c < K + 2; ++c) {
+    int cur = -1;
+    for (int r = 0; r < R; ++r) {
+      if (sel_ctx[r] != c) continue;
+      if (cur < 0 || p.wk.nr[cur] == MAPS_RB) { cur = p.wk.n++; p.wk.ctx[cur] = c; }
+      p.wk.rd[cur] |= (unsigned)r << (8 * p.wk.nr[cur]++);
+    }
+  }
+  const long tiles = ((long)N + 15) / 16;
+  if (tiles * p.wk.n > 0x7fffffffL) return sta_fail(STA_E_UNSUP, "N=%d: too many pixel tiles for one launch", N);
+  const dim3 grid((unsigned)(tiles * p.wk.n), n_img);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const char* const what = "token maps launch";
+    const hipStream_t st = (hipStream_t)stream;
+    switch (ndt) {
+      case 1: return sta_launch<xattn_token_maps_kernel<T, 1>>(what, grid, dim3(64), 0, st, p);
+      case 2: return sta_launch<xattn_token_maps_kernel<T, 2>>(what, grid, dim3(64), 0, st, p);
+      case 3: return sta_launch<xattn_token_maps_kernel<T, 3>>(what, grid, dim3(64), 0, st, p);
+      case 4: return sta_launch<xattn_token_maps_kernel<T, 4>>(what, grid, dim3(64), 0, st, p);
+      case 5: return sta_launch<xattn_token_maps_kernel<T, 5>>(what, grid, dim3(64), 0, st, p);
+      case 6: return sta_launch<xattn_token_maps_kernel<T, 6>>(what, grid, dim3(64), 0, st, p);
+      case 7: return sta_launch<xattn_token_maps_kernel<T, 7>>(what, grid, dim3(64), 0, st, p);
+      case 8: return sta_launch<xattn_token_maps_kernel<T, 8>>(what, grid, dim3(64), 0, st, p);
+      case 9: return sta_launch<xattn_token_maps_kernel<T, 9>>(what, grid, dim3(64), 0, st, p);
+      case 10: return sta_launch<xattn_token_maps_kernel<T, 10>>(what, grid, dim3(64), 0, st, p);
+    }
+    return sta_fail(STA_E_UNSUP, "head dim %d unsupported", d);
+  });
 }
 
 

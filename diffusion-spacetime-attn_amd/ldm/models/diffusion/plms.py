@@ -17,6 +17,7 @@ MI355X-specific: with `opt_epochs=0` (fixed weights; BASELINE config 2) the whol
 captured once into a hipGraph and replayed for the 51 calls of a trajectory (sta.graphs).
 """
 import collections
+import contextlib
 import math
 import os
 
@@ -193,8 +194,11 @@ class _CallRecompute(torch.autograd.Function):
 class PLMSSampler(object):
     def __init__(self, model, schedule="linear", loss_model=None, opt_epochs=3, lr=0.005, weight_init=5.0,
                  local_loss_weight=5.0, use_graph=True, save_images=True, outdir="result_outputs/", loss_scale=None, keep_calls=None,
-                 batched_loss=True, **kwargs):
-        """`loss_scale`: the fidelity loss is multiplied by it before backward and W.grad divided by it before the Adam step.
+                 batched_loss=True, attn_capture=None, **kwargs):
+        """`attn_capture`: a sta.attnmaps.AttnCapture. The trajectory whose image is kept (the last epoch's, never tracked) then runs
+        eagerly — no hipGraph replay — with the capture attached, and its AttnResult is left in `last_attn`; earlier (tracked) epochs
+        record nothing. None: nothing changes.
+        `loss_scale`: the fidelity loss is multiplied by it before backward and W.grad divided by it before the Adam step.
         None = 1 for bf16 / fp32 models; for an fp16 model the power of two that brings the scaled loss to [2^15, 2^16)
         (2^12 for the synthetic CLIP stand-in's loss of ~11; the same gradients whatever the loss model's own scale is:
         tests/test_modules_gpu.py::test_fp16_small_gradients_survive_with_loss_scaling drives a loss 2^-16 of that one), and
@@ -214,6 +218,7 @@ class PLMSSampler(object):
         self.opt_epochs, self.lr, self.weight_init, self.local_loss_weight = opt_epochs, lr, weight_init, local_loss_weight
         self.use_graph, self.save_images, self.outdir = use_graph, save_images, outdir
         self.last_result = None
+        self.attn_capture, self.last_attn = attn_capture, None
         self._graphs = None
         self._call_key = None             # (latent shape, object count) of the trajectory being sampled: keys the measured activation size
 
@@ -323,14 +328,17 @@ class PLMSSampler(object):
             track = W.requires_grad and not last
             scale_backoff = 1.0
             by_call = track and getattr(self.model, "sta_call_recompute", False)
+            cap = self.attn_capture if last else None
+            if cap is not None:
+                cap.begin(boxes, texts=texts, names=names)
             while True:
                 # tracked epochs: eager autograd through the 51 calls, or (sta.pipeline.set_recompute mode "call") the
                 # fixed-weight forward per call + one re-run of the call under autograd in backward, with the glue passes of
                 # the trunk as autograd Functions over the HIP kernels (sta.fused.tracked)
-                with torch.set_grad_enabled(track), _fused.tracked(by_call):
+                with torch.set_grad_enabled(track), _fused.tracked(by_call), (cap if cap is not None else contextlib.nullcontext()):
                     img = self._trajectory(img_input.clone(), cond, unconditional_conditioning, unconditional_guidance_scale,
                                            time_range, W if batched else W[0], block_boxes, text_index,
-                                           graph=self.use_graph and (not track or by_call), call_recompute=by_call)
+                                           graph=self.use_graph and (not track or by_call) and cap is None, call_recompute=by_call)
                     x_img = None
                     if self.model.first_stage_model is not None and self._paste() is not None:
                         # inpainting with a pixel-space pair: the result (and what the loss sees) is the original outside the mask
@@ -362,6 +370,8 @@ class PLMSSampler(object):
             if last:
                 result.update(x0=img.detach(), image=None if x_img is None else x_img.detach(),
                               W=(W if batched else W[0]).detach().clone())
+                if cap is not None:
+                    self.last_attn = cap.result()
                 if self.save_images and x_img is not None:
                     for i in range(b):
                         self._save(x_img[i], epochs - 1, seed, pidx[i], index=i)

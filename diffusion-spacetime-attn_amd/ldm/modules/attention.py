@@ -228,6 +228,7 @@ class BasicTransformerBlock(nn.Module):
         self._last_n = None
         self.keep_maps = False       # parity hook: keep the kernel's [K+2, heads, N, 77] attention maps of the last call
         self.last_maps = None
+        self._attn_capture = None    # sta.attnmaps.AttnCapture while one is attached: token maps of this block's calls
 
     # -- per-prompt state (reference: the `time == 981` branch, attention.py:240-263) ---------------
     def _stale(self, cache, centres, time):
@@ -309,6 +310,9 @@ class BasicTransformerBlock(nn.Module):
 
     def _forward(self, x, coef, cache, in_bias=None):
         c = coef if coef.numel() else None
+        cap = self._attn_capture                     # None unless an AttnCapture is attached (the one test an ordinary call pays)
+        if cap is not None and not cap.wants(x.shape[1]):
+            cap = None
         if _fused.usable(x):
             # inference: every residual add runs inside the LayerNorm pass that consumes it (sta_add_layernorm)
             n1, n2, n3 = self.norm1, self.norm2, self.norm3
@@ -323,7 +327,7 @@ class BasicTransformerBlock(nn.Module):
             else:
                 s, y = _fused.add_layernorm(x, None, in_bias, n1.weight, n1.bias, n1.eps, store_sum=in_bias is not None)
             x = x if s is None else s
-            fused_q = cache.packed_proj is not None and not self.keep_maps
+            fused_q = cache.packed_proj is not None and not self.keep_maps and cap is None      # a capturing block needs q in HBM
             # the GEGLU projection of the feed-forward as one pass over norm3's output in query-fragment order (csrc/sta_ffgemm.hip)
             # (oversize batches — the [rows, inner] GEGLU output beyond what a launch addresses — take the row-major path)
             ffq = self._ff_fusable(x) and _fused.rowgemm_worthwhile(x, self.ff.net[0].proj.out_features // 2)
@@ -355,6 +359,8 @@ class BasicTransformerBlock(nn.Module):
             else:
                 q = self.attn2.to_q(y)
                 self._keep_maps(q, c, cache)
+                if cap is not None:
+                    cap.record(self, q, cache)
                 blended = _ops.xattn_blend(q, c, cache.packed, cache.mask, self.attn2.scale)
             x, y = _fused.add_layernorm(x, self.attn2.to_out(blended), None, n3.weight, n3.bias, n3.eps, qfrag=ffq)
             return self._ff_tail(x, y, ffq)
@@ -366,6 +372,8 @@ class BasicTransformerBlock(nn.Module):
             x, y = _fused.add_layernorm_tracked(x, self.attn1(y), None, n2.weight, n2.bias, n2.eps)
             q = self.attn2.to_q(y)
             self._keep_maps(q, c, cache)
+            if cap is not None:
+                cap.record(self, q, cache)
             blended = _ops.xattn_blend(q, c, cache.packed, cache.mask, self.attn2.scale)
             x, y = _fused.add_layernorm_tracked(x, self.attn2.to_out(blended), None, n3.weight, n3.bias, n3.eps)
             return self.ff(y) + x
@@ -374,6 +382,8 @@ class BasicTransformerBlock(nn.Module):
         x = self.attn1(self.norm1(x)) + x
         q = self.attn2.to_q(self.norm2(x))
         self._keep_maps(q, c, cache)
+        if cap is not None:
+            cap.record(self, q, cache)
         blended = _ops.xattn_blend(q, c, cache.packed, cache.mask, self.attn2.scale)
         x = self.attn2.to_out(blended) + x
         return self.ff(self.norm3(x)) + x

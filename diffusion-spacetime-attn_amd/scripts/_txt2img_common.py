@@ -75,7 +75,28 @@ def build_parser(default_dataset):
     p.add_argument("--synthetic", action="store_true", help="synthetic weights/text embeddings when no checkpoint is available")
     p.add_argument("--batch_prompts", type=int, default=1,
                    help="sample up to this many prompts with the same object count together (one CFG batch of 2I per UNet call)")
+    p.add_argument("--attn_maps", action="store_true",
+                   help="capture per-object cross-attention heat maps over the kept trajectory (sta.attnmaps; that trajectory runs without "
+                        "graph replay): <outdir>/attn/<prompt index>.npz, one PNG overlay per object, and the in-disc mass per object")
+    p.add_argument("--attn_res", type=int, choices=[8, 16, 32, 64], default=16,
+                   help="side of the transformer level whose blocks are captured (16 = the C = 1280 level of a 512 x 512 image)")
     return p
+
+
+def attn_levels(opt):
+    """Sides of the UNet's four transformer levels for the latent of --H / --W."""
+    return [opt.H // opt.f // s for s in (1, 2, 4, 8)]
+
+
+def check_attn_option(opt):
+    """--attn_maps: refusals that need no GPU."""
+    if not opt.attn_maps:
+        return
+    if opt.H != opt.W or opt.H % (8 * opt.f):
+        raise SystemExit("--attn_maps needs a square image whose latent side is a multiple of 8 (got %d x %d, --f %d)" % (opt.H, opt.W, opt.f))
+    if opt.attn_res not in attn_levels(opt):
+        raise SystemExit("--attn_res %d: no transformer level of a %d x %d image has that side (levels: %s)"
+                         % (opt.attn_res, opt.H, opt.W, ", ".join(str(v) for v in attn_levels(opt))))
 
 
 def builtin_clip(opt):
@@ -132,6 +153,7 @@ def check_options(opt):
     if opt.mxfp8 and opt.opt_epochs > 0:
         raise SystemExit("--mxfp8 is an inference option: use --opt_epochs 0")
     check_clip_option(opt, (opt.H, opt.W))
+    check_attn_option(opt)
 
 
 def sampler_choice(opt):
@@ -209,13 +231,30 @@ def run(kind, default_dataset):
         from sta import mxfp8
         n, before, after = mxfp8.convert_transformer_linears_mx_(model.model.diffusion_model)
         print("[rank %d] %d Linear layers -> MXFP8: %.2f GB -> %.2f GB" % (rank, n, before / 1e9, after / 1e9))
-    sampler = sampler_class(sampler_name)(model, opt_epochs=opt.opt_epochs, loss_model=loss_model)
+    capture = None
+    if opt.attn_maps:
+        from sta import attnmaps
+        # name tokens are located with the text encoder's own tokenizer; the synthetic embedder has none (whitespace stand-in)
+        tok = getattr(model.cond_stage_model, "tokenizer", None)
+        capture = attnmaps.AttnCapture(model.model.diffusion_model, resolution=opt.attn_res,
+                                       tokenize=None if tok is None else attnmaps.content_tokenizer(tok))
+    sampler = sampler_class(sampler_name)(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, attn_capture=capture)
     os.makedirs(opt.outdir, exist_ok=True)
 
     seed = 1                                                            # txt2img-gpt.py:304
     shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
     todo = list(enumerate(prompts))[opt.start: opt.start + 500]
     mine = [todo[j] for j in parallel.shard_indices(len(todo), rank, world)]
+
+    def report_attn(group):
+        """--attn_maps: files and the in-disc mass of every object of the prompts just sampled (prompts without objects have no readouts)."""
+        if capture is None or sampler.last_attn is None:
+            return
+        image = sampler.last_result.get("image")
+        for j, (i, _, l) in enumerate(group):
+            for line in attnmaps.save_result(opt.outdir, i, list(l.keys()), [l[n] for n in l], sampler.last_attn,
+                                             None if image is None else image[j], index=j):
+                print("[rank %d] %s" % (rank, line))
 
     def run_one(prompt_idx, prompt, layout):
         torch.manual_seed(seed)                                         # seed_everything(seed), :306
@@ -227,6 +266,7 @@ def run(kind, default_dataset):
                        unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, eta=eta, x_T=x_T,
                        text_index=0, curr_text=prompt, bboxs_curr=[layout[n] for n in names], seed=seed,
                        prompt_idx=prompt_idx, object_names=names, local_conditionings=local_c)
+        report_attn([(prompt_idx, prompt, layout)])
 
     def run_group(group):
         """Prompts with the same number of objects share one CFG batch; every image keeps the reference's
@@ -241,6 +281,7 @@ def run(kind, default_dataset):
                              local_conditionings=[c[2] for c in conds], curr_texts=[p for _, p, _ in group],
                              x_T=x1.expand(len(group), -1, -1, -1), unconditional_guidance_scale=opt.scale, eta=eta,
                              seed=seed, prompt_indices=[i for i, _, _ in group])
+        report_attn(group)
 
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}) for i, p in mine]
     if opt.batch_prompts <= 1:

@@ -36,6 +36,7 @@ OPT_FWD_KERNEL, OPT_STAGED_TILES, OPT_STAGED_WAVES, OPT_STAGED_QT, OPT_HEAD_MAJO
 FWD_STAGED, FWD_SPLIT = 1, 2
 MAX_KEYS, MAX_HEAD_DIM, MAX_OBJECTS = 80, 160, 8
 P3_STATS_WORDS = 8
+MAX_READOUTS = 16
 
 # every symbol include/sta_xattn.h and include/sta_unet.h declare: (restype, argtypes)
 _vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
@@ -47,6 +48,7 @@ SYMBOLS = {
     "sta_xattn_packed_kv_bytes": (_sz, [_i, _i, _i]),
     "sta_xattn_pack_kv": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sta_xattn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "sta_xattn_token_maps": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
     "sta_xattn_fwd_proj_supported": (_i, [_i, _i, _i, _i]),
     "sta_xattn_fwd_proj_locals_from_l2": (_i, [_i, _i, _i, _i]),
     "sta_xattn_packed_wq_bytes": (_sz, [_i, _i]),

@@ -236,6 +236,28 @@ int sta_to_out_ln_ofrag(const void* blended_ofrag, const void* packed_wo, const 
 int sta_selfattn_fwd_sfrag(const void* q, const void* k, const void* vt, void* out_frag, int B, int N, int C, int heads,
                            int ldq, int ldk, long vt_row_stride, long vt_batch_stride, float scale, int dtype, void* stream);
 
+/*
+ * Token maps: WHERE the pixels attend, reduced to what a diagnostic needs. `attn` (attention.py:194) is a local of the
+ * reference's forward; the `maps` output of sta_xattn_fwd writes it out in full ([K+2][heads][N][M] fp32 per image). This
+ * entry point keeps R weighted key sums per pixel instead — readout r names a context c_r = sel_ctx[r] and a weight row:
+ *   out[i][r][p] = (accumulate ? out[i][r][p] : 0)
+ *                  + (1 / heads) sum_h sum_{m < M} w[i][r][m] softmax_m(scale q_h[p] . K_{i, c_r, h}[m])
+ * with q row 0 for context 0 and q row 1 for every other context, as the forward attends them. The disc mask plays no
+ * part (the map covers every pixel) and several readouts may name one context. One launch, no workspace, no atomics:
+ * every element of `out` has one writer and one summation order, so results are bit-reproducible, independent of n_img,
+ * and accumulate = 1 gives exactly old + what accumulate = 0 writes.
+ *   q       : [n_img][2][N][C] dtype, 16-byte aligned
+ *   packed  : image from sta_xattn_pack_kv for n_ctx = n_img * (K + 2) (image-major)
+ *   sel_ctx : [R] int32 in HOST memory, read before the call returns; 0 <= sel_ctx[r] < K + 2
+ *   w       : [n_img][R][M] fp32 device
+ *   out     : [n_img][R][N] fp32 device
+ * Shapes as sta_xattn_fwd; 1 <= R <= STA_MAX_READOUTS; accumulate is 0 or 1.
+ */
+#define STA_MAX_READOUTS 16
+int sta_xattn_token_maps(const void* q, const void* packed, const int32_t* sel_ctx, const float* w, float* out,
+                         int n_img, int N, int C, int heads, int M, int K, int R, float scale, int accumulate,
+                         int dtype, void* stream);
+
 /* Bytes of fp32 workspace sta_xattn_bwd needs for the given shape (deterministic dcoef reduce). */
 size_t sta_xattn_bwd_workspace_bytes(int n_img, int N, int heads, int K);
 
