@@ -34,6 +34,7 @@
 #include "sta_unet.h"
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
+#include "sta_wring_dev.h"
 
 namespace {
 
@@ -43,8 +44,7 @@ constexpr int CV_NW = 8;
 constexpr int cv_part(int ntw) { return 32 * ntw; }                       // output channels per workgroup
 constexpr int cv_nt(int ntw) { return 2 * ntw; }                          // row tiles per part
 constexpr int cv_wfr(int ntw) { return 3 * cv_nt(ntw); }                  // 30 / 24 weight fragments per step (one kernel row)
-constexpr int cv_wper(int ntw) { return (cv_wfr(ntw) + CV_NW - 1) / CV_NW; }   // 4 / 3 weight DMAs per wave per step
-constexpr int cv_wslot(int ntw) { return cv_wper(ntw) * CV_NW * FRAG; }   // 32 / 24 KiB
+template <int NTW> using CvRing = WRing<CV_NW, cv_wfr(NTW)>;              // 4 / 3 weight DMAs per wave per step, 32 / 24 KiB per slot
 // Tile geometries. GEO 0: 8 rows x 32 columns; GEO 1: 16 x 16 (16-pixel-wide images): 256 pixels, four 16-pixel segments per wave.
 // GEO 2: TWO whole 8 x 8 images (the UNet's lowest level): 128 pixels, two segments (four image rows) per wave — at 64 images x 1280
 // channels that is 256 work items, one per CU, where 256-pixel tiles would leave half of the chip idle. The halo tile is stored at a
@@ -57,7 +57,7 @@ constexpr int cv_npx(int geo) { return geo == 2 ? 2 * 10 * 16 : (cv_tr(geo) + 2)
 constexpr int cv_nq(int geo) { return geo == 2 ? 2 : 4; }
 constexpr int cv_xpw(int geo) { return (cv_npx(geo) + 16 * CV_NW - 1) / (16 * CV_NW); }                   // 3
 constexpr int cv_xbuf(int geo) { return cv_xpw(geo) * CV_NW * FRAG; }                                      // 24 KiB
-constexpr int cv_lds(int ntw, int geo) { return 2 * cv_wslot(ntw) + 2 * cv_xbuf(geo); }                    // 112 / 96 KiB
+template <int NTW, int GEO> constexpr int cv_lds = 2 * CvRing<NTW>::SLOT + 2 * cv_xbuf(GEO);              // 112 / 96 KiB
 #ifndef CV_STAGE_AFTER_TAP
 #define CV_STAGE_AFTER_TAP 0                  // the next step's DMA is issued behind the MFMAs of this tap (not right behind the barrier,
 #endif                                        // where every wave of the workgroup would pay the issue cost with the matrix pipe idle)
@@ -103,7 +103,7 @@ template <typename T, int GEO, int NTW>
 __global__ __launch_bounds__(64 * CV_NW, 1) void conv3x3_nhwc_kernel(const CV p) {
   using V8 = typename Tr<T>::V8;
   using V4 = typename Tr<T>::V4;
-  constexpr int CV_PART = cv_part(NTW), CV_NT = cv_nt(NTW), CV_WFR = cv_wfr(NTW), CV_WPER = cv_wper(NTW), CV_WSLOT = cv_wslot(NTW);
+  constexpr int CV_PART = cv_part(NTW), CV_NT = cv_nt(NTW), CV_WFR = cv_wfr(NTW), CV_WSLOT = CvRing<NTW>::SLOT;
   // halo tile: (TR + 2) rows of TC + 2 pixels at a pitch that is a multiple of 4: the chunk swizzle ((pixel index >> 2) & 1) << 1 of pixel
   // (row, xx) is then ((row * (PITCH / 4) + (xx >> 2)) & 1) << 1 — separable in row and column, so a lane needs 12 operand addresses
   // instead of 36 (PITCH / 4 odd: bit 5 of the address flips on odd kernel rows; even: it does not depend on the row at all)
@@ -158,14 +158,7 @@ __global__ __launch_bounds__(64 * CV_NW, 1) void conv3x3_nhwc_kernel(const CV p)
     return ok ? p.x + px * (size_t)p.Cin * sizeof(T) + chunk * 16 : p.zeros + chunk * 16;
   };
   auto stage_w = [&](int part, int kc, int ky, int slot) __attribute__((always_inline)) {
-    const unsigned base = (unsigned)(((part * nkc + kc) * 3 + ky) * CV_WFR) * (unsigned)FRAG;
-#pragma unroll
-    for (int i = 0; i < CV_WPER; ++i) {
-      const int f = wv + CV_NW * i;
-      const int fs = f < CV_WFR ? f : 0;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_srd, (__attribute__((address_space(3))) void*)(wring + slot * CV_WSLOT + f * FRAG), 16, lane16,
-                                               base + (unsigned)fs * (unsigned)FRAG, 0, 0);
-    }
+    CvRing<NTW>::stage(w_srd, wring + slot * CV_WSLOT, (unsigned)(((part * nkc + kc) * 3 + ky) * CV_WFR) * (unsigned)FRAG, 0, wv, lane16);
   };
   auto stage_x = [&](const char* src, int pc, int buf) __attribute__((always_inline)) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -320,14 +313,14 @@ __global__ __launch_bounds__(64 * CV_NW, 1) void conv3x3_nhwc_kernel(const CV p)
         if (p.res) {
 #pragma unroll
           for (int t = 0; t < NTW; ++t)
-            rv[t] = __builtin_bit_cast(V4, __builtin_amdgcn_raw_buffer_load_b64(r_srd, img_ok ? base + (unsigned)(16 * t * sizeof(T)) : 0xfffffff0u, 0, 0));
+            rv[t] = __builtin_bit_cast(V4, __builtin_amdgcn_raw_buffer_load_b64(r_srd, img_ok ? base + (unsigned)(16 * t * sizeof(T)) : SRD_DROP, 0, 0));
         }
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
           V4 o;
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[r] = (T)(acc[q][t][r] + bs[t][r] + (p.res ? (float)rv[t][r] : 0.f));
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), o_srd, img_ok ? base + (unsigned)(16 * t * sizeof(T)) : 0xfffffff0u, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), o_srd, img_ok ? base + (unsigned)(16 * t * sizeof(T)) : SRD_DROP, 0, 0);
           if (p.stats) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -373,7 +366,7 @@ int conv_geo(int H, int W) {                  // tile geometry of an H x W image
 
 template <typename T, int GEO, int NTW>
 int conv_launch(const CV& p, unsigned grid, hipStream_t st) {
-  return sta_launch_lds<conv3x3_nhwc_kernel<T, GEO, NTW>>("conv3x3_nhwc launch", cv_lds(NTW, GEO), dim3(grid), dim3(64 * CV_NW), cv_lds(NTW, GEO), st, p);
+  return sta_launch_lds<conv3x3_nhwc_kernel<T, GEO, NTW>>("conv3x3_nhwc launch", cv_lds<NTW, GEO>, dim3(grid), dim3(64 * CV_NW), cv_lds<NTW, GEO>, st, p);
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 #include "sta_unet.h"
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
+#include "sta_wring_dev.h"
 
 namespace {
 
@@ -31,8 +32,8 @@ constexpr int FF_NKS = FF_C / 32;              // 10 k-steps
 constexpr int FF_NSC = FF_INNER / 32;          // 40 sub-chunks (one pair of value tiles + its pair of gate tiles each)
 constexpr int FF_SC_FR = 4 * FF_NKS;           // 40 fragments per sub-chunk
 constexpr int FF_NW = 8;
-constexpr int FF_PER = FF_SC_FR / FF_NW;       // 5 LDS-DMA instructions per wave per sub-chunk
-constexpr int FF_SLOT = FF_SC_FR * FRAG;       // 40 KiB
+using FfRing = WRing<FF_NW, FF_SC_FR>;         // 5 LDS-DMA instructions per wave per sub-chunk, 40 KiB per slot
+constexpr int FF_SLOT = FfRing::SLOT;
 constexpr int FF_TAB = 2 * FF_INNER * 2;       // bias (value | gate) as 16-bit behind the ring
 constexpr int FF_LDS = 2 * FF_SLOT + FF_TAB;
 
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(64) void pack_w1_kernel(const T* __restrict__ w, T*
   const int fr = blockIdx.x;                   // ((v * 2 + part) * 2 + t) * NKS + f
   const int f = fr % FF_NKS, t = (fr / FF_NKS) & 1, part = (fr / (2 * FF_NKS)) & 1, v = fr / (4 * FF_NKS);
   const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
-  const int row = part * FF_INNER + 32 * v + 8 * (c >> 2) + 4 * t + (c & 3);
+  const int row = part * FF_INNER + 32 * v + 8 * (c >> 2) + 4 * t + (c & 3);     // part * inner + frag_sigma(2 v + t, c), spelled out
   const typename Tr<T>::V8 x = *(const typename Tr<T>::V8*)(w + (size_t)row * FF_C + 32 * f + 8 * g);
   *(typename Tr<T>::V8*)(packed + (size_t)fr * (FRAG / 2) + lane * 8) = x;
 }
@@ -84,9 +85,11 @@ __global__ __launch_bounds__(64 * FF_NW, 2) void ff_geglu_qfrag_kernel(const FF 
   __syncthreads();
   const __amdgpu_buffer_rsrc_t w_srd = make_srd(p.w, (unsigned)(FF_NSC * FF_SC_FR * FRAG));
   const unsigned lane16 = (unsigned)lane * 16u;
+  // FfRing::stage spelled out: 8 waves x 5 copies are the 40 fragments exactly, and this loop has never carried the clamp of the
+  // spare positions (five scalar selects per sub-chunk that the shared loop would add here)
   auto stage = [&](int sc, int slot) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < FF_PER; ++i) {
+    for (int i = 0; i < FfRing::PER; ++i) {
       const int f = wv + FF_NW * i;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(w_srd, (__attribute__((address_space(3))) void*)(ring + slot * FF_SLOT + f * FRAG), 16, lane16,
                                                (unsigned)((sc * FF_SC_FR + f) * FRAG), 0, 0);
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(64 * FF_NW, 2) void ff_geglu_qfrag_kernel(const FF 
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
       const long r0 = row0 + 16 * it;
-      const unsigned vo = r0 < p.R ? (unsigned)(r0 * FF_C * (long)sizeof(T)) + lane16 : 0xfffffff0u;
+      const unsigned vo = r0 < p.R ? (unsigned)(r0 * FF_C * (long)sizeof(T)) + lane16 : SRD_DROP;
 #pragma unroll
       for (int f = 0; f < FF_NKS; ++f) b[it][f] = srd_load16<V8>(y_srd, vo, 1024u * f);
     }
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(64 * FF_NW, 2) void ff_geglu_qfrag_kernel(const FF 
         }
         // ALWAYS two stores per sub-chunk (rows past R: an offset the descriptor drops): the counted vmcnt above relies on it.
         // Fragment order: the lane's 8 channels ARE lane 16 g + c of fragment `sc` of the item's group — one contiguous KiB per store
-        const unsigned ho = row0 + 16 * it >= p.R ? 0xfffffff0u
+        const unsigned ho = row0 + 16 * it >= p.R ? SRD_DROP
                           : p.h_frag ? (unsigned)((row0 + 16 * it) * FF_INNER * (long)sizeof(T)) + (unsigned)sc * (unsigned)FRAG + lane16
                                      : (unsigned)(row * FF_INNER * (long)sizeof(T)) + (unsigned)(32 * sc + 8 * g) * (unsigned)sizeof(T);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), h_srd, ho, 0, 0);
@@ -175,8 +178,8 @@ constexpr int F2_NKC = FF_INNER / FF_C;        // 4 k-chunks of 320
 constexpr int F2_NRT = FF_C / 16;              // 20 output row tiles
 constexpr int F2_NCH = F2_NRT / 2;             // 10 weight chunks (two row tiles) per k-chunk
 constexpr int F2_CH_FR = 2 * FF_NKS;           // 20 fragments per chunk
-constexpr int F2_PER = (F2_CH_FR + FF_NW - 1) / FF_NW;     // 3 (4 padding copies)
-constexpr int F2_SLOT = F2_PER * FF_NW * FRAG; // 24 KiB
+using F2Ring = WRing<FF_NW, F2_CH_FR>;         // 3 LDS-DMA instructions per wave per chunk (4 padding copies), 24 KiB per slot
+constexpr int F2_SLOT = F2Ring::SLOT;
 constexpr int F2_LDS = 2 * F2_SLOT + FF_C * 2;
 
 // net[2].weight [C][inner] -> [k-chunk kc][chunk v][t][k-step f] fragments: lane (g, c) holds
@@ -186,7 +189,7 @@ __global__ __launch_bounds__(64) void pack_w2_kernel(const T* __restrict__ w, T*
   const int fr = blockIdx.x;                   // ((kc * NCH + v) * 2 + t) * NKS + f
   const int f = fr % FF_NKS, t = (fr / FF_NKS) & 1, v = (fr / (2 * FF_NKS)) % F2_NCH, kc = fr / (2 * FF_NKS * F2_NCH);
   const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
-  const int row = 32 * v + 8 * (c >> 2) + 4 * t + (c & 3);
+  const int row = 32 * v + 8 * (c >> 2) + 4 * t + (c & 3);     // frag_sigma(2 v + t, c), spelled out
   const typename Tr<T>::V8 x = *(const typename Tr<T>::V8*)(w + (size_t)row * FF_INNER + FF_C * kc + 32 * f + 8 * g);
   *(typename Tr<T>::V8*)(packed + (size_t)fr * (FRAG / 2) + lane * 8) = x;
 }
@@ -212,19 +215,13 @@ __global__ __launch_bounds__(64 * FF_NW, 2) void ff_out_res_hfrag_kernel(const F
   const __amdgpu_buffer_rsrc_t w_srd = make_srd(p.w, (unsigned)(F2_NKC * F2_NCH * F2_CH_FR * FRAG));
   const unsigned lane16 = (unsigned)lane * 16u;
   auto stage = [&](int chunk, int slot) __attribute__((always_inline)) {      // chunk = kc * NCH + ch, 0 .. 39
-#pragma unroll
-    for (int i = 0; i < F2_PER; ++i) {
-      const int f = wv + FF_NW * i;
-      const int fs = f < F2_CH_FR ? f : 0;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_srd, (__attribute__((address_space(3))) void*)(ring + slot * F2_SLOT + f * FRAG), 16, lane16,
-                                               (unsigned)((chunk * F2_CH_FR + fs) * FRAG), 0, 0);
-    }
+    F2Ring::stage(w_srd, ring + slot * F2_SLOT, 0u, chunk * F2_CH_FR, wv, lane16);
   };
   const __amdgpu_buffer_rsrc_t h_srd = make_srd(p.h, (unsigned)((size_t)p.R * FF_INNER * sizeof(T)));
   const long nblk = (p.R + 16 * FF_NW - 1) / (16 * FF_NW);
   auto h_off = [&](long blk) -> unsigned {
     const long row0 = (blk * FF_NW + wv) * 16;
-    return (blk < nblk && row0 < p.R) ? (unsigned)(row0 * FF_INNER * (long)sizeof(T)) + lane16 : 0xfffffff0u;
+    return (blk < nblk && row0 < p.R) ? (unsigned)(row0 * FF_INNER * (long)sizeof(T)) + lane16 : SRD_DROP;
   };
   long blk = blockIdx.x;
   V8 b[FF_NKS], bn[FF_NKS];
@@ -280,10 +277,7 @@ __global__ __launch_bounds__(64 * FF_NW, 2) void ff_out_res_hfrag_kernel(const F
         acc[2 * CH] = a0;
         acc[2 * CH + 1] = a1;
       };
-      chunk(std::integral_constant<int, 0>{}); chunk(std::integral_constant<int, 1>{}); chunk(std::integral_constant<int, 2>{});
-      chunk(std::integral_constant<int, 3>{}); chunk(std::integral_constant<int, 4>{}); chunk(std::integral_constant<int, 5>{});
-      chunk(std::integral_constant<int, 6>{}); chunk(std::integral_constant<int, 7>{}); chunk(std::integral_constant<int, 8>{});
-      chunk(std::integral_constant<int, 9>{});
+      sta_static_for<F2_NCH>(chunk);
 #pragma unroll
       for (int f = 0; f < FF_NKS; ++f) b[f] = bn[f];
     }
@@ -301,7 +295,7 @@ __global__ __launch_bounds__(64 * FF_NW, 2) void ff_out_res_hfrag_kernel(const F
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = (T)(acc[2 * v + (e >> 2)][e & 3] + (float)bs[e] + (float)xv[e]);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), o_srd,
-                                             ok ? (unsigned)(row * FF_C * (long)sizeof(T)) + (unsigned)(32 * v + 8 * g) * (unsigned)sizeof(T) : 0xfffffff0u, 0, 0);
+                                             ok ? (unsigned)(row * FF_C * (long)sizeof(T)) + (unsigned)(32 * v + 8 * g) * (unsigned)sizeof(T) : SRD_DROP, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
   }

@@ -20,6 +20,7 @@
 #include "sta_unet.h"
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
+#include "sta_wring_dev.h"
 
 namespace {
 
@@ -28,11 +29,10 @@ constexpr int GM_ROWS = 256;                                                // r
 constexpr int gm_part(int ntw) { return 32 * ntw; }
 constexpr int gm_nt(int ntw) { return 2 * ntw; }
 constexpr int gm_wfr(int ntw) { return 2 * gm_nt(ntw); }                    // 20 / 16 weight fragments per step (two k-chunks)
-constexpr int gm_wper(int ntw) { return (gm_wfr(ntw) + GM_NW - 1) / GM_NW; }     // 3 / 2
-constexpr int gm_wslot(int ntw) { return gm_wper(ntw) * GM_NW * FRAG; }     // 24 / 16 KiB
+template <int NTW> using GmRing = WRing<GM_NW, gm_wfr(NTW)>;                // 3 / 2 weight DMAs per wave per step, 24 / 16 KiB per slot
 constexpr int GM_XPER = 2 * (GM_ROWS / 16) / GM_NW;                         // 4 input pieces (16 rows x 32 channels) per wave per step
 constexpr int GM_XBUF = 2 * GM_ROWS * 64;                                   // 32 KiB: [k-chunk][row][64 B]
-constexpr int gm_lds(int ntw) { return 2 * gm_wslot(ntw) + 2 * GM_XBUF; }   // 112 / 96 KiB
+template <int NTW> constexpr int gm_lds = 2 * GmRing<NTW>::SLOT + 2 * GM_XBUF;    // 112 / 96 KiB
 
 // w[n][k] (element (n, k) at n * sn + k * sk) -> fragments [part][step][kci][tile t]: lane (g, c) holds W[16 nt part + 16 t + c][64 step + 32 kci + 8 g .. + 7]
 template <typename T>
@@ -75,7 +75,7 @@ template <typename T, int NTW>
 __global__ __launch_bounds__(64 * GM_NW, 1) void gemm_rows_kernel(const GM p) {
   using V8 = typename Tr<T>::V8;
   using V4 = typename Tr<T>::V4;
-  constexpr int PART = gm_part(NTW), NT = gm_nt(NTW), WFR = gm_wfr(NTW), WPER = gm_wper(NTW), WSLOT = gm_wslot(NTW);
+  constexpr int PART = gm_part(NTW), NT = gm_nt(NTW), WFR = gm_wfr(NTW), WSLOT = GmRing<NTW>::SLOT;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, c16 = lane & 15;
@@ -107,14 +107,7 @@ __global__ __launch_bounds__(64 * GM_NW, 1) void gemm_rows_kernel(const GM p) {
     return row < p.R ? base + (pc >> 4) * 64 + chunk * 16 : p.zeros + (pc >> 4) * 64 + chunk * 16;
   };
   auto stage_w = [&](int part, int step, int slot) __attribute__((always_inline)) {
-    const unsigned base = (unsigned)((part * nsteps + step) * WFR) * (unsigned)FRAG;
-#pragma unroll
-    for (int i = 0; i < WPER; ++i) {
-      const int f = wv + GM_NW * i;
-      const int fs = f < WFR ? f : 0;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_srd, (__attribute__((address_space(3))) void*)(wring + slot * WSLOT + f * FRAG), 16, lane16,
-                                               base + (unsigned)fs * (unsigned)FRAG, 0, 0);
-    }
+    GmRing<NTW>::stage(w_srd, wring + slot * WSLOT, (unsigned)((part * nsteps + step) * WFR) * (unsigned)FRAG, 0, wv, lane16);
   };
   auto stage_x = [&](const char* src, int pc, int buf) __attribute__((always_inline)) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -247,14 +240,14 @@ __global__ __launch_bounds__(64 * GM_NW, 1) void gemm_rows_kernel(const GM p) {
         if (p.res) {
 #pragma unroll
           for (int t = 0; t < NTW; ++t)
-            rv[t] = __builtin_bit_cast(V4, __builtin_amdgcn_raw_buffer_load_b64(r_srd, ok ? base + (unsigned)(16 * t * sizeof(T)) : 0xfffffff0u, 0, 0));
+            rv[t] = __builtin_bit_cast(V4, __builtin_amdgcn_raw_buffer_load_b64(r_srd, ok ? base + (unsigned)(16 * t * sizeof(T)) : SRD_DROP, 0, 0));
         }
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
           V4 o;
 #pragma unroll
           for (int r = 0; r < 4; ++r) o[r] = (T)(acc[q][t][r] + bs[t][r] + (p.res ? (float)rv[t][r] : 0.f));
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), o_srd, ok ? base + (unsigned)(16 * t * sizeof(T)) : 0xfffffff0u, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), o_srd, ok ? base + (unsigned)(16 * t * sizeof(T)) : SRD_DROP, 0, 0);
           if (p.stats) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -337,8 +330,8 @@ static int linear_rows_impl(const void* x, const void* xb, int Ka, const void* p
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     const char* const what = "linear_rows launch";
-    if (ntw == 5) return sta_launch_lds<gemm_rows_kernel<T, 5>>(what, gm_lds(5), dim3(grid), dim3(64 * GM_NW), gm_lds(5), st, p);
-    return sta_launch_lds<gemm_rows_kernel<T, 4>>(what, gm_lds(4), dim3(grid), dim3(64 * GM_NW), gm_lds(4), st, p);
+    if (ntw == 5) return sta_launch_lds<gemm_rows_kernel<T, 5>>(what, gm_lds<5>, dim3(grid), dim3(64 * GM_NW), gm_lds<5>, st, p);
+    return sta_launch_lds<gemm_rows_kernel<T, 4>>(what, gm_lds<4>, dim3(grid), dim3(64 * GM_NW), gm_lds<4>, st, p);
   });
 }
 

@@ -29,6 +29,7 @@
 #include "sta_unet.h"
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
+#include "sta_wring_dev.h"
 
 namespace {
 
@@ -38,18 +39,11 @@ constexpr int LQ_NSC_QK = 2 * LQ_C / 32;       // 20 sub-chunks of q|k (32 outpu
 constexpr int LQ_NSC = 3 * LQ_C / 32;          // 30 sub-chunks in all (the last 10: V)
 constexpr int LQ_SC_FR = 2 * LQ_NKS;           // 20 fragments per sub-chunk
 constexpr int LQ_NW = 8;
-constexpr int LQ_PER = (LQ_SC_FR + LQ_NW - 1) / LQ_NW;     // 3 LDS-DMA instructions per wave per sub-chunk (4 padding copies)
-constexpr int LQ_SLOT = LQ_PER * LQ_NW * FRAG; // 24 KiB
+using LqRing = WRing<LQ_NW, LQ_SC_FR>;         // 3 LDS-DMA instructions per wave per sub-chunk (4 padding copies), 24 KiB per slot
+constexpr int LQ_SLOT = LqRing::SLOT;
 constexpr int LQ_CHUNK = 272;                  // LDS bytes per 8-channel chunk of a 16-row item: 16 rows x 16 B + 16 B of padding
 constexpr int LQ_TILE = (LQ_C / 8) * LQ_CHUNK; // 10 880 bytes per wave
 constexpr int LQ_LDS = 2 * LQ_SLOT + LQ_NW * LQ_TILE;
-
-// csrc/sta_unet.hip::wave_sum — the same butterfly, so the row statistics are the same bits
-__device__ __forceinline__ float lq_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // [Wq'; Wk] [2C][C] and Wv [C][C] -> [sub-chunk sc][t][k-step f] fragments. q|k (sc < 20): lane (g, c) holds
 // Wqk[32 sc + 8 (c >> 2) + 4 t + (c & 3)][32 f + 8 g .. + 7]; V: Wv[32 (sc - 20) + 16 t + c][32 f + 8 g .. + 7]
@@ -58,7 +52,7 @@ __global__ __launch_bounds__(64) void pack_wqkv_kernel(const T* __restrict__ wqk
   const int fr = blockIdx.x;                   // (sc * 2 + t) * NKS + f
   const int f = fr % LQ_NKS, t = (fr / LQ_NKS) & 1, sc = fr / (2 * LQ_NKS);
   const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
-  const T* src = sc < LQ_NSC_QK ? wqk + (size_t)(32 * sc + 8 * (c >> 2) + 4 * t + (c & 3)) * LQ_C
+  const T* src = sc < LQ_NSC_QK ? wqk + (size_t)(32 * sc + 8 * (c >> 2) + 4 * t + (c & 3)) * LQ_C      // row frag_sigma(2 sc + t, c), spelled out
                                 : wv + (size_t)(32 * (sc - LQ_NSC_QK) + 16 * t + c) * LQ_C;
   const typename Tr<T>::V8 x = *(const typename Tr<T>::V8*)(src + 32 * f + 8 * g);
   *(typename Tr<T>::V8*)(packed + (size_t)fr * (FRAG / 2) + lane * 8) = x;
@@ -92,13 +86,7 @@ __global__ __launch_bounds__(64 * LQ_NW, 2) void ln_qkv_kernel(const LQ p) {
   const unsigned lane16 = (unsigned)lane * 16u;
   const __amdgpu_buffer_rsrc_t w_srd = make_srd(p.w, (unsigned)(LQ_NSC * LQ_SC_FR * FRAG));
   auto stage = [&](int sc, int slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < LQ_PER; ++i) {
-      const int f = wv + LQ_NW * i;
-      const int fs = f < LQ_SC_FR ? f : 0;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_srd, (__attribute__((address_space(3))) void*)(ring + slot * LQ_SLOT + f * FRAG), 16, lane16,
-                                               (unsigned)((sc * LQ_SC_FR + fs) * FRAG), 0, 0);
-    }
+    LqRing::stage(w_srd, ring + slot * LQ_SLOT, 0u, sc * LQ_SC_FR, wv, lane16);
   };
   const unsigned xbytes = (unsigned)((size_t)p.R * LQ_C * sizeof(T));
   const __amdgpu_buffer_rsrc_t x_srd = make_srd(p.x, xbytes);
@@ -126,7 +114,7 @@ __global__ __launch_bounds__(64 * LQ_NW, 2) void ln_qkv_kernel(const LQ p) {
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
         const long row = row0 + 8 * (c >> 2) + 4 * it + (c & 3);
-        xo[it][c] = (on && row < p.R) ? (unsigned)(row * LQ_C * (long)sizeof(T)) + lane16 : 0xfffffff0u;
+        xo[it][c] = (on && row < p.R) ? (unsigned)(row * LQ_C * (long)sizeof(T)) + lane16 : SRD_DROP;
         raw[it][c] = srd_load16<V8>(x_srd, xo[it][c], 0);
       }
 #pragma unroll
@@ -160,7 +148,7 @@ __global__ __launch_bounds__(64 * LQ_NW, 2) void ln_qkv_kernel(const LQ p) {
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float mean = lq_wave_sum(sum[r]) / (float)C;
+          const float mean = wave_sum(sum[r]) / (float)C;
           float q = 0.f;
           if (on) {
 #pragma unroll
@@ -169,7 +157,7 @@ __global__ __launch_bounds__(64 * LQ_NW, 2) void ln_qkv_kernel(const LQ p) {
               q += dlt * dlt;
             }
           }
-          const float rstd = rsqrtf(lq_wave_sum(q) / (float)C + p.eps);
+          const float rstd = rsqrtf(wave_sum(q) / (float)C + p.eps);
           V8 o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = (T)((v[r][e] - mean) * rstd * (float)gm[e] + (float)bt[e]);
@@ -224,7 +212,7 @@ __global__ __launch_bounds__(64 * LQ_NW, 2) void ln_qkv_kernel(const LQ p) {
           V8 o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = (T)acc[e >> 2][it][e & 3];
-          const unsigned qo = row < p.R ? (unsigned)(row * (2 * LQ_C) * (long)sizeof(T)) + (unsigned)(32 * sc + 8 * g) * (unsigned)sizeof(T) : 0xfffffff0u;
+          const unsigned qo = row < p.R ? (unsigned)(row * (2 * LQ_C) * (long)sizeof(T)) + (unsigned)(32 * sc + 8 * g) * (unsigned)sizeof(T) : SRD_DROP;
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), qk_srd, qo, 0, 0);
         }
       } else {
@@ -237,7 +225,7 @@ __global__ __launch_bounds__(64 * LQ_NW, 2) void ln_qkv_kernel(const LQ p) {
           V8 o;
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = (T)acc[t][e >> 2][e & 3];
-          const unsigned vo = rowb < p.R ? (unsigned)((ch * p.R + rowb) * (long)sizeof(T)) : 0xfffffff0u;
+          const unsigned vo = rowb < p.R ? (unsigned)((ch * p.R + rowb) * (long)sizeof(T)) : SRD_DROP;
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), vt_srd, vo, 0, 0);
         }
       }

@@ -27,6 +27,7 @@
 #include "sta_xattn.h"
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
+#include "sta_wring_dev.h"
 #include "sta_xattn_proj3.h"
 
 namespace {
@@ -37,12 +38,10 @@ constexpr int RG_NRT = RG_C / 16;          // 20 output row tiles
 constexpr int RG_NCH = RG_NRT / 2;         // 10 chunks of two row tiles
 constexpr int RG_NW = 8;                   // waves per workgroup
 constexpr int RG_CHUNK_FR = 2 * RG_NKS;    // 20 fragments per chunk
-constexpr int RG_PER = (RG_CHUNK_FR + RG_NW - 1) / RG_NW;   // LDS-DMA instructions per wave per chunk (3; 4 padding copies)
-constexpr int RG_SLOT = RG_PER * RG_NW * FRAG;              // 24 KiB per ring slot
+using RgRing = WRing<RG_NW, RG_CHUNK_FR>;  // 3 LDS-DMA instructions per wave per chunk (4 padding copies), 24 KiB per slot
+constexpr int RG_SLOT = RgRing::SLOT;
 constexpr int RG_TAB = 3 * RG_C * 2;       // bias | gamma | beta as 16-bit, behind the ring
 constexpr int RG_LDS = 2 * RG_SLOT + RG_TAB;
-
-__host__ __device__ constexpr int rg_sigma(int u, int rho) { return 32 * (u >> 1) + 8 * (rho >> 2) + 4 * (u & 1) + (rho & 3); }
 
 // Channel behind slot j of lane row g of fragment f of the SELF-attention kernel's out-fragment order (sta_selfattn_fwd_sfrag):
 // f < 8: head f, O^T rows 4g + j of tile 0 | 16 + 4g + (j - 4) of tile 1 (= head dims, no permutation there);
@@ -58,7 +57,7 @@ __global__ __launch_bounds__(64) void pack_wo_ofrag_kernel(const T* __restrict__
   const int fr = blockIdx.x;               // (v * 2 + t) * NKS + f
   const int u = fr / RG_NKS, f = fr % RG_NKS;
   const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
-  const int row = rg_sigma(u, c);
+  const int row = frag_sigma(u, c);
   T* dst = packed + (size_t)fr * (FRAG / 2) + lane * 8;
 #pragma unroll
   for (int j = 0; j < 8; ++j) dst[j] = wo[(size_t)row * RG_C + (kind ? sfrag_channel(f, g, j) : sta_p3::ofrag_channel(f, g, j))];
@@ -93,25 +92,17 @@ __global__ __launch_bounds__(64 * RG_NW, 2) void to_out_ln_ofrag_kernel(const RG
     tab[2 * RG_C + i] = ((const T*)p.beta)[i];
   }
   const long nblk = (p.R + 16 * RG_NW - 1) / (16 * RG_NW);
-  // LDS-DMA of weight chunk `ch` into ring slot `slot`: 20 fragments, waves round-robin, the 4 spare positions re-read fragment 0
-  // (buffer form: the per-lane part of the address is ONE register, lane * 16; the fragment is a scalar offset)
   const __amdgpu_buffer_rsrc_t w_srd = make_srd(p.wo, (unsigned)(RG_NRT * RG_NKS * FRAG));
   const unsigned lane16 = (unsigned)lane * 16u;
-  auto stage = [&](int ch, int slot) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < RG_PER; ++i) {
-      const int f = wv + RG_NW * i;
-      const int fs = f < RG_CHUNK_FR ? f : 0;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_srd, (__attribute__((address_space(3))) void*)(ring + slot * RG_SLOT + f * FRAG), 16, lane16,
-                                           (unsigned)((ch * RG_CHUNK_FR + fs) * FRAG), 0, 0);
-    }
+  auto stage = [&](int ch, int slot) __attribute__((always_inline)) {      // weight chunk `ch` into ring slot `slot`
+    RgRing::stage(w_srd, ring + slot * RG_SLOT, 0u, ch * RG_CHUNK_FR, wv, lane16);
   };
   const size_t total = (size_t)p.R * RG_C * sizeof(T);
   const __amdgpu_buffer_rsrc_t a_srd = make_srd(p.a, (unsigned)(total > 0xfffffff0ull ? 0xfffffff0ull : total));
   // (activations above 4 GiB are refused by the host wrapper: 32-bit buffer offsets)
   auto a_off = [&](long blk) -> unsigned {
     const long row0 = (blk * RG_NW + wv) * 16;
-    return (blk < nblk && row0 < p.R) ? (unsigned)(row0 * RG_C * (long)sizeof(T)) + (unsigned)lane * 16u : 0xfffffff0u;
+    return (blk < nblk && row0 < p.R) ? (unsigned)(row0 * RG_C * (long)sizeof(T)) + (unsigned)lane * 16u : SRD_DROP;
   };
   long blk = blockIdx.x;
   V8 b[RG_NKS];
@@ -155,10 +146,7 @@ __global__ __launch_bounds__(64 * RG_NW, 2) void to_out_ln_ofrag_kernel(const RG
       acc[2 * CH] = a0;
       acc[2 * CH + 1] = a1;
     };
-    chunk(std::integral_constant<int, 0>{}); chunk(std::integral_constant<int, 1>{}); chunk(std::integral_constant<int, 2>{});
-    chunk(std::integral_constant<int, 3>{}); chunk(std::integral_constant<int, 4>{}); chunk(std::integral_constant<int, 5>{});
-    chunk(std::integral_constant<int, 6>{}); chunk(std::integral_constant<int, 7>{}); chunk(std::integral_constant<int, 8>{});
-    chunk(std::integral_constant<int, 9>{});
+    sta_static_for<RG_NCH>(chunk);
     {   // the NEXT item's B fragments into the registers the last MFMA just released: they land under the epilogue
       const unsigned vo = a_off(blk + gridDim.x);
 #pragma unroll

@@ -8,16 +8,11 @@
 #include "sta_xattn.h"
 #include "sta_unet.h"
 #include "sta_internal.h"
+#include "sta_wring_dev.h"
 
 namespace {
 
 template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // sum over the workgroup; `sh` holds NT/64 floats; every thread gets the result
 template <int NT>

@@ -13,16 +13,11 @@
 #include "sta_xattn.h"
 #include "sta_unet.h"
 #include "sta_internal.h"
+#include "sta_wring_dev.h"
 
 namespace {
 
 template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // --------------------------------------------------------------------------------------------------
 // GroupNorm (+ pre-add) (+ SiLU) backward on NHWC activations, same work split as the forward (sta_unet.hip): a workgroup

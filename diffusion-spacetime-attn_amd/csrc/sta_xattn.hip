@@ -153,10 +153,10 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const Params pin) {
     for (int qt = 0; qt < QT; ++qt) {
       const int px = px0 + 16 * qt + c16;
       // pixels >= N and head-dim offsets >= d are pushed out of the descriptor's range -> read as 0
-      const unsigned base = px < N ? (unsigned)px * row_bytes + (unsigned)(h * d + 8 * g) * (unsigned)sizeof(T) : 0xfffffff0u;
+      const unsigned base = px < N ? (unsigned)px * row_bytes + (unsigned)(h * d + 8 * g) * (unsigned)sizeof(T) : SRD_DROP;
 #pragma unroll
       for (int s = 0; s < NKS; ++s)
-        qf[qt][s] = srd_load16<V8>(q_srd, (32 * s + 8 * g < d) ? base : 0xfffffff0u, qrow + 64u * s);
+        qf[qt][s] = srd_load16<V8>(q_srd, (32 * s + 8 * g < d) ? base : SRD_DROP, qrow + 64u * s);
     }
     const unsigned cbase = (unsigned)cc * ctx_stride;
 #pragma unroll
@@ -598,7 +598,7 @@ __global__ __launch_bounds__(64) void xattn_token_maps_kernel(const MapParams p)
   }
 
   // pixels >= N and head-dim offsets >= d are pushed out of the descriptor's range -> read as 0
-  const unsigned qbase = px < N ? (unsigned)px * row_bytes + (unsigned)(8 * g) * (unsigned)sizeof(T) : 0xfffffff0u;
+  const unsigned qbase = px < N ? (unsigned)px * row_bytes + (unsigned)(8 * g) * (unsigned)sizeof(T) : SRD_DROP;
   float acc[MAPS_RB];
 #pragma unroll
   for (int j = 0; j < MAPS_RB; ++j) acc[j] = 0.f;
@@ -607,7 +607,7 @@ __global__ __launch_bounds__(64) void xattn_token_maps_kernel(const MapParams p)
     const unsigned qoff = (unsigned)(h * d) * (unsigned)sizeof(T);
     const unsigned koff = (unsigned)h * all_frags(NDT) * FRAG;
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) qf[s] = srd_load16<V8>(q_srd, (32 * s + 8 * g < d) ? qbase : 0xfffffff0u, qoff + 64u * s);
+    for (int s = 0; s < NKS; ++s) qf[s] = srd_load16<V8>(q_srd, (32 * s + 8 * g < d) ? qbase : SRD_DROP, qoff + 64u * s);
 #pragma unroll
     for (int f = 0; f < NKF; ++f) ka[f] = srd_load16<V8>(kv_srd, lane * 16, koff + f * FRAG);
     f32x4 st[NKT];

@@ -257,10 +257,10 @@ __global__ __launch_bounds__(64 * NWV, 1) void xattn_bwd_res_kernel(const Params
       const int px = (wt + it * W) * TP + (wv * QT + qt) * 16 + c16;
       const bool ok = it < iters && px < N;
       o.own[qt] = p.mask[ok ? px : 0];
-      const unsigned base = ok ? (unsigned)px * row_bytes + (unsigned)(h * d + 8 * g) * (unsigned)sizeof(T) : 0xfffffff0u;
+      const unsigned base = ok ? (unsigned)px * row_bytes + (unsigned)(h * d + 8 * g) * (unsigned)sizeof(T) : SRD_DROP;
 #pragma unroll
       for (int s = 0; s < NKS; ++s) {
-        const unsigned vo = (32 * s + 8 * g < d) ? base : 0xfffffff0u;
+        const unsigned vo = (32 * s + 8 * g < d) ? base : SRD_DROP;
         o.q0[qt][s] = srd_load16<V8>(q_srd, vo, 64u * s);
         o.g0[qt][s] = srd_load16<V8>(g_srd, vo, 64u * s);
         o.g1[qt][s] = srd_load16<V8>(g_srd, vo, row1 + 64u * s);

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include "sta_xattn.h"
 #include "sta_internal.h"
+#include "sta_wring_dev.h"
 
 namespace {
 
@@ -19,7 +20,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int NKT = 5;      // key tiles of 16 for S^T (M <= 80)
 constexpr int NPS = 3;      // key steps of 32 for PV (96 slots; slots of tile 5 are zero)
-constexpr int FRAG = 1024;  // bytes of one operand fragment (64 lanes x 16 B)
 constexpr int MAXK = STA_MAX_OBJECTS;
 
 template <typename T> struct Tr;

@@ -171,10 +171,10 @@ __global__ __launch_bounds__(64 * NWV, 2) void xattn_fwd_proj_kernel(const PPara
   auto voff_of = [&](int it) -> unsigned {
     if constexpr (YFRAG) {      // fragment s of the wave's 16-pixel group: byte offset of its first pixel's row + 1024 s + 16 lane
       const int px0 = tile_of(it) * TP + wv * 16;
-      return (it < iters && px0 < N) ? (unsigned)px0 * row_bytes + (unsigned)lane * 16u : 0xfffffff0u;
+      return (it < iters && px0 < N) ? (unsigned)px0 * row_bytes + (unsigned)lane * 16u : SRD_DROP;
     }
     const int px = tile_of(it) * TP + wv * 16 + c16;
-    return (it < iters && px < N) ? (unsigned)px * row_bytes + (unsigned)g * 16u : 0xfffffff0u;
+    return (it < iters && px < N) ? (unsigned)px * row_bytes + (unsigned)g * 16u : SRD_DROP;
   };
   auto mask_of = [&](int it) -> unsigned {
     const int px = tile_of(it) * TP + wv * 16 + c16;
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void xattn_fwd_proj_wqs_kernel(const P
   auto px_of = [&](int it, int qt) -> int { return (wt + it * W) * TP + (wv * QT + qt) * 16 + c16; };
   auto voff_of = [&](int it, int qt) -> unsigned {
     const int px = px_of(it, qt);
-    return (it < iters && px < N) ? (unsigned)px * row_bytes + (unsigned)g * 16u : 0xfffffff0u;
+    return (it < iters && px < N) ? (unsigned)px * row_bytes + (unsigned)g * 16u : SRD_DROP;
   };
   auto mask_of = [&](int it, int qt) -> unsigned {
     const int px = px_of(it, qt);

@@ -168,7 +168,7 @@ __device__ __forceinline__ OutRow pack_out(const f32x4 (&a)[3]) {
 //   bytes  64..127: lane row 0 = A tail, rows 1..3 = B main (B dims 0..23)      address = seg + 64 + 16 g
 //   bytes 128..159: lane row 0 = B main (B dims 24..31), row 1 = B tail          address = seg + 128 + 16 g, rows 2, 3 off
 // `seg` = byte offset of the pair segment of this lane's pixel row in the output buffer; lanes that must not store (pixel
-// >= N: `valid` false; lane rows 2, 3 of the last store) get the offset 0xfffffff0, which the descriptor's bounds check drops.
+// >= N: `valid` false; lane rows 2, 3 of the last store) get the offset SRD_DROP, which the descriptor's bounds check drops.
 __device__ __forceinline__ void store_pair_rest(__amdgpu_buffer_rsrc_t srd, unsigned seg, bool valid, int g, const unsigned (&tailA)[2], const OutRow& b) {
   auto s0 = __builtin_amdgcn_permlane16_swap(tailA[0], b.tail[0], false, false);
   auto s1 = __builtin_amdgcn_permlane16_swap(tailA[1], b.tail[1], false, false);
@@ -176,8 +176,8 @@ __device__ __forceinline__ void store_pair_rest(__amdgpu_buffer_rsrc_t srd, unsi
   const bool row0 = g == 0;
   const u32x4 v2 = {row0 ? tail[0] : b.main[0], row0 ? tail[1] : b.main[1], row0 ? tail[2] : b.main[2], row0 ? tail[3] : b.main[3]};
   const u32x4 v3 = {row0 ? b.main[0] : tail[0], row0 ? b.main[1] : tail[1], row0 ? b.main[2] : tail[2], row0 ? b.main[3] : tail[3]};
-  __builtin_amdgcn_raw_buffer_store_b128(v2, srd, valid ? seg + 64u + 16u * (unsigned)g : 0xfffffff0u, 0, 0);
-  __builtin_amdgcn_raw_buffer_store_b128(v3, srd, (valid && g < 2) ? seg + 128u + 16u * (unsigned)g : 0xfffffff0u, 0, 0);
+  __builtin_amdgcn_raw_buffer_store_b128(v2, srd, valid ? seg + 64u + 16u * (unsigned)g : SRD_DROP, 0, 0);
+  __builtin_amdgcn_raw_buffer_store_b128(v3, srd, (valid && g < 2) ? seg + 128u + 16u * (unsigned)g : SRD_DROP, 0, 0);
 }
 
 template <typename T>
@@ -445,11 +445,11 @@ __global__ __launch_bounds__(512, 2) void xattn_fwd_proj_p3_kernel(const P3 p) {
   auto voff_of = [&](int q, int half = 0) -> unsigned {
     if constexpr (YFRAG) {      // fragment s of the item's group: byte offset of its first pixel's row + 1024 s + 16 lane
       const int px0 = px0_of(q);
-      return (q < nitems && px0 < N) ? (unsigned)px0 * row_bytes + (unsigned)lane * 16u : 0xfffffff0u;
+      return (q < nitems && px0 < N) ? (unsigned)px0 * row_bytes + (unsigned)lane * 16u : SRD_DROP;
     }
     const int px = px0_of(q) + (YFULL ? (c16 & 7) + 8 * half : c16);
     const unsigned slot = YFULL ? (unsigned)(g + 4 * (c16 >> 3)) : (unsigned)g;
-    return (q < nitems && px < N) ? (unsigned)px * row_bytes + slot * 16u : 0xfffffff0u;
+    return (q < nitems && px < N) ? (unsigned)px * row_bytes + slot * 16u : SRD_DROP;
   };
   auto mask_of = [&](int q) -> unsigned {
     const int px = px0_of(q) + c16;
@@ -626,7 +626,7 @@ __global__ __launch_bounds__(512, 2) void xattn_fwd_proj_p3_kernel(const P3 p) {
     head(std::integral_constant<int, 0>{}, qA0, qA1, au_A, ac_A);
     if constexpr (OF) {
       // out-fragment order: fragment 2 pr of the item's group, one contiguous KiB per batch row
-      const unsigned fb = valid ? (unsigned)px0_of(qcur) * row_bytes + (unsigned)lane * 16u + 2048u * (unsigned)pr : 0xfffffff0u;
+      const unsigned fb = valid ? (unsigned)px0_of(qcur) * row_bytes + (unsigned)lane * 16u + 2048u * (unsigned)pr : SRD_DROP;
       __builtin_amdgcn_raw_buffer_store_b128(au_A.main, o_srd, fb, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b128(ac_A.main, o_srd, fb, row1, 0);
       head(std::integral_constant<int, 1>{}, qB0, qB1, au_B, ac_B);
@@ -635,13 +635,13 @@ __global__ __launch_bounds__(512, 2) void xattn_fwd_proj_p3_kernel(const P3 p) {
       // tails: lane rows 0, 1 hold [A rows 32 + 4g .. | B rows 32 + 4g ..]; two pairs share fragment 8 + (pr >> 1)
       const u32x4 zu = {au_A.tail[0], au_A.tail[1], au_B.tail[0], au_B.tail[1]}, zc = {ac_A.tail[0], ac_A.tail[1], ac_B.tail[0], ac_B.tail[1]};
       const unsigned zb = (valid && g < 2) ? (unsigned)px0_of(qcur) * row_bytes + (unsigned)lane * 16u + 8192u + 1024u * (unsigned)(pr >> 1) + 512u * (unsigned)(pr & 1)
-                                           : 0xfffffff0u;
+                                           : SRD_DROP;
       __builtin_amdgcn_raw_buffer_store_b128(zu, o_srd, zb, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b128(zc, o_srd, zb, row1, 0);
     } else {
       // head A's dims 0..31 of both batch rows: bytes 0..63 of the pair segment, 16 bytes per lane, no cross-lane exchange
-      __builtin_amdgcn_raw_buffer_store_b128(au_A.main, o_srd, valid ? seg + 16u * (unsigned)g : 0xfffffff0u, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(ac_A.main, o_srd, valid ? seg1 + 16u * (unsigned)g : 0xfffffff0u, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(au_A.main, o_srd, valid ? seg + 16u * (unsigned)g : SRD_DROP, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(ac_A.main, o_srd, valid ? seg1 + 16u * (unsigned)g : SRD_DROP, 0, 0);
       head(std::integral_constant<int, 1>{}, qB0, qB1, au_B, ac_B);
       store_pair_rest(o_srd, seg, valid, g, au_A.tail, au_B);
       store_pair_rest(o_srd, seg1, valid, g, ac_A.tail, ac_B);

@@ -116,14 +116,14 @@ class CrossAttention(nn.Module):
         forward that keeps the log-sum-exp, and the HIP backward kernels (sta.ops.SelfAttentionQKV) instead of PyTorch's SDPA —
         whose backward was the largest kernel of the tracked epochs (profiles/r02_config3_breakdown.txt)."""
         ws = (self.to_q.weight, self.to_k.weight, self.to_v.weight)
-        key = tuple((w.data_ptr(), w._version) for w in ws)
-        if getattr(self, "_wqkv_key", None) != key:
+
+        def cat():
             # as in _self_attention_hip: softmax scale * log2(e) rides in W_q (fp32 product, rounded once), the kernels run in the
             # log2 domain (scale = ln 2: forward with the running maximum as accumulator initial value, 1112 -> 977 us at level 0,
             # 32 rows); autograd differentiates the GEMM with the folded weight, so dx is unchanged
             wq2 = (ws[0].detach().float() * (self.scale * 1.4426950408889634)).to(ws[0].dtype)
-            self._wqkv, self._wqkv_key = torch.cat([wq2, ws[1].detach(), ws[2].detach()]), key
-        o = _ops.SelfAttentionQKV.apply(F.linear(x, self._wqkv), self.heads, _ops.LN2)
+            return torch.cat([wq2, ws[1].detach(), ws[2].detach()])
+        o = _ops.SelfAttentionQKV.apply(F.linear(x, _fused.cached_image(self, "wqkv", ws, cat)), self.heads, _ops.LN2)
         return self.to_out(o)
 
     def _self_attention_hip(self, x, pre_to_out_sfrag=False):
@@ -148,22 +148,18 @@ class CrossAttention(nn.Module):
     def _wqk_cat(self):
         """[Wq * scale * log2 e; Wk], rebuilt only when a weight tensor changes."""
         wq, wk = self.to_q.weight, self.to_k.weight
-        key = (wq.data_ptr(), wq._version, wk.data_ptr(), wk._version)
-        if getattr(self, "_wqk_key", None) != key:
+
+        def cat():
             # softmax scale * log2(e) rides in W_q (multiplied in fp32, rounded once): q leaves the GEMM in log2 units and the
             # kernel's exponent is a bare exp2 of the MFMA result (sta_selfattn.hip, PRE)
             wq2 = (wq.detach().float() * (self.scale * 1.4426950408889634)).to(wq.dtype)
-            self._wqk, self._wqk_key = torch.cat([wq2, wk.detach()]), key
-        return self._wqk
+            return torch.cat([wq2, wk.detach()])
+        return _fused.cached_image(self, "wqk", (wq, wk), cat)
 
     def _ln_qkv_fragments(self):
         """[Wq'; Wk; Wv] as sta_ln_qkv streams it (csrc/sta_lnqkv.hip), repacked only when a weight tensor changes."""
         wv = self.to_v.weight
-        wqk = self._wqk_cat()
-        key = (self._wqk_key, wv.data_ptr(), wv._version, wv.dtype)
-        if getattr(self, "_wqkv_frag_key", None) != key:
-            self._wqkv_frag, self._wqkv_frag_key = _fused.pack_ln_qkv_weight(wqk, wv), key
-        return self._wqkv_frag
+        return _fused.cached_image(self, "ln_qkv", (self.to_q.weight, self.to_k.weight, wv), lambda: _fused.pack_ln_qkv_weight(self._wqk_cat(), wv))
 
     def _self_attention_hip_fp8(self, x):
         """The same with e4m3 weights (sta.fp8, BASELINE configs[4]): x is quantised ONCE per call (sta_quant_rows_fp8) and
@@ -391,10 +387,7 @@ class BasicTransformerBlock(nn.Module):
     def _wq_fragments(self):
         """to_q.weight of attn2 in MFMA operand order, repacked only when the weight tensor changes."""
         w = self.attn2.to_q.weight
-        key = (w.data_ptr(), w._version, w.dtype)
-        if getattr(self, "_wq_key", None) != key:
-            self._wq_frag, self._wq_key = _ops.pack_wq(w, self.attn2.heads), key
-        return self._wq_frag
+        return _fused.cached_image(self, "wq", (w,), lambda: _ops.pack_wq(w, self.attn2.heads))
 
     def _ff_fusable(self, x):
         net = self.ff.net
@@ -406,35 +399,25 @@ class BasicTransformerBlock(nn.Module):
         if not ffq:
             return self.ff(y) + x
         proj = self.ff.net[0].proj
-        key = (proj.weight.data_ptr(), proj.weight._version, proj.weight.dtype)
-        if getattr(self, "_w1_key", None) != key:
-            self._w1_frag, self._w1_key = _fused.pack_geglu_weight(proj.weight), key
+        w1 = _fused.cached_image(self, "w1", (proj.weight,), lambda: _fused.pack_geglu_weight(proj.weight))
         out = self.ff.net[2]
         if isinstance(out, nn.Linear):
             # ... and the output Linear + the block's last residual as one pass over h in fragment order (net[1] is Dropout(0))
-            key2 = (out.weight.data_ptr(), out.weight._version, out.weight.dtype)
-            if getattr(self, "_w2_key", None) != key2:
-                self._w2_frag, self._w2_key = _fused.pack_ff_out_weight(out.weight), key2
-            h = _fused.ff_geglu_qfrag(y, self._w1_frag, proj.bias, proj.out_features // 2, h_frag=True)
-            return _fused.ff_out_res_hfrag(x, h, self._w2_frag, out.bias)
-        h = _fused.ff_geglu_qfrag(y, self._w1_frag, proj.bias, proj.out_features // 2)
+            w2 = _fused.cached_image(self, "w2", (out.weight,), lambda: _fused.pack_ff_out_weight(out.weight))
+            h = _fused.ff_geglu_qfrag(y, w1, proj.bias, proj.out_features // 2, h_frag=True)
+            return _fused.ff_out_res_hfrag(x, h, w2, out.bias)
+        h = _fused.ff_geglu_qfrag(y, w1, proj.bias, proj.out_features // 2)
         return out(self.ff.net[1](h)) + x
 
     def _wo1_fragments(self):
         """attn1.to_out.weight laid out for the self-attention kernel's out-fragment order."""
         w = self.attn1.to_out[0].weight
-        key = (w.data_ptr(), w._version, w.dtype)
-        if getattr(self, "_wo1_key", None) != key:
-            self._wo1_frag, self._wo1_key = _fused.pack_to_out_weight(w, self.attn1.heads, _fused.FRAG_SELFATTN), key
-        return self._wo1_frag
+        return _fused.cached_image(self, "wo1", (w,), lambda: _fused.pack_to_out_weight(w, self.attn1.heads, _fused.FRAG_SELFATTN))
 
     def _wo_fragments(self):
         """to_out.weight of attn2 as sta_to_out_ln_ofrag streams it, repacked only when the weight tensor changes."""
         w = self.attn2.to_out[0].weight
-        key = (w.data_ptr(), w._version, w.dtype)
-        if getattr(self, "_wo_key", None) != key:
-            self._wo_frag, self._wo_key = _fused.pack_to_out_weight(w, self.attn2.heads), key
-        return self._wo_frag
+        return _fused.cached_image(self, "wo", (w,), lambda: _fused.pack_to_out_weight(w, self.attn2.heads))
 
     def _keep_maps(self, q, coef, cache):
         """Parity hook (off by default): the per-step attention maps are a local of the reference's forward

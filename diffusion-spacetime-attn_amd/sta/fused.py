@@ -188,6 +188,19 @@ def _version(t):
         return None
 
 
+def cached_image(owner, slot, weights, build):
+    """The image `build()` makes of `weights` (a packed, concatenated or mirrored copy a kernel streams), kept on `owner` under `slot`
+    and rebuilt only when one of the weight tensors changed: another storage, an in-place update (version counter) or another
+    dtype. THE repack rule of every packed-weight cache. A weight without a version counter (inference tensors, `_version`) keys
+    with None: such tensors cannot be updated in place, so storage and dtype identify them."""
+    key = tuple((w.data_ptr(), _version(w), w.dtype) for w in weights)
+    images = owner.__dict__.setdefault("_sta_images", {})
+    hit = images.get(slot)
+    if hit is None or hit[0] != key:
+        hit = images[slot] = (key, build())
+    return hit[1]
+
+
 def _producer_stats(x):
     """The per-channel sums the producing kernel left on `x` — only while x still holds what that kernel wrote (an in-place update
     since then bumps the tensor's version and the sums are ignored: the consumer then takes its own statistics pass)."""
@@ -385,12 +398,7 @@ def conv3x3_nhwc(x, w_packed, Cout, up2=False, bias=None, res=None, stats=False)
 def packed_conv_weight(owner, conv):
     """conv.weight as sta_conv3x3_nhwc streams it, cached on the owning module and repacked only when the weight tensor changes."""
     w = conv.weight
-    key = (w.data_ptr(), _version(w), w.dtype)
-    cache = owner.__dict__.setdefault("_sta_conv_cache", {})
-    hit = cache.get(id(conv))
-    if hit is None or hit[0] != key:
-        hit = cache[id(conv)] = (key, pack_conv3x3_weight(w))
-    return hit[1]
+    return cached_image(owner, ("conv", id(conv)), (w,), lambda: pack_conv3x3_weight(w))
 
 
 def conv3x3_module(owner, conv, x, bias=None, res=None, up2=False, stats=True):
@@ -592,12 +600,7 @@ def linear_rows(x, w_packed, N, bias=None, res=None, stats_rows=None):
 
 def packed_linear_weight(owner, key_obj, weight):
     """weight as sta_linear_rows streams it, cached on the owning module and repacked only when the weight tensor changes."""
-    key = (weight.data_ptr(), _version(weight), weight.dtype)
-    cache = owner.__dict__.setdefault("_sta_linear_cache", {})
-    hit = cache.get(id(key_obj))
-    if hit is None or hit[0] != key:
-        hit = cache[id(key_obj)] = (key, pack_linear_weight(weight))
-    return hit[1]
+    return cached_image(owner, ("linear", id(key_obj)), (weight,), lambda: pack_linear_weight(weight))
 
 
 def linear_module(lin, x, res=None):
@@ -781,13 +784,11 @@ def conv3x3_tracked_supported(x, weight):
 def conv3x3_tracked(owner, conv, x):
     """conv(x) WITHOUT its bias for a frozen 3x3 nn.Conv2d under autograd (callers fold the bias into the pass that follows)."""
     w = conv.weight
-    key = (w.data_ptr(), _version(w), w.dtype)
-    cache = owner.__dict__.setdefault("_sta_conv_bwd_cache", {})
-    hit = cache.get(id(conv))
-    if hit is None or hit[0] != key:
+
+    def mirrored():                 # the input gradient's weight: channel axes exchanged, taps mirrored
         with torch.no_grad():
-            hit = cache[id(conv)] = (key, pack_conv3x3_weight(w.detach().permute(1, 0, 2, 3).flip(2, 3)))
-    return Conv3x3Fn.apply(x, packed_conv_weight(owner, conv), hit[1], w.shape[1], w.shape[0])
+            return pack_conv3x3_weight(w.detach().permute(1, 0, 2, 3).flip(2, 3))
+    return Conv3x3Fn.apply(x, packed_conv_weight(owner, conv), cached_image(owner, ("conv_bwd", id(conv)), (w,), mirrored), w.shape[1], w.shape[0])
 
 
 def add_bias_tracked(a, b=None, bias=None):

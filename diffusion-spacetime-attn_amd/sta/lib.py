@@ -6,6 +6,7 @@ be resolved, :class:`StaLibraryError` is raised — the product path must never 
 kernels.
 """
 import ctypes
+import glob
 import os
 import shutil
 import subprocess
@@ -133,7 +134,7 @@ def _stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = SOURCES + [os.path.join(_HERE, "isa_lint.py"), os.path.join(INCLUDE, "sta_xattn.h"), os.path.join(INCLUDE, "sta_unet.h"), os.path.join(CSRC, "sta_internal.h"), os.path.join(CSRC, "sta_xattn_dev.h"), os.path.join(CSRC, "sta_xattn_proj3.h"), os.path.join(CSRC, "sta_selfattn_dev.h")]
+    deps = SOURCES + [os.path.join(_HERE, "isa_lint.py")] + glob.glob(os.path.join(INCLUDE, "*.h")) + glob.glob(os.path.join(CSRC, "*.h"))
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 

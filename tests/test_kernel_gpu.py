@@ -773,7 +773,7 @@ def test_self_attention_tracked_module_matches_sdpa():
         finally:
             ops.SELFATTN_ENABLED = True
     torch.cuda.synchronize()
-    assert getattr(attn, "_wqkv", None) is not None          # the tracked HIP path ran
+    assert attn.__dict__.get("_sta_images", {}).get("wqkv") is not None          # the tracked HIP path ran
     for a, b_ in zip(res[0], res[1]):
         assert (a - b_).abs().max() <= 2.0 ** -7 * b_.abs().max(), ((a - b_).abs().max(), b_.abs().max())
 

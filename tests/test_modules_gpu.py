@@ -100,6 +100,48 @@ def test_block_projection_fused_path_vs_reference_golden(dtype, pair, monkeypatc
     assert err.mean() <= 4 * eps * np.abs(ref).mean(), (err.mean(), np.abs(ref).mean())
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_block_fused_chain_repacks_updated_weights(dtype, monkeypatch):
+    """Every packed-weight image of the fused level-0 chain follows an in-place update of its weight: after `w.mul_(0.5)` the block
+    that already holds images of the old weights must give the output of a FRESH block loaded from the updated state_dict, for
+    each weight the chain keeps an image of. Both blocks run the same kernels on the same inputs: bit equality, no tolerance."""
+    from ldm.modules.attention import BasicTransformerBlock
+    from sta import fused, lib, ops, prompt_state
+    monkeypatch.setattr(ops, "PROJ_MIN_WORKGROUPS", 0)
+    monkeypatch.setattr(fused, "ROWGEMM_MIN_ROWS", 0)
+    lib.set_option(lib.OPT_PROJ_PAIR, 1)              # reset after the test by conftest
+    passes, real_tail, real_ff, real_ff2 = [], fused.to_out_add_layernorm_ofrag, fused.ff_geglu_qfrag, fused.ff_out_res_hfrag
+    monkeypatch.setattr(fused, "to_out_add_layernorm_ofrag", lambda *a, **k: (passes.append("to_out"), real_tail(*a, **k))[1])
+    monkeypatch.setattr(fused, "ff_geglu_qfrag", lambda *a, **k: (passes.append("ff1"), real_ff(*a, **k))[1])
+    monkeypatch.setattr(fused, "ff_out_res_hfrag", lambda *a, **k: (passes.append("ff2"), real_ff2(*a, **k))[1])
+    g = _load("block_d40.npz")
+    dim, C, heads, K, seed = (int(g[k]) for k in ("dim", "C", "heads", "K", "seed"))
+    x, context, local_ctx = gi.block_inputs(dim, C, K, seed, gi.load_uncond())
+    x, context = x.cuda().to(dtype), context.cuda().to(dtype)
+    coef, boxes = torch.from_numpy(g["coef"]).cuda(), [list(c) for c in g["centres"]]
+    prompt_state.begin_prompt([c.cuda() for c in local_ctx], first_timestep=981)
+
+    def run(b):
+        with torch.no_grad():
+            return b(x, context=context, time=torch.tensor(981), coef=coef, bboxs_curr=boxes)
+
+    blk = BasicTransformerBlock(C, heads, C // heads, context_dim=768, checkpoint=False)
+    seeded_fill_(blk, seed)
+    blk = blk.to("cuda", dtype)
+    before = run(blk)
+    assert passes == ["to_out", "to_out", "ff1", "ff2"], "the fused chain of level 0 was not taken"
+    for name in ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "attn2.to_q", "attn2.to_out.0", "ff.net.0.proj", "ff.net.2"):
+        with torch.no_grad():
+            blk.get_submodule(name).weight.mul_(0.5)
+        got = run(blk)
+        fresh = BasicTransformerBlock(C, heads, C // heads, context_dim=768, checkpoint=False).to("cuda", dtype)
+        fresh.load_state_dict(blk.state_dict())
+        want = run(fresh)
+        assert not torch.equal(want, before), name      # the update is visible in the output at all
+        assert torch.equal(got, want), (name, (got.float() - want.float()).abs().max().item())
+        before = want
+
+
 @pytest.mark.parametrize("name", ["d40", "d80", "d160", "d8k4"])
 @pytest.mark.parametrize("dtype,tol", [(torch.float16, 1e-3), (torch.bfloat16, 8e-3)])
 def test_block_attention_maps_vs_reference(name, dtype, tol):
