@@ -451,3 +451,6 @@ int sta_xattn_bwd(const void* q, const void* packed, const uint8_t* mask, const 
 
 }  // extern "C"
 
+// The backward of the token-map readout (sta_xattn_token_maps_bwd) is a file of its own, compiled as part of this translation unit
+// (sta/lib.py::INCLUDED_SOURCES): same flags, same pass through the hazard lint.
+#include "sta_xattn_maps_bwd.hip"

@@ -164,11 +164,14 @@ class _CallRecompute(torch.autograd.Function):
     instead (util.py:105-145) because 51 calls of saved activations do not fit its GPU; here one call's activations
     (~1.6 GiB per prompt at 512^2) exist only while that call is differentiated, so 32 prompts per step fit in 288 GB and the
     launch-bound eager autograd is amortised over all of them. The gradient is the recomputed call's (16-bit roundings of the
-    two forward chains differ in the last bit; tests/test_modules_gpu.py holds dW to the float64 chain)."""
+    two forward chains differ in the last bit; tests/test_modules_gpu.py holds dW to the float64 chain).
+    `inject` (an _AttnInject, only passed while an attention-layout loss is attached): that loss is a sum of per-call terms E_k,
+    each a function of its own call's activations alone, so the recomputed call needs nothing from the forward — the eager re-run
+    records E_k and it is differentiated together with the call's output, seeded with d(scaled loss) / dE_k."""
 
     @staticmethod
-    def forward(ctx, fast_fn, slow_fn, t, x, coef):
-        ctx.slow_fn, ctx.t = slow_fn, t
+    def forward(ctx, fast_fn, slow_fn, t, x, coef, inject=None):
+        ctx.slow_fn, ctx.t, ctx.inject = slow_fn, t, inject
         ctx.save_for_backward(x, coef)
         with torch.no_grad():
             return fast_fn(x, t, coef).clone()          # the graph's output buffer is reused by the next replay
@@ -182,20 +185,41 @@ class _CallRecompute(torch.autograd.Function):
         gx = gc = None
         with torch.enable_grad():
             out = ctx.slow_fn(x_, ctx.t, c_)
+            term = None if ctx.inject is None else ctx.inject.term()        # E_k of this re-run (None: nothing attached / recorded)
             wrt = [t for t, need in ((x_, need_x), (c_, need_c)) if need]
             if wrt:
-                grads = list(torch.autograd.grad(out, wrt, grad_out.to(out.dtype), allow_unused=True))
+                if term is None:
+                    grads = list(torch.autograd.grad(out, wrt, grad_out.to(out.dtype), allow_unused=True))
+                else:
+                    grads = list(torch.autograd.grad([out, term], wrt, [grad_out.to(out.dtype), ctx.inject.seed(term)], allow_unused=True))
                 gx = grads.pop(0) if need_x else None
                 gc = grads.pop(0) if need_c else None
-        ctx.slow_fn = None
-        return None, None, None, gx, gc
+        ctx.slow_fn = ctx.inject = None
+        return (None, None, None, gx, gc) + ((None,) if len(ctx.needs_input_grad) > 5 else ())
+
+
+class _AttnInject:
+    """What a recomputed call needs to differentiate its own term of the attention-layout loss: the collector and the factor
+    d(scaled loss) / dE_k = attn_loss_weight * loss scale / n_calls (the scale is known only right before backward)."""
+
+    def __init__(self, loss, weight, n_calls):
+        self.loss, self.weight, self.n_calls, self.scale = loss, float(weight), int(n_calls), 1.0
+
+    def term(self):
+        return self.loss.take_call()
+
+    def seed(self, term):
+        return torch.full_like(term, self.weight * self.scale / self.n_calls)
 
 
 class PLMSSampler(object):
     def __init__(self, model, schedule="linear", loss_model=None, opt_epochs=3, lr=0.005, weight_init=5.0,
                  local_loss_weight=5.0, use_graph=True, save_images=True, outdir="result_outputs/", loss_scale=None, keep_calls=None,
-                 batched_loss=True, attn_capture=None, **kwargs):
-        """`attn_capture`: a sta.attnmaps.AttnCapture. The trajectory whose image is kept (the last epoch's, never tracked) then runs
+                 batched_loss=True, attn_capture=None, attn_loss=None, attn_loss_weight=1.0, **kwargs):
+        """`attn_loss`: a sta.attnloss.AttnLayoutLoss. Tracked epochs then minimise [the fidelity loss if `loss_model` is given] +
+        attn_loss_weight x the attention-layout loss, recorded inside the tracked UNet calls; with `loss_model=None` they decode
+        nothing. The last epoch is untouched (never tracked: the loss records nothing there). None: nothing changes.
+        `attn_capture`: a sta.attnmaps.AttnCapture. The trajectory whose image is kept (the last epoch's, never tracked) then runs
         eagerly — no hipGraph replay — with the capture attached, and its AttnResult is left in `last_attn`; earlier (tracked) epochs
         record nothing. None: nothing changes.
         `loss_scale`: the fidelity loss is multiplied by it before backward and W.grad divided by it before the Adam step.
@@ -219,6 +243,8 @@ class PLMSSampler(object):
         self.use_graph, self.save_images, self.outdir = use_graph, save_images, outdir
         self.last_result = None
         self.attn_capture, self.last_attn = attn_capture, None
+        self.attn_loss, self.attn_loss_weight = attn_loss, float(attn_loss_weight)
+        self._attn_inject = None          # _AttnInject while a tracked epoch with an attention loss runs
         self._graphs = None
         self._call_key = None             # (latent shape, object count) of the trajectory being sampled: keys the measured activation size
 
@@ -316,8 +342,9 @@ class PLMSSampler(object):
         W = torch.full((b, K, S), self.weight_init / K if K else 0.0, device=device, dtype=torch.float32)   # :204-209
         W.requires_grad_(self.opt_epochs > 0 and K > 0)
         optimizer = torch.optim.Adam([W], lr=self.lr) if W.requires_grad else None
-        if W.requires_grad and self.opt_epochs > 1 and self.clip_loss_model is None:      # before the first trajectory, not after it
-            raise RuntimeError("opt_epochs > 0 needs a loss_model (see DCLIPLoss / load_clip_model); use opt_epochs=0 for fixed weights")
+        if W.requires_grad and self.opt_epochs > 1 and self.clip_loss_model is None and self.attn_loss is None:      # before the first trajectory, not after it
+            raise RuntimeError("opt_epochs > 0 needs a loss_model (see DCLIPLoss / load_clip_model) or an attn_loss (sta.attnloss); "
+                               "use opt_epochs=0 for fixed weights")
 
         epochs = max(self.opt_epochs, 1)
         result = {}
@@ -331,16 +358,24 @@ class PLMSSampler(object):
             cap = self.attn_capture if last else None
             if cap is not None:
                 cap.begin(boxes, texts=texts, names=names)
+            al = self.attn_loss if track else None
+            decode = not track or self.clip_loss_model is not None or al is None      # tracked with the attention loss alone: no decode
             while True:
+                if al is not None:
+                    al.begin(boxes, texts=texts, names=names, n_calls=self._n_calls(S))
+                    self._attn_inject = _AttnInject(al, self.attn_loss_weight, self._n_calls(S))
                 # tracked epochs: eager autograd through the 51 calls, or (sta.pipeline.set_recompute mode "call") the
                 # fixed-weight forward per call + one re-run of the call under autograd in backward, with the glue passes of
                 # the trunk as autograd Functions over the HIP kernels (sta.fused.tracked)
-                with torch.set_grad_enabled(track), _fused.tracked(by_call), (cap if cap is not None else contextlib.nullcontext()):
+                with torch.set_grad_enabled(track), _fused.tracked(by_call), (cap if cap is not None else contextlib.nullcontext()), \
+                        (self._attn_epoch(al) if al is not None else contextlib.nullcontext()):
                     img = self._trajectory(img_input.clone(), cond, unconditional_conditioning, unconditional_guidance_scale,
                                            time_range, W if batched else W[0], block_boxes, text_index,
                                            graph=self.use_graph and (not track or by_call) and cap is None, call_recompute=by_call)
                     x_img = None
-                    if self.model.first_stage_model is not None and self._paste() is not None:
+                    if not decode:
+                        pass
+                    elif self.model.first_stage_model is not None and self._paste() is not None:
                         # inpainting with a pixel-space pair: the result (and what the loss sees) is the original outside the mask
                         from sta import solver as _solver
                         x_img = _solver.image_composite(self.model.decode_first_stage(img), *self._paste())
@@ -348,13 +383,18 @@ class PLMSSampler(object):
                         x_img = torch.clamp((self.model.decode_first_stage(img) + 1.0) / 2.0, min=0.0, max=1.0)   # :249-250
                     if track:
                         lm = self.clip_loss_model
-                        if self.batched_loss and getattr(lm, "batch_ready", None) is not None and lm.batch_ready(x_img):
+                        if not decode:
+                            loss = None
+                        elif self.batched_loss and getattr(lm, "batch_ready", None) is not None and lm.batch_ready(x_img):
                             loss = lm.forward_batch(x_img, texts, boxes, names, self.local_loss_weight)
                         else:
                             loss = sum(self._fidelity_loss(x_img[i].float(), texts[i], boxes[i], names[i]) for i in range(b))
                         optimizer.zero_grad()
-                        scale = self._loss_scale(float(loss.detach())) * scale_backoff
-                        (loss * scale if scale != 1.0 else loss).backward()
+                        if al is None:
+                            scale = self._loss_scale(float(loss.detach())) * scale_backoff
+                            (loss * scale if scale != 1.0 else loss).backward()
+                        else:
+                            loss, scale = self._backward_with_attn_loss(loss, al, img, by_call, scale_backoff)
                         # checked whatever the scale (a backoff can land on exactly 1.0): Adam must never see a non-finite gradient
                         if not bool(torch.isfinite(W.grad).all()):
                             if scale_backoff > 2.0 ** -24:
@@ -365,6 +405,7 @@ class PLMSSampler(object):
                         if scale != 1.0:
                             W.grad.div_(scale)
                         optimizer.step()
+                        # (with an attention loss: the whole value, every call's term, whichever way it was differentiated)
                         result.setdefault("losses", []).append(float(loss.detach()))
                 break
             if last:
@@ -377,6 +418,44 @@ class PLMSSampler(object):
                         self._save(x_img[i], epochs - 1, seed, pidx[i], index=i)
         self.last_result = result
         return None
+
+    @contextlib.contextmanager
+    def _attn_epoch(self, al):
+        """The collector attached to the blocks for one tracked trajectory and its backward; detached whatever happens."""
+        try:
+            with al:
+                yield al
+        finally:
+            self._attn_inject = None
+
+    def _backward_with_attn_loss(self, image_loss, al, img, by_call, scale_backoff):
+        """Backward of a tracked epoch with an attention-layout loss attached -> (the whole loss value, the loss scale used).
+        The calls recorded under plain autograd (every call in modes none / res / all, the kept trailing calls in mode call) are
+        ordinary autograd values; the recomputed calls of mode `call` differentiate their own term inside _CallRecompute.backward,
+        seeded with the same weight and loss scale. Without an image loss nothing hangs off the final state, so the backward is
+        rooted there with a zero gradient: it then still reaches every recompute node."""
+        recorded = al.graph_value()
+        if recorded is None and not by_call:
+            raise RuntimeError("the attention loss recorded nothing: no transformer block works at %d x %d in this UNet"
+                               % (al.resolution, al.resolution))
+        parts = [p for p in (image_loss, None if recorded is None else self.attn_loss_weight * recorded) if p is not None]
+        known = sum(parts) if parts else None
+        scale = self._loss_scale(float(known.detach()) if known is not None else 0.0) * scale_backoff
+        self._attn_inject.scale = scale
+        roots, seeds = [], []
+        if known is not None:
+            roots.append(known * scale if scale != 1.0 else known)
+            seeds.append(None)
+        if by_call and image_loss is None and img.requires_grad:
+            roots.append(img)
+            seeds.append(torch.zeros_like(img))
+        torch.autograd.backward(roots, seeds)
+        total = self.attn_loss_weight * al.value().to(img.device)
+        return (total if image_loss is None else image_loss.detach() + total), scale
+
+    def _n_calls(self, S):
+        """UNet calls of a trajectory over S timesteps: the first PLMS step evaluates the UNet twice."""
+        return S + 1
 
     def _loss_scale(self, loss_value):
         if self.loss_scale is not None:
@@ -482,6 +561,8 @@ class PLMSSampler(object):
         def eps(x, t, coef):
             k = calls[0]
             calls[0] += 1
+            if self._attn_inject is not None and torch.is_grad_enabled():
+                self._attn_inject.loss.next_call()          # a new UNet call starts: close the one the attention loss was recording
             if call_recompute and torch.is_grad_enabled() and k >= n_calls - keep_last:
                 # one of the last calls: plain autograd, its activations stay until backward reaches it (_calls_to_keep)
                 before = torch.cuda.memory_allocated() if x.is_cuda else 0
@@ -491,7 +572,8 @@ class PLMSSampler(object):
                     self._call_bytes_key = self._call_key
             elif call_recompute and torch.is_grad_enabled():
                 out = _CallRecompute.apply(lambda x_, t_, c_: unet(apply_fn, x_, t_, c_),
-                                           lambda x_, t_, c_: unet(self.model.apply_model_extra, x_, t_, c_), t, x, coef)
+                                           lambda x_, t_, c_: unet(self.model.apply_model_extra, x_, t_, c_), t, x, coef,
+                                           *(() if self._attn_inject is None else (self._attn_inject,)))
             else:
                 out = unet(apply_fn, x, t, coef)
             if raw:
@@ -560,6 +642,9 @@ class SolverSamplerBase(PLMSSampler):
 
     def _first_call(self):
         return self._start
+
+    def _n_calls(self, S):
+        return S - self._start
 
     # ------------------------------------------------------------------------------------------------ inpainting
     def _set_inpaint(self, mask, x0, image=None, mask_px=None, batch=None):

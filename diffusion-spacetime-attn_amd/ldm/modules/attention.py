@@ -225,6 +225,7 @@ class BasicTransformerBlock(nn.Module):
         self.keep_maps = False       # parity hook: keep the kernel's [K+2, heads, N, 77] attention maps of the last call
         self.last_maps = None
         self._attn_capture = None    # sta.attnmaps.AttnCapture while one is attached: token maps of this block's calls
+        self._attn_loss = None       # sta.attnloss.AttnLayoutLoss while one is attached: differentiable token maps of tracked calls
 
     # -- per-prompt state (reference: the `time == 981` branch, attention.py:240-263) ---------------
     def _stale(self, cache, centres, time):
@@ -302,6 +303,10 @@ class BasicTransformerBlock(nn.Module):
             if len(cache.centres[0]):
                 raise ValueError("coef is required when objects are present")
             coef = x.new_zeros(0, dtype=torch.float32)
+        al = self._attn_loss
+        if al is not None and al.wants(x.shape[1]):
+            # the loss's side value cannot leave a checkpointed forward: a recording block keeps its activations (sta.attnloss)
+            return self._forward(x, coef, cache, in_bias)
         return checkpoint(lambda xx, cc: self._forward(xx, cc, cache, in_bias), (x, coef), self.parameters(), self.checkpoint)
 
     def _forward(self, x, coef, cache, in_bias=None):
@@ -360,6 +365,9 @@ class BasicTransformerBlock(nn.Module):
                 blended = _ops.xattn_blend(q, c, cache.packed, cache.mask, self.attn2.scale)
             x, y = _fused.add_layernorm(x, self.attn2.to_out(blended), None, n3.weight, n3.bias, n3.eps, qfrag=ffq)
             return self._ff_tail(x, y, ffq)
+        al = self._attn_loss                         # an AttnLayoutLoss records only while autograd is enabled: the two branches below
+        if al is not None and not al.wants(x.shape[1]):
+            al = None
         if _fused.tracked_usable(x):
             # tracked epochs (opt-in, fused.TRACKED): the residual adds run inside the LayerNorm passes as above, each pass an
             # autograd Function whose backward is one HIP input-gradient kernel (parameters are frozen)
@@ -370,6 +378,8 @@ class BasicTransformerBlock(nn.Module):
             self._keep_maps(q, c, cache)
             if cap is not None:
                 cap.record(self, q, cache)
+            if al is not None:
+                al.record(self, q, cache)
             blended = _ops.xattn_blend(q, c, cache.packed, cache.mask, self.attn2.scale)
             x, y = _fused.add_layernorm_tracked(x, self.attn2.to_out(blended), None, n3.weight, n3.bias, n3.eps)
             return self.ff(y) + x
@@ -380,6 +390,8 @@ class BasicTransformerBlock(nn.Module):
         self._keep_maps(q, c, cache)
         if cap is not None:
             cap.record(self, q, cache)
+        if al is not None:
+            al.record(self, q, cache)
         blended = _ops.xattn_blend(q, c, cache.packed, cache.mask, self.attn2.scale)
         x = self.attn2.to_out(blended) + x
         return self.ff(self.norm3(x)) + x

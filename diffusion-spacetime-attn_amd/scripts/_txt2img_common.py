@@ -9,6 +9,7 @@ ignores, accepted for compatibility). Added: --layout (JSON replacing the layout
 With torch.distributed.run the prompts are sharded round-robin over the ranks (one GPU each).
 """
 import argparse
+import importlib.util
 import os
 import sys
 
@@ -80,7 +81,18 @@ def build_parser(default_dataset):
                         "graph replay): <outdir>/attn/<prompt index>.npz, one PNG overlay per object, and the in-disc mass per object")
     p.add_argument("--attn_res", type=int, choices=[8, 16, 32, 64], default=16,
                    help="side of the transformer level whose blocks are captured (16 = the C = 1280 level of a 512 x 512 image)")
+    p.add_argument("--attn_loss", type=_positive_float, default=None, metavar="LAMBDA",
+                   help="add LAMBDA x the attention-layout loss (sta.attnloss: (1 - in-disc share of each object's token maps)^2, recorded "
+                        "at --attn_res inside the tracked UNet calls) to the loss of --opt_epochs > 1; without --clip it is the only loss "
+                        "and the tracked epochs neither need CLIP weights nor decode")
     return p
+
+
+def _positive_float(text):
+    value = float(text)
+    if not value > 0:
+        raise argparse.ArgumentTypeError("must be > 0, got %s" % text)
+    return value
 
 
 def attn_levels(opt):
@@ -89,11 +101,17 @@ def attn_levels(opt):
 
 
 def check_attn_option(opt):
-    """--attn_maps: refusals that need no GPU."""
-    if not opt.attn_maps:
+    """--attn_maps / --attn_loss: refusals that need no GPU."""
+    if opt.attn_loss is not None and opt.opt_epochs <= 1:
+        raise SystemExit("--attn_loss needs --opt_epochs > 1: with %d no epoch is tracked and nothing would be optimised" % opt.opt_epochs)
+    if opt.opt_epochs > 1 and opt.clip is None and opt.attn_loss is None and importlib.util.find_spec("clip") is None:
+        raise SystemExit("--opt_epochs %d needs a loss: --clip (the fidelity loss needs a CLIP model; the OpenAI `clip` package of the "
+                         "default is not installed) and / or --attn_loss LAMBDA (the attention-layout loss, which needs no other model), "
+                         "or --opt_epochs 0 for fixed blend weights" % opt.opt_epochs)
+    if not opt.attn_maps and opt.attn_loss is None:
         return
     if opt.H != opt.W or opt.H % (8 * opt.f):
-        raise SystemExit("--attn_maps needs a square image whose latent side is a multiple of 8 (got %d x %d, --f %d)" % (opt.H, opt.W, opt.f))
+        raise SystemExit("--attn_maps / --attn_loss need a square image whose latent side is a multiple of 8 (got %d x %d, --f %d)" % (opt.H, opt.W, opt.f))
     if opt.attn_res not in attn_levels(opt):
         raise SystemExit("--attn_res %d: no transformer level of a %d x %d image has that side (levels: %s)"
                          % (opt.attn_res, opt.H, opt.W, ", ".join(str(v) for v in attn_levels(opt))))
@@ -204,7 +222,9 @@ def run(kind, default_dataset):
         loss_tokenize = loss_tokenizer(opt)
         check_loss_texts(loss_tokenize, [(p, list((datasets.layout_for(layouts, p, i) or {}).keys())) for i, p in enumerate(prompts)])
     loss_model = None
-    if opt.opt_epochs > 1:        # the sampler evaluates the loss only when an epoch is tracked (opt_epochs > 1); fail here, not after the first 51-call trajectory
+    if opt.opt_epochs > 1 and (opt.clip is not None or opt.attn_loss is None):
+        # the sampler evaluates the loss only when an epoch is tracked (opt_epochs > 1); fail here, not after the first 51-call trajectory
+        # (--attn_loss without --clip: the attention-layout loss alone, no CLIP model is looked for)
         from ldm.models.diffusion.plms import DCLIPLoss, load_clip_model
         if opt.clip == "synthetic":
             from sta.synth import SyntheticCLIP
@@ -231,14 +251,19 @@ def run(kind, default_dataset):
         from sta import mxfp8
         n, before, after = mxfp8.convert_transformer_linears_mx_(model.model.diffusion_model)
         print("[rank %d] %d Linear layers -> MXFP8: %.2f GB -> %.2f GB" % (rank, n, before / 1e9, after / 1e9))
-    capture = None
-    if opt.attn_maps:
+    capture = attn_loss = None
+    if opt.attn_maps or opt.attn_loss is not None:
         from sta import attnmaps
         # name tokens are located with the text encoder's own tokenizer; the synthetic embedder has none (whitespace stand-in)
         tok = getattr(model.cond_stage_model, "tokenizer", None)
-        capture = attnmaps.AttnCapture(model.model.diffusion_model, resolution=opt.attn_res,
-                                       tokenize=None if tok is None else attnmaps.content_tokenizer(tok))
-    sampler = sampler_class(sampler_name)(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, attn_capture=capture)
+        tokenize = None if tok is None else attnmaps.content_tokenizer(tok)
+    if opt.attn_maps:
+        capture = attnmaps.AttnCapture(model.model.diffusion_model, resolution=opt.attn_res, tokenize=tokenize)
+    if opt.attn_loss is not None:
+        from sta import attnloss
+        attn_loss = attnloss.AttnLayoutLoss(model.model.diffusion_model, resolution=opt.attn_res, tokenize=tokenize)
+    sampler = sampler_class(sampler_name)(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, attn_capture=capture,
+                                          attn_loss=attn_loss, attn_loss_weight=opt.attn_loss if attn_loss is not None else 1.0)
     os.makedirs(opt.outdir, exist_ok=True)
 
     seed = 1                                                            # txt2img-gpt.py:304

@@ -5,6 +5,9 @@ that worked is visible in the cross-attention itself, without any other model: t
 name tokens — inside the global prompt (context 1) and inside its own local prompt (context 2 + i).
 
   token_maps            sta_xattn_token_maps (csrc/sta_xattn.hip): R weighted key sums per pixel, head mean, one launch
+  token_maps_backward   sta_xattn_token_maps_bwd (csrc/sta_xattn_maps_bwd.hip): the gradient of the maps w.r.t. q, one launch
+  token_maps_tracked    the differentiable readout (TokenMapsFn: forward = the launch above, backward = that one) — what
+                        sta.attnloss builds the attention-layout loss on
   token_maps_reference  the same formula in plain torch on unpacked keys — the oracle of the GPU tests and what host-logic tests
                         on a CPU run (the product path has no CPU fall-back: a CPU tensor with a real packed image raises)
   token_weights         which keys a readout weighs: the positions of an object's name tokens in a tokenised prompt
@@ -101,6 +104,66 @@ def token_maps(q, packed, sel_ctx, w, scale, out=None, accumulate=False):
                                                 out.data_ptr(), I, N, C, packed.heads, M, packed.n_ctx - 2, R, float(scale),
                                                 1 if accumulate else 0, _ops._dtype_code(q), _ops._stream(q)), "sta_xattn_token_maps")
     return out
+
+
+def token_maps_backward(q, packed, sel_ctx, w, dmaps, scale, out=None):
+    """dq [2 I, N, C] (q's dtype) of token_maps(accumulate=False) for the upstream dmaps [I, R, N] fp32; arguments as token_maps.
+    `out` given: overwritten completely (a q row no readout names comes back zero). Only q has a gradient: the keys, the key
+    weights and the text embeddings are constants of the optimisation."""
+    I = packed.n_img
+    if q.dim() != 3 or q.shape[0] != 2 * I:
+        raise ValueError("q must be [2 * n_img, N, C] with n_img=%d, got %s" % (I, tuple(q.shape)))
+    N, C = q.shape[1], q.shape[2]
+    if C != packed.C:
+        raise ValueError("q has C=%d but K/V were packed with C=%d" % (C, packed.C))
+    sel = _check_sel(sel_ctx, packed.n_ctx)
+    R, M = len(sel), packed.M
+    if not q.is_cuda:
+        raise RuntimeError("token_maps_backward needs CUDA/HIP tensors (there is no CPU path)")
+    if q.dtype != packed.dtype:
+        raise TypeError("q is %s but K/V were packed as %s" % (q.dtype, packed.dtype))
+    w = _expand_w(w, I, R, M, q.device)
+    if tuple(dmaps.shape) != (I, R, N) or dmaps.device != q.device:
+        raise ValueError("dmaps must be [%d, %d, %d] on %s, got %s" % (I, R, N, q.device, tuple(dmaps.shape)))
+    dmaps = dmaps.to(torch.float32).contiguous()
+    if out is None:
+        out = torch.empty((2 * I, N, C), dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (2 * I, N, C) or out.dtype != q.dtype or not out.is_contiguous() or out.device != q.device:
+        raise ValueError("out must be a contiguous %s [%d, %d, %d] on %s" % (q.dtype, 2 * I, N, C, q.device))
+    q = q.contiguous()
+    sel_arr = (ctypes.c_int32 * R)(*sel)
+    _lib.check(_lib.load().sta_xattn_token_maps_bwd(q.data_ptr(), packed.buf.data_ptr(), ctypes.cast(sel_arr, ctypes.c_void_p), w.data_ptr(),
+                                                    dmaps.data_ptr(), out.data_ptr(), I, N, C, packed.heads, M, packed.n_ctx - 2, R,
+                                                    float(scale), _ops._dtype_code(q), _ops._stream(q)), "sta_xattn_token_maps_bwd")
+    return out
+
+
+class TokenMapsFn(torch.autograd.Function):
+    """maps = token_maps(q, ...) (accumulate = 0) under autograd; backward = sta_xattn_token_maps_bwd. Only q gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, q, packed, sel_ctx, w, scale):
+        ctx.packed, ctx.sel, ctx.scale = packed, list(sel_ctx), float(scale)
+        ctx.save_for_backward(q, w)
+        return token_maps(q, packed, sel_ctx, w, scale)
+
+    @staticmethod
+    def backward(ctx, dmaps):
+        q, w = ctx.saved_tensors
+        return token_maps_backward(q, ctx.packed, ctx.sel, w, dmaps, ctx.scale), None, None, None, None
+
+
+def token_maps_tracked(q, packed, sel_ctx, w, scale):
+    """token_maps as a differentiable function of q -> [I, R, N] fp32. GPU: TokenMapsFn (both directions are HIP launches). CPU
+    tensors with the host-logic stand-in (packed.k: tests/cpu_backend.py) run token_maps_reference under autograd; a CPU tensor with
+    a real packed image raises, as token_maps does."""
+    if q.is_cuda:
+        I = packed.n_img
+        sel = _check_sel(sel_ctx, packed.n_ctx)
+        return TokenMapsFn.apply(q, packed, sel, _expand_w(w, I, len(sel), packed.M, q.device), scale)
+    if not hasattr(packed, "k"):
+        raise RuntimeError("token_maps needs CUDA/HIP tensors (there is no CPU path)")
+    return token_maps_reference(q, packed.k, sel_ctx, w, packed.heads, scale).to(torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -18,6 +18,10 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(REPO_ROOT, "include")
 LIB_PATH = os.path.join(CSRC, "libsta_xattn.so")
 SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip", "sta_xattn_proj.hip", "sta_xattn_proj3.hip", "sta_rowgemm.hip", "sta_ffgemm.hip", "sta_lnqkv.hip", "sta_conv.hip", "sta_gemm.hip", "sta_selfattn.hip", "sta_selfattn_bwd.hip", "sta_unet.hip", "sta_unet_bwd.hip", "sta_fp8.hip", "sta_mxfp8.hip", "sta_sampler.hip", "sta_encode.hip", "sta_clip.hip", "sta_inpaint.hip")]
+# csrc/*.hip files that are not translation units of their own: each is #included at the end of the source named here and so
+# shares its flags (-ffinite-math-only) and its pass through the hazard lint. sta_xattn_maps_bwd.hip (sta_xattn_token_maps_bwd) is the
+# backward of the token-map readout and is built with the cross-attention backward.
+INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip"}
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -50,6 +54,7 @@ SYMBOLS = {
     "sta_xattn_pack_kv": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sta_xattn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "sta_xattn_token_maps": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    "sta_xattn_token_maps_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "sta_xattn_fwd_proj_supported": (_i, [_i, _i, _i, _i]),
     "sta_xattn_fwd_proj_locals_from_l2": (_i, [_i, _i, _i, _i]),
     "sta_xattn_packed_wq_bytes": (_sz, [_i, _i]),
@@ -134,7 +139,7 @@ def _stale():
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = SOURCES + [os.path.join(_HERE, "isa_lint.py")] + glob.glob(os.path.join(INCLUDE, "*.h")) + glob.glob(os.path.join(CSRC, "*.h"))
+    deps = SOURCES + [os.path.join(CSRC, n) for n in INCLUDED_SOURCES] + [os.path.join(_HERE, "isa_lint.py")] + glob.glob(os.path.join(INCLUDE, "*.h")) + glob.glob(os.path.join(CSRC, "*.h"))
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 

@@ -258,6 +258,24 @@ int sta_xattn_token_maps(const void* q, const void* packed, const int32_t* sel_c
                          int n_img, int N, int C, int heads, int M, int K, int R, float scale, int accumulate,
                          int dtype, void* stream);
 
+/*
+ * Backward of sta_xattn_token_maps (accumulate = 0) w.r.t. q — what makes the readout a training signal. With
+ * P_h = softmax_m(scale q_h[p] . K_{c,h}[m]) and o_{r,h}[p] = sum_m w_r[m] P_h[p][m]:
+ *   dS_h[p][m] = (1 / heads) P_h[p][m] sum_{r : c_r = c} dmaps[r][p] (w_r[m] - o_{r,h}[p])
+ *   dq_h[p]    = scale sum_c sum_m dS_h[p][m] K_{c,h}[m]        (c over the contexts that q row attends)
+ * No gradient for K, w or the text embeddings (constants of the optimisation, as in sta_xattn_bwd). One launch, no
+ * workspace, no atomics: every dq element has one writer and one summation order (bit-reproducible, independent of n_img).
+ *   q, packed, sel_ctx (HOST memory, read before the call returns), w : as sta_xattn_token_maps
+ *   dmaps : [n_img][R][N] fp32 device — gradient w.r.t. the non-accumulated map
+ *   dq    : [n_img][2][N][C] dtype, 16-byte aligned, OVERWRITTEN completely: a row no readout names is zero (row 0 whenever
+ *           context 0 is not selected)
+ * Shapes and refusals as sta_xattn_token_maps.
+ */
+int sta_xattn_token_maps_bwd(const void* q, const void* packed, const int32_t* sel_ctx, const float* w,
+                             const float* dmaps, void* dq,
+                             int n_img, int N, int C, int heads, int M, int K, int R, float scale,
+                             int dtype, void* stream);
+
 /* Bytes of fp32 workspace sta_xattn_bwd needs for the given shape (deterministic dcoef reduce). */
 size_t sta_xattn_bwd_workspace_bytes(int n_img, int N, int heads, int K);
 
