@@ -153,3 +153,6 @@ int sta_sampler_step_bwd(const float* g_xn, const float* g_m, float* g_x, void* 
 }
 
 }  // extern "C"
+
+// the latent update of attention-guided sampling (sta_latent_guide): same helpers, same flags, same pass through the hazard lint
+#include "sta_guide.hip"

@@ -215,8 +215,11 @@ class _AttnInject:
 class PLMSSampler(object):
     def __init__(self, model, schedule="linear", loss_model=None, opt_epochs=3, lr=0.005, weight_init=5.0,
                  local_loss_weight=5.0, use_graph=True, save_images=True, outdir="result_outputs/", loss_scale=None, keep_calls=None,
-                 batched_loss=True, attn_capture=None, attn_loss=None, attn_loss_weight=1.0, **kwargs):
-        """`attn_loss`: a sta.attnloss.AttnLayoutLoss. Tracked epochs then minimise [the fidelity loss if `loss_model` is given] +
+                 batched_loss=True, attn_capture=None, attn_loss=None, attn_loss_weight=1.0, latent_guidance=None, **kwargs):
+        """`latent_guidance`: a sta.guidance.AttnGuidance. In every trajectory that runs WITHOUT autograd (the fixed-weight one, the kept
+        last epoch) its first `steps` UNet calls are each preceded by its latent updates (eager evaluations; the ordinary calls run as
+        before, graph replay included); what they saw is left in `last_guidance`. Tracked epochs are never guided. None: nothing changes.
+        `attn_loss`: a sta.attnloss.AttnLayoutLoss. Tracked epochs then minimise [the fidelity loss if `loss_model` is given] +
         attn_loss_weight x the attention-layout loss, recorded inside the tracked UNet calls; with `loss_model=None` they decode
         nothing. The last epoch is untouched (never tracked: the loss records nothing there). None: nothing changes.
         `attn_capture`: a sta.attnmaps.AttnCapture. The trajectory whose image is kept (the last epoch's, never tracked) then runs
@@ -245,6 +248,7 @@ class PLMSSampler(object):
         self.attn_capture, self.last_attn = attn_capture, None
         self.attn_loss, self.attn_loss_weight = attn_loss, float(attn_loss_weight)
         self._attn_inject = None          # _AttnInject while a tracked epoch with an attention loss runs
+        self.latent_guidance, self.last_guidance = latent_guidance, None
         self._graphs = None
         self._call_key = None             # (latent shape, object count) of the trajectory being sampled: keys the measured activation size
 
@@ -358,6 +362,9 @@ class PLMSSampler(object):
             cap = self.attn_capture if last else None
             if cap is not None:
                 cap.begin(boxes, texts=texts, names=names)
+            lg = self.latent_guidance if not track else None
+            if lg is not None:
+                lg.begin(boxes, texts=texts, names=names)
             al = self.attn_loss if track else None
             decode = not track or self.clip_loss_model is not None or al is None      # tracked with the attention loss alone: no decode
             while True:
@@ -413,6 +420,8 @@ class PLMSSampler(object):
                               W=(W if batched else W[0]).detach().clone())
                 if cap is not None:
                     self.last_attn = cap.result()
+                if lg is not None:
+                    self.last_guidance = lg.result()
                 if self.save_images and x_img is not None:
                     for i in range(b):
                         self._save(x_img[i], epochs - 1, seed, pidx[i], index=i)
@@ -504,11 +513,14 @@ class PLMSSampler(object):
         if call_recompute and torch.is_grad_enabled():
             self.last_kept_calls = keep
         eps_fn = self._make_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute, keep_last=keep, n_calls=S + 1)
+        guide = self._guide(eps_fn)
         old_eps = []
         for i, step in enumerate(time_range):
             index = S - i - 1
             ts = torch.full((b,), int(step), device=device, dtype=torch.long)
             ts_next = torch.full((b,), int(time_range[min(i + 1, S - 1)]), device=device, dtype=torch.long)
+            if guide is not None and i < guide.steps:          # before the step's first evaluation; old_eps stays as it is
+                img, _ = guide.update(img, None, ts, W[..., i], i, float(self.ddim_alphas[index]))
             img, _, e_t = self._plms_update(eps_fn, img, ts, ts_next, index, old_eps, W[..., i])
             old_eps.append(e_t)
             if len(old_eps) >= 4:
@@ -581,7 +593,16 @@ class PLMSSampler(object):
             out = out.reshape(b, 2, *out.shape[1:])
             e_u, e_c = out[:, 0], out[:, 1]
             return e_u + scale * (e_c - e_u)
+        eps.eager_call = lambda x_, t_, c_: unet(self.model.apply_model_extra, x_, t_, c_)      # sta.guidance: never the graph
         return eps
+
+    def _guide(self, eps_fn):
+        """The latent guidance of this trajectory, bound to its eager UNet call, or None: trajectories under autograd (tracked epochs)
+        are never guided, nor are prompts without objects."""
+        lg = self.latent_guidance
+        if lg is None or torch.is_grad_enabled() or not lg.ready:
+            return None
+        return lg.bind(eps_fn.eager_call)
 
     def _x_prev(self, x, e_t, index):
         """DDIM step with sigma = 0 (:321-338); the tables live on the host as Python floats."""
@@ -751,9 +772,15 @@ class SolverSamplerBase(PLMSSampler):
             x, xin = solver.latent_blend(x, self._blend(start, x), dtype=wdtype, want_xin=fast)
         elif fast:
             xin = self._xin0 if self._xin0 is not None else solver._pair(img).to(wdtype)
+        guide = self._guide(eps_fn)
         for i in range(start, S):
             t_val = float(time_range[i]) if self.t_dtype.is_floating_point else int(time_range[i])
             t = torch.full((b,), t_val, device=device, dtype=self.t_dtype)
+            if guide is not None and i - start < guide.steps:
+                # after the blend of a masked trajectory (the kept region is not guided); alpha_cumprod of the call's time is alpha_t^2 in
+                # both tables; m_prev stays as it is
+                x, xin = guide.update(x, xin, t, W[..., i], i - start, float(self.tables["alpha_t"][i]) ** 2,
+                                      self._inpaint["keep"] if masked else None)
             out = eps_fn(x if xin is None else xin, t, W[..., i])
             c = self._coef(i, scale)
             noise = self._noise(i - start, x) if c.c_n else None           # the eta draw of call i, then the blend draw of call i + 1

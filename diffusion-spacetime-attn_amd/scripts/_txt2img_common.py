@@ -5,7 +5,9 @@ Kept from the reference CLI (txt2img-gpt.py:105-247): --plms / --dpm_solver / ne
 --ddim_eta --fixed_code --config --ckpt --precision --outdir --seed --process_id (+ the flags it parses and
 ignores, accepted for compatibility). Added: --layout (JSON replacing the layout-predictor call),
 --dataset (path override), --opt_epochs (0 = fixed weights), --limit/--start, --dtype, --synthetic,
---clip (the fidelity-loss model; checked BEFORE sampling), --clip_tokenizer (vocabulary of the text encoder).
+--clip (the fidelity-loss model; checked BEFORE sampling), --clip_tokenizer (vocabulary of the text encoder),
+--attn_guidance ETA / --attn_guidance_steps / --attn_guidance_iters (attention-guided latent updates, sta.guidance; shared with
+img2img.py and inpaint.py through add_guidance_arguments / check_guidance_option / make_guidance / report_guidance).
 With torch.distributed.run the prompts are sharded round-robin over the ranks (one GPU each).
 """
 import argparse
@@ -85,7 +87,35 @@ def build_parser(default_dataset):
                    help="add LAMBDA x the attention-layout loss (sta.attnloss: (1 - in-disc share of each object's token maps)^2, recorded "
                         "at --attn_res inside the tracked UNet calls) to the loss of --opt_epochs > 1; without --clip it is the only loss "
                         "and the tracked epochs neither need CLIP weights nor decode")
+    add_guidance_arguments(p)
     return p
+
+
+def add_guidance_arguments(p, attn_res=False):
+    """The flags of attention-guided sampling; attn_res=True adds --attn_res for a parser that does not have it yet."""
+    p.add_argument("--attn_guidance", type=_positive_float, default=None, metavar="ETA",
+                   help="step the latent down the gradient of the attention-layout energy (sta.guidance) before each of the first "
+                        "--attn_guidance_steps UNet calls of the kept trajectory: x <- x - ETA (1 - alphas_cumprod_t) g / rms(g), read at "
+                        "--attn_res on the encoder side of the UNet; needs no epochs and no CLIP; prompts without objects are not guided")
+    p.add_argument("--attn_guidance_steps", type=_non_negative_int, default=10, metavar="N", help="guided UNet calls per trajectory")
+    p.add_argument("--attn_guidance_iters", type=_positive_int, default=1, metavar="N", help="updates before each guided call")
+    if attn_res:
+        p.add_argument("--attn_res", type=int, choices=[8, 16, 32, 64], default=16,
+                       help="side of the transformer level whose blocks feed the guidance (16 = the C = 1280 level of a 512 x 512 image)")
+
+
+def _positive_int(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError("must be >= 1, got %s" % text)
+    return value
+
+
+def _non_negative_int(text):
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError("must be >= 0, got %s" % text)
+    return value
 
 
 def _positive_float(text):
@@ -108,13 +138,50 @@ def check_attn_option(opt):
         raise SystemExit("--opt_epochs %d needs a loss: --clip (the fidelity loss needs a CLIP model; the OpenAI `clip` package of the "
                          "default is not installed) and / or --attn_loss LAMBDA (the attention-layout loss, which needs no other model), "
                          "or --opt_epochs 0 for fixed blend weights" % opt.opt_epochs)
-    if not opt.attn_maps and opt.attn_loss is None:
+    if not opt.attn_maps and opt.attn_loss is None and opt.attn_guidance is None:
         return
     if opt.H != opt.W or opt.H % (8 * opt.f):
-        raise SystemExit("--attn_maps / --attn_loss need a square image whose latent side is a multiple of 8 (got %d x %d, --f %d)" % (opt.H, opt.W, opt.f))
+        raise SystemExit("--attn_maps / --attn_loss / --attn_guidance need a square image whose latent side is a multiple of 8 (got %d x %d, --f %d)" % (opt.H, opt.W, opt.f))
     if opt.attn_res not in attn_levels(opt):
         raise SystemExit("--attn_res %d: no transformer level of a %d x %d image has that side (levels: %s)"
                          % (opt.attn_res, opt.H, opt.W, ", ".join(str(v) for v in attn_levels(opt))))
+
+
+def check_guidance_option(opt, side=None):
+    """--attn_guidance of the entry points that read their image size from a file (img2img.py, inpaint.py): the same refusals as
+    check_attn_option, against the square image of `side` pixels once it is known."""
+    if opt.attn_guidance is None or side is None:
+        return
+    levels = [side // opt.f // s for s in (1, 2, 4, 8)]
+    if side % (8 * opt.f):
+        raise SystemExit("--attn_guidance needs a square image whose latent side is a multiple of 8 (got %d, --f %d)" % (side, opt.f))
+    if opt.attn_res not in levels:
+        raise SystemExit("--attn_res %d: no transformer level of a %d x %d image has that side (levels: %s)"
+                         % (opt.attn_res, side, side, ", ".join(str(v) for v in levels)))
+
+
+def make_guidance(opt, model):
+    """The sta.guidance.AttnGuidance of --attn_guidance, or None."""
+    if opt.attn_guidance is None:
+        return None
+    from sta import attnmaps, guidance
+    tok = getattr(model.cond_stage_model, "tokenizer", None)
+    return guidance.AttnGuidance(model.model.diffusion_model, resolution=opt.attn_res, scale=opt.attn_guidance, steps=opt.attn_guidance_steps,
+                                 iters=opt.attn_guidance_iters, tokenize=None if tok is None else attnmaps.content_tokenizer(tok))
+
+
+def report_guidance(sampler, indices, tag=""):
+    """After sampling: per prompt the energy before the first and before the last update (with one update per call the last figure is
+    the energy the last guided call started from), and the skipped updates."""
+    res = getattr(sampler, "last_guidance", None)
+    if getattr(sampler, "latent_guidance", None) is None:
+        return
+    if res is None:
+        print("%sprompts %s: no objects (or no guided call), not guided" % (tag, list(indices)))
+        return
+    for j, i in enumerate(indices):
+        print("%sprompt %d: attention-layout energy %.4f before the first update, %.4f before the last of %d (%d skipped in the batch)"
+              % (tag, i, res["energy"][0, j].item(), res["energy"][-1, j].item(), len(res["calls"]), res["skipped"]))
 
 
 def builtin_clip(opt):
@@ -263,7 +330,8 @@ def run(kind, default_dataset):
         from sta import attnloss
         attn_loss = attnloss.AttnLayoutLoss(model.model.diffusion_model, resolution=opt.attn_res, tokenize=tokenize)
     sampler = sampler_class(sampler_name)(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, attn_capture=capture,
-                                          attn_loss=attn_loss, attn_loss_weight=opt.attn_loss if attn_loss is not None else 1.0)
+                                          attn_loss=attn_loss, attn_loss_weight=opt.attn_loss if attn_loss is not None else 1.0,
+                                          latent_guidance=make_guidance(opt, model))
     os.makedirs(opt.outdir, exist_ok=True)
 
     seed = 1                                                            # txt2img-gpt.py:304
@@ -292,6 +360,7 @@ def run(kind, default_dataset):
                        text_index=0, curr_text=prompt, bboxs_curr=[layout[n] for n in names], seed=seed,
                        prompt_idx=prompt_idx, object_names=names, local_conditionings=local_c)
         report_attn([(prompt_idx, prompt, layout)])
+        report_guidance(sampler, [prompt_idx], "[rank %d] " % rank)
 
     def run_group(group):
         """Prompts with the same number of objects share one CFG batch; every image keeps the reference's
@@ -307,6 +376,7 @@ def run(kind, default_dataset):
                              x_T=x1.expand(len(group), -1, -1, -1), unconditional_guidance_scale=opt.scale, eta=eta,
                              seed=seed, prompt_indices=[i for i, _, _ in group])
         report_attn(group)
+        report_guidance(sampler, [i for i, _, _ in group], "[rank %d] " % rank)
 
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}) for i, p in mine]
     if opt.batch_prompts <= 1:

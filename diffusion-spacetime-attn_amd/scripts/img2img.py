@@ -65,6 +65,7 @@ def build_parser():
     p.add_argument("--clip_tokenizer", type=str, default=None)
     p.add_argument("--synthetic", action="store_true", help="synthetic weights/text embeddings when no checkpoint is available")
     p.add_argument("--batch_prompts", type=int, default=1)
+    _txt2img_common.add_guidance_arguments(p, attn_res=True)
     return p
 
 
@@ -161,6 +162,7 @@ def main(argv=None):
     images = {p: load_img(p) for p in dict.fromkeys(paths)}
     size = check_images(images)
     _txt2img_common.check_clip_option(opt, (size, size))
+    _txt2img_common.check_guidance_option(opt, size)
     from sta import datasets
     layouts = datasets.load_layouts(opt.layout) if opt.layout else None
     loss_tokenize = None
@@ -195,7 +197,8 @@ def main(argv=None):
                         real_text_encoder=ckpt is not None, with_encoder=True)
     vae = model.first_stage_model
     vae.encoder.to(memory_format=torch.channels_last)            # NHWC encoder: its convolutions on the HIP kernels
-    sampler = DDIMSampler(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, outdir=opt.outdir, save_images=not opt.skip_save)
+    sampler = DDIMSampler(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, outdir=opt.outdir, save_images=not opt.skip_save,
+                          latent_guidance=_txt2img_common.make_guidance(opt, model))
     sampler.make_schedule(opt.ddim_steps, ddim_eta=opt.ddim_eta, verbose=False)
     os.makedirs(opt.outdir, exist_ok=True)
     lat = size // opt.f
@@ -236,6 +239,7 @@ def main(argv=None):
                                  [list(l.keys()) for _, _, l, _ in group], [c[2] for c in conds], t_enc,
                                  curr_texts=[p for _, p, _, _ in group], unconditional_guidance_scale=opt.scale, seed=opt.seed,
                                  prompt_indices=[i for i, _, _, _ in group], xin=xin)
+        _txt2img_common.report_guidance(sampler, [i for i, _, _, _ in group])
 
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}, paths[i]) for i, p in enumerate(prompts)]
     by_k = {}

@@ -121,6 +121,7 @@ def main(argv=None):
     images = {p: _i2i.load_img(p) for p in dict.fromkeys(paths)}
     size = _i2i.check_images(images)
     _txt2img_common.check_clip_option(opt, (size, size))
+    _txt2img_common.check_guidance_option(opt, size)
     from sta import datasets
     layouts = datasets.load_layouts(opt.layout) if opt.layout else None
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}, paths[i]) for i, p in enumerate(prompts)]
@@ -164,7 +165,8 @@ def main(argv=None):
     vae = model.first_stage_model
     vae.encoder.to(memory_format=torch.channels_last)            # NHWC encoder: its convolutions on the HIP kernels
     cls = DPMSolverSampler if opt.dpm_solver else DDIMSampler
-    sampler = cls(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, outdir=opt.outdir, save_images=not opt.skip_save)
+    sampler = cls(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, outdir=opt.outdir, save_images=not opt.skip_save,
+                  latent_guidance=_txt2img_common.make_guidance(opt, model))
     sampler.make_schedule(opt.ddim_steps, ddim_eta=opt.ddim_eta, verbose=False)
     encoder = sampler                                            # the fused encode step lives on the DDIM sampler (its tables)
     if opt.dpm_solver:
@@ -222,6 +224,7 @@ def main(argv=None):
                 sampler.sample_batch(opt.ddim_steps, list(shape[1:]), *args, x_T=n_enc, eta=opt.ddim_eta, **kw)
             else:
                 sampler.decode_batch(x, *args, t_enc, **kw)
+        _txt2img_common.report_guidance(sampler, [i for i, _, _, _ in group])
 
     by_k = {}
     for it in items:

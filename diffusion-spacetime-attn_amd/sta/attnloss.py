@@ -33,6 +33,11 @@ def layout_energy(maps, disc, valid):
     return e.sum(-1) / valid.sum(-1).clamp(min=1).to(maps.dtype)
 
 
+class _EarlyExit(Exception):
+    """Raised by record() right behind the q of the block named in `stop_after`: the rest of that UNet call is not needed
+    (sta.guidance catches it; nothing else sets `stop_after`)."""
+
+
 class AttnLayoutLoss:
     """Collector of the attention-layout loss over one tracked trajectory.
 
@@ -50,10 +55,15 @@ class AttnLayoutLoss:
 
     Recompute mode `all`: a side value cannot leave a checkpointed forward, so while a loss is attached and autograd is on a
     recording block runs its _forward directly instead of through its own checkpoint(...) — only the few blocks of one resolution
-    keep their activations; every other block recomputes as before."""
+    keep their activations; every other block recomputes as before.
 
-    def __init__(self, unet, resolution=16, tokenize=None, M=77):
+    `block_filter` (None = every block, today's behaviour): a predicate on a BasicTransformerBlock; only the blocks it accepts are
+    attached, the others never see the collector. `stop_after` (None = never): a block behind whose record() the call is abandoned
+    with _EarlyExit — for a caller that needs the energy of the blocks up to that one and nothing of the call's output."""
+
+    def __init__(self, unet, resolution=16, tokenize=None, M=77, block_filter=None):
         self.unet, self.resolution, self.tokenize, self.M = unet, int(resolution), tokenize, int(M)
+        self.block_filter, self.stop_after = block_filter, None
         self.recording = False
         self._explicit = None
         self._blocks = []
@@ -100,7 +110,8 @@ class AttnLayoutLoss:
         if self.centres is None:
             raise RuntimeError("AttnLayoutLoss has no readouts yet: call begin(...) before entering it")
         from ldm.modules.attention import BasicTransformerBlock
-        self._blocks = [m for m in self.unet.modules() if isinstance(m, BasicTransformerBlock)]
+        self._blocks = [m for m in self.unet.modules() if isinstance(m, BasicTransformerBlock)
+                        and (self.block_filter is None or self.block_filter(m))]
         for blk in self._blocks:
             blk._attn_loss = self
         self.recording = True
@@ -128,6 +139,8 @@ class AttnLayoutLoss:
         self._sum = maps if self._sum is None else self._sum + maps
         self._nblk += 1
         self.block_calls += 1
+        if block is self.stop_after:
+            raise _EarlyExit()
 
     def next_call(self):
         """Close the UNet call being recorded (the sampler announces a new one; a no-op when nothing was recorded since)."""

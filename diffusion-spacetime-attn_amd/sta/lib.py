@@ -20,8 +20,9 @@ LIB_PATH = os.path.join(CSRC, "libsta_xattn.so")
 SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip", "sta_xattn_proj.hip", "sta_xattn_proj3.hip", "sta_rowgemm.hip", "sta_ffgemm.hip", "sta_lnqkv.hip", "sta_conv.hip", "sta_gemm.hip", "sta_selfattn.hip", "sta_selfattn_bwd.hip", "sta_unet.hip", "sta_unet_bwd.hip", "sta_fp8.hip", "sta_mxfp8.hip", "sta_sampler.hip", "sta_encode.hip", "sta_clip.hip", "sta_inpaint.hip")]
 # csrc/*.hip files that are not translation units of their own: each is #included at the end of the source named here and so
 # shares its flags (-ffinite-math-only) and its pass through the hazard lint. sta_xattn_maps_bwd.hip (sta_xattn_token_maps_bwd) is the
-# backward of the token-map readout and is built with the cross-attention backward.
-INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip"}
+# backward of the token-map readout and is built with the cross-attention backward; sta_guide.hip (sta_latent_guide) is the latent update of
+# attention-guided sampling and is built with the sampler step, whose helpers it uses (no -ffinite-math-only there: it tests for Inf / NaN).
+INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip"}
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -128,6 +129,7 @@ SYMBOLS = {
     "sta_latent_blend": (_i, [_vp] * 6 + [_l, _l, _l, _f, _f, _i, _vp]),
     "sta_image_composite": (_i, [_vp] * 4 + [_l, _l, _i, _vp]),
     "sta_image_composite_bwd": (_i, [_vp] * 4 + [_l, _l, _i, _vp]),
+    "sta_latent_guide": (_i, [_vp] * 7 + [_l, _l, _l, _i, _f, _i, _vp]),
 }
 
 

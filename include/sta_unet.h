@@ -312,6 +312,25 @@ int sta_image_composite(const void* dec, const float* orig, const float* keep_px
 int sta_image_composite_bwd(const void* g, const void* dec, const float* keep_px, void* g_dec, long b, long hw, int dtype, void* stream);
 
 /*
+ * Attention-guided sampling (csrc/sta_guide.hip): the latent steps down the gradient of the attention-layout energy before a UNet call.
+ * The UNet's input is the 16-bit CFG pair (rows 2i, 2i + 1 = the same latent), so autograd hands the gradient back as a pair as well.
+ *   g: [2b][n] dtype, the gradient w.r.t. the input pair;  x, x_out: [b][n] fp32;  keep: [b][hw] fp32 or NULL (inpainting: the kept region
+ *   is not guided; NULL = factor 1), broadcast over the n / hw channels;  step: [b] fp32;  xin: [2b][n] dtype or NULL;  stats: [b] fp32 or NULL.
+ * Per image i, fp32 arithmetic:
+ *     d_j   = (g[2i][j] + g[2i+1][j]) (1 - keep[i][j mod hw])
+ *     rms_i = sqrt(sum_j d_j^2 / n)
+ *     s_i   = normalize ? step[i] / rms_i : step[i] inv_scale            (inv_scale undoes the loss scale of a 16-bit backward)
+ *     x_out = x - s_i d  if rms_i is finite and > 0, else x_out = x bit for bit (the image is skipped: a zero or non-finite gradient)
+ *     xin   = (x_out, x_out) rounded once to dtype, rows 2i and 2i + 1;  stats[i] = rms_i (non-finite or 0 marks a skipped image)
+ * One launch, no atomics: every workgroup of an image reduces the whole image's gradient in the same fixed order, so the result is
+ * bit-reproducible from launch to launch and an image's outputs depend on that image's inputs alone.
+ * Rules (STA_E_ARG with text, nothing launched): g, x, step, x_out non-NULL; n % 8 == 0, hw % 8 == 0, n % hw == 0 (also with keep == NULL);
+ * g, x, keep, x_out, xin 16-byte aligned (step, stats: 4-byte); no output may overlap an input or another output.
+ */
+int sta_latent_guide(const void* g, const float* x, const float* keep, const float* step, float* x_out, void* xin, float* stats, long b, long n,
+                     long hw, int normalize, float inv_scale, int dtype, void* stream);
+
+/*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
  * of its patch-embedding GEMM, and the gradient of the image from the gradient of those rows.
  *   img:   [B][3][H][W] fp32 in [0, 1] (the clamped decoder output);
