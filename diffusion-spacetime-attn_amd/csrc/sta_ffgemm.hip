@@ -370,3 +370,7 @@ int sta_ff_geglu_qfrag(const void* y_qfrag, const void* packed_w, const void* bi
 }
 
 }  // extern "C"
+
+// The level-1 shape (C = 640, inner = 2560) of the GEGLU projection pass is a kernel of its own in a file of its own, compiled as part
+// of this translation unit (sta/lib.py::INCLUDED_SOURCES): same flags, same pass through the hazard lint, the same ff_gelu_erf.
+#include "sta_ffgemm640.hip"

@@ -401,16 +401,25 @@ class BasicTransformerBlock(nn.Module):
         w = self.attn2.to_q.weight
         return _fused.cached_image(self, "wq", (w,), lambda: _ops.pack_wq(w, self.attn2.heads))
 
+    def _ff_c640(self, x):
+        """Level 1 (C = 640): the GEGLU projection pass of csrc/sta_ffgemm640.hip in front of the library output Linear."""
+        net = self.ff.net
+        return _fused.FF_GEGLU_C640 and isinstance(net[2], nn.Linear) and _fused.ff_geglu_c640_supported(x.shape[-1], net[0].proj.out_features // 2)
+
     def _ff_fusable(self, x):
         net = self.ff.net
         return isinstance(net[0], GEGLU) and isinstance(net[0].proj, nn.Linear) and (x.numel() // x.shape[-1]) % 16 == 0 \
-            and _fused.ff_geglu_supported(x.shape[-1], net[0].proj.out_features // 2)
+            and (_fused.ff_geglu_supported(x.shape[-1], net[0].proj.out_features // 2) or self._ff_c640(x))
 
     def _ff_tail(self, x, y, ffq):
         """x + ff(y) (attention.py:299). `ffq`: y is in query-fragment order and the GEGLU projection runs as the fused pass."""
         if not ffq:
             return self.ff(y) + x
         proj = self.ff.net[0].proj
+        if self._ff_c640(x):
+            w1 = _fused.cached_image(self, "w1", (proj.weight,), lambda: _fused.pack_geglu_c640_weight(proj.weight))
+            h = _fused.ff_geglu_c640_qfrag(y, w1, proj.bias, proj.out_features // 2)
+            return self.ff.net[2](self.ff.net[1](h)) + x
         w1 = _fused.cached_image(self, "w1", (proj.weight,), lambda: _fused.pack_geglu_weight(proj.weight))
         out = self.ff.net[2]
         if isinstance(out, nn.Linear):

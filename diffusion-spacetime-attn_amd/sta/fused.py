@@ -253,6 +253,37 @@ def ff_geglu_qfrag(y_qfrag, w_packed, bias, inner, h_frag=False):
     return h
 
 
+FF_GEGLU_C640 = True    # level 1 (C = 640): the GEGLU projection + gelu * mul as one pass (csrc/sta_ffgemm640.hip); False: library GEMM + sta_geglu
+
+
+def pack_geglu_c640_weight(weight):
+    """GEGLU proj.weight [5120, 640] -> the fragment image sta_ff_geglu_c640_qfrag streams through LDS (uint8 tensor); once per model."""
+    two_inner, C = weight.shape
+    L = lib.load()
+    n = L.sta_ff_geglu_c640_packed_w_bytes(C, two_inner // 2)
+    if n == 0 or not weight.is_cuda:
+        raise ValueError("fused GEGLU projection (c640): a CUDA weight [5120, 640]; got %s" % (tuple(weight.shape),))
+    w = weight.detach().contiguous()
+    buf = torch.empty(n, dtype=torch.uint8, device=w.device)
+    lib.check(L.sta_ff_geglu_c640_pack_w(w.data_ptr(), buf.data_ptr(), C, two_inner // 2, _DT[w.dtype], _stream()), "sta_ff_geglu_c640_pack_w")
+    return buf
+
+
+def ff_geglu_c640_supported(C, inner):
+    return bool(lib.load().sta_ff_geglu_c640_packed_w_bytes(C, inner))
+
+
+def ff_geglu_c640_qfrag(y_qfrag, w_packed, bias, inner, max_workgroups=0):
+    """ff_geglu_qfrag at C = 640, inner = 2560 (csrc/sta_ffgemm640.hip); h [.., inner] row-major. `max_workgroups` > 0 caps the
+    grid (tests: several passes per persistent workgroup at a small row count)."""
+    C = y_qfrag.shape[-1]
+    R = y_qfrag.numel() // C
+    h = torch.empty(*y_qfrag.shape[:-1], inner, dtype=y_qfrag.dtype, device=y_qfrag.device)
+    lib.check(lib.load().sta_ff_geglu_c640_qfrag(y_qfrag.data_ptr(), w_packed.data_ptr(), _ptr(bias), h.data_ptr(), R, C, inner, int(max_workgroups),
+                                                 _DT[y_qfrag.dtype], _stream()), "sta_ff_geglu_c640_qfrag")
+    return h
+
+
 def pack_ff_out_weight(weight):
     """FeedForward net[2].weight [C, inner] -> the fragment image sta_ff_out_res_hfrag streams through LDS; once per model."""
     C, inner = weight.shape

@@ -21,8 +21,9 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # csrc/*.hip files that are not translation units of their own: each is #included at the end of the source named here and so
 # shares its flags (-ffinite-math-only) and its pass through the hazard lint. sta_xattn_maps_bwd.hip (sta_xattn_token_maps_bwd) is the
 # backward of the token-map readout and is built with the cross-attention backward; sta_guide.hip (sta_latent_guide) is the latent update of
-# attention-guided sampling and is built with the sampler step, whose helpers it uses (no -ffinite-math-only there: it tests for Inf / NaN).
-INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip"}
+# attention-guided sampling and is built with the sampler step, whose helpers it uses (no -ffinite-math-only there: it tests for Inf / NaN);
+# sta_ffgemm640.hip (sta_ff_geglu_c640_*) is the level-1 GEGLU projection pass and is built with the level-0 feed-forward passes, whose GELU it uses.
+INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_ffgemm640.hip": "sta_ffgemm.hip"}
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -35,6 +36,10 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
                     "sta_selfattn_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-ffinite-math-only"],
                     "sta_xattn.hip": ["-ffinite-math-only"], "sta_xattn_bwd.hip": ["-ffinite-math-only"], "sta_xattn_proj.hip": ["-ffinite-math-only"],
                     "sta_xattn_proj3.hip": ["-ffinite-math-only"], "sta_rowgemm.hip": ["-ffinite-math-only"], "sta_ffgemm.hip": ["-ffinite-math-only"], "sta_conv.hip": ["-ffinite-math-only"], "sta_gemm.hip": ["-ffinite-math-only"]}
+
+# Kernels built to the last register of their occupancy: {translation unit: substrings of the kernel names}. build() refuses a toolchain
+# that spills one (a spilled B fragment is a scratch round trip per MFMA: the pass would be slower than the pair it replaces).
+NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_c640_qfrag_kernel",)}
 
 STA_BF16, STA_F16 = 0, 1
 STA_MX8_GEGLU, STA_MX8_MX_OUT = 1, 2
@@ -86,6 +91,9 @@ SYMBOLS = {
     "sta_ff_geglu_packed_w_bytes": (_sz, [_i, _i]),
     "sta_ff_geglu_pack_w": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sta_ff_geglu_qfrag": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp]),
+    "sta_ff_geglu_c640_packed_w_bytes": (_sz, [_i, _i]),
+    "sta_ff_geglu_c640_pack_w": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "sta_ff_geglu_c640_qfrag": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp]),
     "sta_ff_out_packed_w_bytes": (_sz, [_i, _i]),
     "sta_ff_out_pack_w": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sta_ff_out_res_hfrag": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp]),
@@ -167,6 +175,49 @@ def _run(cmd):
         raise StaLibraryError("build step failed: %s\n%s" % (" ".join(cmd), r.stdout + r.stderr))
 
 
+_META_KEYS = ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def kernel_metadata(text):
+    """{kernel name: {key: int}} from the amdhsa.kernels metadata of a device assembly text — registers, spills, scratch
+    (private segment) and static LDS (group segment) only; nothing else of the assembly is looked at."""
+    out, cur, inside = {}, None, False
+    for line in text.splitlines():
+        if line.startswith("amdhsa.kernels:"):
+            inside = True
+        elif inside and line[:1] not in (" ", ""):
+            inside = False
+        if not inside:
+            continue
+        if line.startswith("  - ."):
+            cur = {}
+            line = "    " + line[4:]
+        if cur is None or not line.startswith("    ."):
+            continue
+        key, _, val = line.strip()[1:].partition(":")
+        val = val.strip()
+        if key == "name":
+            out[val] = cur
+        elif key in _META_KEYS:
+            cur[key] = int(val)
+    return out
+
+
+def check_no_spill(src, text):
+    """The kernels NO_SPILL_KERNELS names for `src` use no scratch in `text` -> [(name, metadata)]; StaLibraryError otherwise."""
+    found = []
+    for want in NO_SPILL_KERNELS.get(os.path.basename(src), ()):
+        hits = [(n, m) for n, m in kernel_metadata(text).items() if want in n]
+        if not hits:
+            raise StaLibraryError("%s: no kernel named *%s* in the device assembly" % (src, want))
+        for n, m in hits:
+            if m.get("vgpr_spill_count", -1) != 0 or m.get("sgpr_spill_count", -1) != 0 or m.get("private_segment_fixed_size", -1) != 0:
+                raise StaLibraryError("%s: %s spills with this toolchain (%s): it is built to the last register of two waves per SIMD "
+                                      "and must not use scratch" % (src, n, ", ".join("%s=%s" % kv for kv in sorted(m.items()))))
+        found += hits
+    return found
+
+
 def _compile_checked(hipcc, base, flags, src, obj, workdir, verbose):
     """One translation unit: device code to ASSEMBLY, the hazard lint + its s_nop cure on that text (sta/isa_lint.py: the table
     measured by tools/hazard_probe.py, which knows one pair hipcc 7.2 does not pad — an MFMA accumulating into the result of an MFMA
@@ -180,6 +231,7 @@ def _compile_checked(hipcc, base, flags, src, obj, workdir, verbose):
     _run(base + flags + ["--cuda-device-only", "-S", src, "-o", stem + ".s"])
     with open(stem + ".s") as fh:
         text = fh.read()
+    check_no_spill(src, text)
     fixed, log = isa_lint.fix_text(text)
     left = isa_lint.lint_text(fixed)
     if left:

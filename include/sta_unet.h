@@ -86,6 +86,18 @@ int sta_ff_out_res_hfrag(const void* h_frag, const void* packed_w, const void* b
                          int inner, int dtype, void* stream);
 
 /*
+ * The first half of the feed-forward at SD-v1 level 1 in one pass (csrc/sta_ffgemm640.hip): sta_ff_geglu_qfrag's computation,
+ * operand orders, GELU and single rounding at C = 640, inner = 2560 (sta_ff_geglu_c640_packed_w_bytes: 0 for any other shape;
+ * the packed image differs from sta_ff_geglu_pack_w's: a sub-chunk holds one half of the reduction dimension). h leaves row-major.
+ *   bias: [2 * inner] dtype or NULL;  h: [R][inner] dtype;  R % 16 == 0, R * inner * 2 bytes < 4 GiB
+ *   max_workgroups: 0 = one persistent workgroup per CU; n > 0 caps the grid (tests: several 256-row passes per workgroup)
+ */
+size_t sta_ff_geglu_c640_packed_w_bytes(int C, int inner);
+int sta_ff_geglu_c640_pack_w(const void* w, void* packed, int C, int inner, int dtype, void* stream);
+int sta_ff_geglu_c640_qfrag(const void* y_qfrag, const void* packed_w, const void* bias, void* h, long R, int C, int inner,
+                            int max_workgroups, int dtype, void* stream);
+
+/*
  * The front end of the block's self-attention in one pass (csrc/sta_lnqkv.hip):
  *     s = x + bias;  y = LayerNorm(s) * gamma + beta;  q|k = y [Wq'; Wk]^T;  V^T = Wv y^T
  * instead of sta_add_layernorm + two library GEMMs that read y back: y never exists in HBM. bias (may be NULL) and s (may be
