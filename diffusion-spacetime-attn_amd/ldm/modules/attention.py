@@ -402,7 +402,7 @@ class BasicTransformerBlock(nn.Module):
         return _fused.cached_image(self, "wq", (w,), lambda: _ops.pack_wq(w, self.attn2.heads))
 
     def _ff_c640(self, x):
-        """Level 1 (C = 640): the GEGLU projection pass of csrc/sta_ffgemm640.hip in front of the library output Linear."""
+        """Level 1 (C = 640): the GEGLU projection pass of csrc/sta_ffgemm.hip in front of the library output Linear."""
         net = self.ff.net
         return _fused.FF_GEGLU_C640 and isinstance(net[2], nn.Linear) and _fused.ff_geglu_c640_supported(x.shape[-1], net[0].proj.out_features // 2)
 

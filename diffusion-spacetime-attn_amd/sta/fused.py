@@ -225,17 +225,33 @@ def rowgemm_worthwhile(x, width=None):
     return x.numel() // x.shape[-1] >= ROWGEMM_MIN_ROWS and rows_addressable(x, width)
 
 
+def _pack_ff_weight(weight, C, inner, bytes_symbol, pack_symbol, expected):
+    """A feed-forward weight -> the fragment image its pass streams through LDS (uint8 tensor); once per model. `expected`: what the
+    ValueError says the pass takes."""
+    L = lib.load()
+    n = getattr(L, bytes_symbol)(C, inner)
+    if n == 0 or not weight.is_cuda:
+        raise ValueError("%s; got %s" % (expected, tuple(weight.shape)))
+    w = weight.detach().contiguous()
+    buf = torch.empty(n, dtype=torch.uint8, device=w.device)
+    lib.check(getattr(L, pack_symbol)(w.data_ptr(), buf.data_ptr(), C, inner, _DT[w.dtype], _stream()), pack_symbol)
+    return buf
+
+
+def _ff_geglu(symbol, y_qfrag, w_packed, bias, inner, option):
+    """One GEGLU projection pass (csrc/sta_ffgemm.hip); `option`: the entry point's one integer (h_frag | max_workgroups)."""
+    C = y_qfrag.shape[-1]
+    R = y_qfrag.numel() // C
+    h = torch.empty(*y_qfrag.shape[:-1], inner, dtype=y_qfrag.dtype, device=y_qfrag.device)
+    lib.check(getattr(lib.load(), symbol)(y_qfrag.data_ptr(), w_packed.data_ptr(), _ptr(bias), h.data_ptr(), R, C, inner, option,
+                                          _DT[y_qfrag.dtype], _stream()), symbol)
+    return h
+
+
 def pack_geglu_weight(weight):
     """GEGLU proj.weight [2 * inner, C] -> the fragment image sta_ff_geglu_qfrag streams through LDS (uint8 tensor); once per model."""
     two_inner, C = weight.shape
-    L = lib.load()
-    n = L.sta_ff_geglu_packed_w_bytes(C, two_inner // 2)
-    if n == 0 or not weight.is_cuda:
-        raise ValueError("fused GEGLU projection: a CUDA weight [2560, 320]; got %s" % (tuple(weight.shape),))
-    w = weight.detach().contiguous()
-    buf = torch.empty(n, dtype=torch.uint8, device=w.device)
-    lib.check(L.sta_ff_geglu_pack_w(w.data_ptr(), buf.data_ptr(), C, two_inner // 2, _DT[w.dtype], _stream()), "sta_ff_geglu_pack_w")
-    return buf
+    return _pack_ff_weight(weight, C, two_inner // 2, "sta_ff_geglu_packed_w_bytes", "sta_ff_geglu_pack_w", "fused GEGLU projection: a CUDA weight [2560, 320]")
 
 
 def ff_geglu_supported(C, inner):
@@ -245,28 +261,16 @@ def ff_geglu_supported(C, inner):
 def ff_geglu_qfrag(y_qfrag, w_packed, bias, inner, h_frag=False):
     """h = (y W_v^T + b_v) * gelu(y W_g^T + b_g) with y in query-fragment order ([.., C] container); returns h [.., inner], row-major
     or (`h_frag`) in the fragment order ff_out_res_hfrag reads. The [.., 2 * inner] projection never exists in HBM (csrc/sta_ffgemm.hip)."""
-    C = y_qfrag.shape[-1]
-    R = y_qfrag.numel() // C
-    h = torch.empty(*y_qfrag.shape[:-1], inner, dtype=y_qfrag.dtype, device=y_qfrag.device)
-    lib.check(lib.load().sta_ff_geglu_qfrag(y_qfrag.data_ptr(), w_packed.data_ptr(), _ptr(bias), h.data_ptr(), R, C, inner, int(bool(h_frag)),
-                                            _DT[y_qfrag.dtype], _stream()), "sta_ff_geglu_qfrag")
-    return h
+    return _ff_geglu("sta_ff_geglu_qfrag", y_qfrag, w_packed, bias, inner, int(bool(h_frag)))
 
 
-FF_GEGLU_C640 = True    # level 1 (C = 640): the GEGLU projection + gelu * mul as one pass (csrc/sta_ffgemm640.hip); False: library GEMM + sta_geglu
+FF_GEGLU_C640 = True    # level 1 (C = 640): the GEGLU projection + gelu * mul as one pass (csrc/sta_ffgemm.hip); False: library GEMM + sta_geglu
 
 
 def pack_geglu_c640_weight(weight):
     """GEGLU proj.weight [5120, 640] -> the fragment image sta_ff_geglu_c640_qfrag streams through LDS (uint8 tensor); once per model."""
     two_inner, C = weight.shape
-    L = lib.load()
-    n = L.sta_ff_geglu_c640_packed_w_bytes(C, two_inner // 2)
-    if n == 0 or not weight.is_cuda:
-        raise ValueError("fused GEGLU projection (c640): a CUDA weight [5120, 640]; got %s" % (tuple(weight.shape),))
-    w = weight.detach().contiguous()
-    buf = torch.empty(n, dtype=torch.uint8, device=w.device)
-    lib.check(L.sta_ff_geglu_c640_pack_w(w.data_ptr(), buf.data_ptr(), C, two_inner // 2, _DT[w.dtype], _stream()), "sta_ff_geglu_c640_pack_w")
-    return buf
+    return _pack_ff_weight(weight, C, two_inner // 2, "sta_ff_geglu_c640_packed_w_bytes", "sta_ff_geglu_c640_pack_w", "fused GEGLU projection (c640): a CUDA weight [5120, 640]")
 
 
 def ff_geglu_c640_supported(C, inner):
@@ -274,27 +278,15 @@ def ff_geglu_c640_supported(C, inner):
 
 
 def ff_geglu_c640_qfrag(y_qfrag, w_packed, bias, inner, max_workgroups=0):
-    """ff_geglu_qfrag at C = 640, inner = 2560 (csrc/sta_ffgemm640.hip); h [.., inner] row-major. `max_workgroups` > 0 caps the
-    grid (tests: several passes per persistent workgroup at a small row count)."""
-    C = y_qfrag.shape[-1]
-    R = y_qfrag.numel() // C
-    h = torch.empty(*y_qfrag.shape[:-1], inner, dtype=y_qfrag.dtype, device=y_qfrag.device)
-    lib.check(lib.load().sta_ff_geglu_c640_qfrag(y_qfrag.data_ptr(), w_packed.data_ptr(), _ptr(bias), h.data_ptr(), R, C, inner, int(max_workgroups),
-                                                 _DT[y_qfrag.dtype], _stream()), "sta_ff_geglu_c640_qfrag")
-    return h
+    """ff_geglu_qfrag at C = 640, inner = 2560; h [.., inner] row-major. `max_workgroups` > 0 caps the grid (tests: several passes per
+    persistent workgroup at a small row count)."""
+    return _ff_geglu("sta_ff_geglu_c640_qfrag", y_qfrag, w_packed, bias, inner, int(max_workgroups))
 
 
 def pack_ff_out_weight(weight):
     """FeedForward net[2].weight [C, inner] -> the fragment image sta_ff_out_res_hfrag streams through LDS; once per model."""
     C, inner = weight.shape
-    L = lib.load()
-    n = L.sta_ff_out_packed_w_bytes(C, inner)
-    if n == 0 or not weight.is_cuda:
-        raise ValueError("fused feed-forward output: a CUDA weight [320, 1280]; got %s" % (tuple(weight.shape),))
-    w = weight.detach().contiguous()
-    buf = torch.empty(n, dtype=torch.uint8, device=w.device)
-    lib.check(L.sta_ff_out_pack_w(w.data_ptr(), buf.data_ptr(), C, inner, _DT[w.dtype], _stream()), "sta_ff_out_pack_w")
-    return buf
+    return _pack_ff_weight(weight, C, inner, "sta_ff_out_packed_w_bytes", "sta_ff_out_pack_w", "fused feed-forward output: a CUDA weight [320, 1280]")
 
 
 def ff_out_res_hfrag(x, h_frag, w_packed, bias):

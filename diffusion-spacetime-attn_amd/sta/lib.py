@@ -21,9 +21,8 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # csrc/*.hip files that are not translation units of their own: each is #included at the end of the source named here and so
 # shares its flags (-ffinite-math-only) and its pass through the hazard lint. sta_xattn_maps_bwd.hip (sta_xattn_token_maps_bwd) is the
 # backward of the token-map readout and is built with the cross-attention backward; sta_guide.hip (sta_latent_guide) is the latent update of
-# attention-guided sampling and is built with the sampler step, whose helpers it uses (no -ffinite-math-only there: it tests for Inf / NaN);
-# sta_ffgemm640.hip (sta_ff_geglu_c640_*) is the level-1 GEGLU projection pass and is built with the level-0 feed-forward passes, whose GELU it uses.
-INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_ffgemm640.hip": "sta_ffgemm.hip"}
+# attention-guided sampling and is built with the sampler step, whose helpers it uses (no -ffinite-math-only there: it tests for Inf / NaN).
+INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip"}
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -39,7 +38,7 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 
 # Kernels built to the last register of their occupancy: {translation unit: substrings of the kernel names}. build() refuses a toolchain
 # that spills one (a spilled B fragment is a scratch round trip per MFMA: the pass would be slower than the pair it replaces).
-NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_c640_qfrag_kernel",)}
+NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",)}
 
 STA_BF16, STA_F16 = 0, 1
 STA_MX8_GEGLU, STA_MX8_MX_OUT = 1, 2

@@ -86,7 +86,7 @@ int sta_ff_out_res_hfrag(const void* h_frag, const void* packed_w, const void* b
                          int inner, int dtype, void* stream);
 
 /*
- * The first half of the feed-forward at SD-v1 level 1 in one pass (csrc/sta_ffgemm640.hip): sta_ff_geglu_qfrag's computation,
+ * The first half of the feed-forward at SD-v1 level 1 in one pass (csrc/sta_ffgemm.hip, the same kernel template): sta_ff_geglu_qfrag's computation,
  * operand orders, GELU and single rounding at C = 640, inner = 2560 (sta_ff_geglu_c640_packed_w_bytes: 0 for any other shape;
  * the packed image differs from sta_ff_geglu_pack_w's: a sub-chunk holds one half of the reduction dimension). h leaves row-major.
  *   bias: [2 * inner] dtype or NULL;  h: [R][inner] dtype;  R % 16 == 0, R * inner * 2 bytes < 4 GiB

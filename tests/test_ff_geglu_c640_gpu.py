@@ -1,4 +1,4 @@
-"""sta_ff_geglu_c640_qfrag (csrc/sta_ffgemm640.hip): the GEGLU projection + gelu * mul of the level-1 feed-forward (C = 640,
+"""sta_ff_geglu_c640_qfrag (csrc/sta_ffgemm.hip): the GEGLU projection + gelu * mul of the level-1 feed-forward (C = 640,
 inner = 2560) as one pass — the kernel against fp64, its refusals, and the C = 640 BasicTransformerBlock with the pass on and off."""
 import os
 

@@ -1,6 +1,6 @@
 """sta_geglu at the FF shapes of the default bench (32 prompts: rows = 64 * N): time, HBM-side GB/s and max error vs fp64.
 
---C 640: the level-1 GEGLU projection A/B instead — the one pass of csrc/sta_ffgemm640.hip against the pair it replaces
+--C 640: the level-1 GEGLU projection A/B instead — the one pass of csrc/sta_ffgemm.hip (the C = 640 instance) against the pair it replaces
 (F.linear + fused.geglu) at R rows (default 131072: the five level-1 blocks of the bench), both 16-bit types, the two variants
 alternating launch by launch in one process, one HIP event pair per launch, 20 launches after 3 warm-ups. Every input comes from
 HBM: a launch moves > 1 GB, far beyond what the caches keep from the previous one."""
