@@ -341,6 +341,8 @@ GN_STATS_FROM_PRODUCER = True   # convolutions / row GEMMs accumulate the consum
 CONV_MIN_ITEMS = 64     # (tile, channel part) work items below which the library convolution is the faster one (a launch feeds 256 CUs:
                         # at one prompt per step the 16 x 16 / 8 x 8 levels have 16 items and lose 2 - 3 x: tools/conv_bench.py --batch 2)
 CONV3X3 = True          # the HIP implicit-GEMM 3x3 convolution for the NHWC trunk (csrc/sta_conv.hip); False: library convolution
+CONV_UP2_SUBPIXEL = True    # Upsample.conv (`up2`) as four 2x2 sub-pixel convolutions of the half-resolution tensor (4/9 of the flops:
+                            # csrc/sta_conv.hip, SUB); False: the 3x3 kernel reading the small tensor through (y >> 1, x >> 1)
 _conv_zeros = {}
 CONV_MAX_BYTES = 0xfffffff0 - 1     # output bytes one launch addresses (32-bit buffer descriptor)
 
@@ -371,6 +373,70 @@ def conv3x3_work_items(B, H, W, Cout):
     return tiles * (Cout // 160 if Cout % 160 == 0 else Cout // 128)
 
 
+def conv3x3_up2_subpixel_supported(x, weight):
+    """x ([B, Cin, Hs, Ws], what conv3x3_supported(x, weight, up2=True) accepted) at a geometry the sub-pixel mode takes (the tiles are
+    those of the Hs x Ws input: a 16-wide, 8-high input has none and stays with the 3x3 kernel), with enough (tile, part, phase) items."""
+    B, Cin, Hs, Ws = x.shape
+    Cout = weight.shape[0]
+    return (bool(lib.load().sta_conv3x3_up2_nhwc_supported(1, 2 * Hs, 2 * Ws, Cin, Cout))
+            and conv3x3_up2_work_items(B, 2 * Hs, 2 * Ws, Cout) >= CONV_MIN_ITEMS)
+
+
+def conv3x3_up2_work_items(B, H, W, Cout):
+    """(pixel tile of the H / 2 x W / 2 input, output-channel part, output phase) items of one sta_conv3x3_up2_nhwc launch."""
+    return 4 * conv3x3_work_items(B, H // 2, W // 2, Cout)
+
+
+def subpixel_weights(weight):
+    """Conv2d weight [Cout, Cin, 3, 3] -> [4, Cout, Cin, 2, 2]: the 2x2 taps W'_ab[u][v] of output phase 2a + b (row, column parity) of
+    conv2d(interpolate(x, 2, 'nearest'), weight, padding=1) as a convolution of x itself,
+        out[2y + a][2x + b] = sum_{u, v} W'_ab[u][v] . x[y + u + a - 1][x + v + b - 1],
+        W'_ab[u][v] = sum_{ky in R_a(u)} sum_{kx in R_b(v)} w[ky][kx],   R_0 = ({0}, {1, 2}),  R_1 = ({0, 1}, {2}).
+    The restatement of sta_conv3x3_up2_pack_w: 16-bit weights are summed in fp32, ky-major and kx-minor, and rounded once (wider
+    types are summed in their own precision: the unrounded sums). Runs on any device."""
+    w = weight.detach()
+    acc_dt = torch.float32 if w.dtype in (torch.float16, torch.bfloat16) else w.dtype
+    R = (((0,), (1, 2)), ((0, 1), (2,)))
+    out = torch.empty((4,) + tuple(w.shape[:2]) + (2, 2), dtype=w.dtype, device=w.device)
+    for a in range(2):
+        for b in range(2):
+            for u in range(2):
+                for v in range(2):
+                    s = torch.zeros(w.shape[:2], dtype=acc_dt, device=w.device)
+                    for ky in R[a][u]:
+                        for kx in R[b][v]:
+                            s = s + w[:, :, ky, kx].to(acc_dt)
+                    out[2 * a + b, :, :, u, v] = s.to(w.dtype)
+    return out
+
+
+def subpixel_conv_reference(x, wsub):
+    """The four 2x2 convolutions of the zero-padded x [B, Cin, Hs, Ws] with wsub = subpixel_weights(w) ([4, Cout, Cin, 2, 2]), interleaved
+    into [B, Cout, 2 Hs, 2 Ws]: what sta_conv3x3_up2_nhwc computes, in torch and in x's precision (the tests' reference)."""
+    B, _, Hs, Ws = x.shape
+    xp = torch.nn.functional.pad(x, (1, 1, 1, 1))
+    out = x.new_empty((B, wsub.shape[1], 2 * Hs, 2 * Ws))
+    for a in range(2):
+        for b in range(2):
+            out[:, :, a::2, b::2] = torch.nn.functional.conv2d(xp[:, :, a:a + Hs + 1, b:b + Ws + 1], wsub[2 * a + b].to(x.dtype))
+    return out
+
+
+def pack_conv3x3_up2_weight(weight):
+    """Conv2d weight [Cout, Cin, 3, 3] (any memory format) -> the A-operand fragment image of sta_conv3x3_up2_nhwc: subpixel_weights(weight)
+    as 1-KiB fragments [phase][part][channel step][u][v][tile] (include/sta_unet.h); once per model."""
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    L = lib.load()
+    n = L.sta_conv3x3_up2_packed_w_bytes(Cin, Cout)
+    if n == 0 or not weight.is_cuda or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("conv3x3_up2: a CUDA weight [Cout %% 160 == 0 or Cout %% 128 == 0, Cin %% 64 == 0, 3, 3]; got %s" % (tuple(weight.shape),))
+    w = weight.detach()
+    buf = torch.empty(n, dtype=torch.uint8, device=w.device)
+    so, si, sy, sx = w.stride()
+    lib.check(L.sta_conv3x3_up2_pack_w(w.data_ptr(), so, si, sy, sx, buf.data_ptr(), Cin, Cout, _DT[w.dtype], _stream()), "sta_conv3x3_up2_pack_w")
+    return buf
+
+
 def pack_conv3x3_weight(weight):
     """Conv2d weight [Cout, Cin, 3, 3] (any memory format) -> the A-operand fragment image of sta_conv3x3_nhwc; once per model."""
     Cout, Cin = weight.shape[0], weight.shape[1]
@@ -385,12 +451,15 @@ def pack_conv3x3_weight(weight):
     return buf
 
 
-def conv3x3_nhwc(x, w_packed, Cout, up2=False, bias=None, res=None, stats=False):
+def conv3x3_nhwc(x, w_packed, Cout, up2=False, bias=None, res=None, stats=False, subpixel=False):
     """conv2d(x, w, bias, padding=1) + res on an NHWC activation (logical shape [B, Cin, H, W], channels_last strides);
     up2: of the nearest-neighbour 2x upsampling of x, which is never written. Returns [B, Cout, H', W'] channels_last.
     A launch addresses its output through one 32-bit buffer descriptor: batches whose output exceeds 4 GiB go in several launches.
     stats: the kernel also accumulates every output channel's sum / sum of squares; they ride on the result as `_sta_stats`
-    ([B, Cout, 2] fp32) for the GroupNorm that consumes it (groupnorm_silu skips its statistics pass)."""
+    ([B, Cout, 2] fp32) for the GroupNorm that consumes it (groupnorm_silu skips its statistics pass).
+    subpixel (with up2): w_packed is pack_conv3x3_up2_weight's image and the launch is sta_conv3x3_up2_nhwc — the same operation as four
+    2x2 convolutions of x, equal to the 3x3 path up to one rounding of every pre-summed weight."""
+    assert up2 or not subpixel, "subpixel is a mode of up2"
     B, Cin, Hs, Ws = x.shape
     H, W = (2 * Hs, 2 * Ws) if up2 else (Hs, Ws)
     z = _zeros_page(x.device, 2 * Cin)
@@ -403,15 +472,18 @@ def conv3x3_nhwc(x, w_packed, Cout, up2=False, bias=None, res=None, stats=False)
     per_img = H * W * Cout * esz
     nb = max(1, min(B, CONV_MAX_BYTES // per_img))
     L = lib.load()
-    slots = L.sta_conv3x3_stats_slots(H, W) if stats else 0
+    slots = (L.sta_conv3x3_up2_stats_slots(H, W) if subpixel else L.sta_conv3x3_stats_slots(H, W)) if stats else 0
     part = torch.empty((B + 1, slots, Cout, 2), dtype=torch.float32, device=x.device) if slots else None
     for b0 in range(0, B, nb):
         n = min(nb, B - b0)
         # (a chunk's spare image slot is the next chunk's first image, written later; the last chunk's is the tensor's spare slot)
-        lib.check(L.sta_conv3x3_nhwc(x.data_ptr() + b0 * Hs * Ws * Cin * esz, w_packed.data_ptr(), z.data_ptr(), _ptr(bias),
-                                     0 if res is None else res.data_ptr() + b0 * per_img, out.data_ptr() + b0 * per_img,
-                                     0 if part is None else part.data_ptr() + b0 * slots * Cout * 8, n, H, W, Cin, Cout,
-                                     int(bool(up2)), _DT[x.dtype], _stream()), "sta_conv3x3_nhwc")
+        ptrs = (x.data_ptr() + b0 * Hs * Ws * Cin * esz, w_packed.data_ptr(), z.data_ptr(), _ptr(bias),
+                0 if res is None else res.data_ptr() + b0 * per_img, out.data_ptr() + b0 * per_img,
+                0 if part is None else part.data_ptr() + b0 * slots * Cout * 8)
+        if subpixel:
+            lib.check(L.sta_conv3x3_up2_nhwc(*ptrs, n, H, W, Cin, Cout, _DT[x.dtype], _stream()), "sta_conv3x3_up2_nhwc")
+        else:
+            lib.check(L.sta_conv3x3_nhwc(*ptrs, n, H, W, Cin, Cout, int(bool(up2)), _DT[x.dtype], _stream()), "sta_conv3x3_nhwc")
     if part is not None:
         if _version(out) is not None:           # (inference tensors: no producer statistics, the consumer takes its own pass)
             out._sta_stats = (out._version, _finalize_stats(part, B, slots, Cout))
@@ -424,12 +496,21 @@ def packed_conv_weight(owner, conv):
     return cached_image(owner, ("conv", id(conv)), (w,), lambda: pack_conv3x3_weight(w))
 
 
+def packed_conv_up2_weight(owner, conv):
+    """conv.weight as sta_conv3x3_up2_nhwc streams it (the sub-pixel image), cached under a slot of its own and repacked as above."""
+    w = conv.weight
+    return cached_image(owner, ("conv_up2", id(conv)), (w,), lambda: pack_conv3x3_up2_weight(w))
+
+
 def conv3x3_module(owner, conv, x, bias=None, res=None, up2=False, stats=True):
     """conv(x) (+ bias + res) for a 3x3 nn.Conv2d outside autograd: the HIP convolution where it applies, the library convolution
     (+ the fused bias / residual pass) elsewhere. `bias=None` means bias-free (the caller folds conv.bias into a later pass).
     `stats=False`: the result is not read by a GroupNorm next (e.g. it feeds an Upsample convolution) — no epilogue statistics, no
     partial buffer, no finalize launch."""
     if conv3x3_supported(x, conv.weight, up2=up2) and (res is None or is_nhwc(res)):
+        if up2 and CONV_UP2_SUBPIXEL and conv3x3_up2_subpixel_supported(x, conv.weight):
+            return conv3x3_nhwc(x, packed_conv_up2_weight(owner, conv), conv.weight.shape[0], up2=True, bias=bias, res=res,
+                                stats=GN_STATS_FROM_PRODUCER and stats, subpixel=True)
         return conv3x3_nhwc(x, packed_conv_weight(owner, conv), conv.weight.shape[0], up2=up2, bias=bias, res=res,
                             stats=GN_STATS_FROM_PRODUCER and stats)
     if up2:

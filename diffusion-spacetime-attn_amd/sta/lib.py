@@ -38,7 +38,8 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 
 # Kernels built to the last register of their occupancy: {translation unit: substrings of the kernel names}. build() refuses a toolchain
 # that spills one (a spilled B fragment is a scratch round trip per MFMA: the pass would be slower than the pair it replaces).
-NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",)}
+# (sta_conv.hip: the sub-pixel instantiations conv3x3_nhwc_kernel<T, GEO, NTW, true> — "Lb1E" is the mangled `true`)
+NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",)}
 
 STA_BF16, STA_F16 = 0, 1
 STA_MX8_GEGLU, STA_MX8_MX_OUT = 1, 2
@@ -103,6 +104,11 @@ SYMBOLS = {
     "sta_conv3x3_packed_w_bytes": (_sz, [_i, _i]),
     "sta_conv3x3_pack_w": (_i, [_vp, _l, _l, _l, _l, _vp, _i, _i, _i, _vp]),
     "sta_conv3x3_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "sta_conv3x3_up2_nhwc_supported": (_i, [_i, _i, _i, _i, _i]),
+    "sta_conv3x3_up2_stats_slots": (_i, [_i, _i]),
+    "sta_conv3x3_up2_packed_w_bytes": (_sz, [_i, _i]),
+    "sta_conv3x3_up2_pack_w": (_i, [_vp, _l, _l, _l, _l, _vp, _i, _i, _i, _vp]),
+    "sta_conv3x3_up2_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sta_linear_rows_supported": (_i, [_l, _i, _i]),
     "sta_linear_rows_packed_w_bytes": (_sz, [_i, _i]),
     "sta_linear_rows_pack_w": (_i, [_vp, _l, _l, _vp, _i, _i, _i, _vp]),

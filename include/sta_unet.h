@@ -139,6 +139,28 @@ int sta_conv3x3_nhwc(const void* x, const void* packed_w, const void* zeros, con
                      int H, int W, int Cin, int Cout, int up2, int dtype, void* stream);
 
 /*
+ * The up2 = 1 convolution above as four 2x2 sub-pixel convolutions of the half-resolution tensor, one per output phase (a, b) =
+ * (row parity, column parity) — 16 instead of 36 multiply-adds per input pixel, channel and output channel:
+ *     out[b][2y + a][2x + b'][o] = bias[o] + res + sum_{u, v in {0,1}, i} W'_ab'[o][i][u][v] * x[b][y + u + a - 1][x + v + b' - 1][i]
+ *     W'_ab'[u][v] = sum_{ky in R_a(u)} sum_{kx in R_b'(v)} w[ky][kx],   R_0 = ({0}, {1, 2}),  R_1 = ({0, 1}, {2})
+ * (zero outside x; identical to the 3x3 convolution of the upsampled tensor in exact arithmetic). sta_conv3x3_up2_pack_w forms W' in
+ * fp32, ky-major and kx-minor, rounds ONCE to dtype and writes 1-KiB A-operand fragments [phase 2a + b'][part][kc][u][v][tile t]: lane
+ * (g, c) of a fragment holds W'[16 nt part + 16 t + c][32 kc + 8 g .. + 7][u][v] (nt = 10 or 8 row tiles per part, as for
+ * sta_conv3x3_pack_w). The result differs from sta_conv3x3_nhwc(up2 = 1) by that one rounding of every summed weight.
+ *   H, W: the OUTPUT size (x is [B][H / 2][W / 2][Cin]); all other arguments as for sta_conv3x3_nhwc;
+ *   stats: NULL, or [B + 1][sta_conv3x3_up2_stats_slots(H, W)][Cout][2] (four times the slots of the H / 2 x W / 2 geometry: one per phase).
+ * sta_conv3x3_up2_nhwc_supported: H, W even and the H / 2 x W / 2 input one of sta_conv3x3_nhwc's geometries (W / 2 % 32 == 0 and
+ * H / 2 % 8 == 0, or W / 2 == 16 and H / 2 % 16 == 0, or 8 x 8); Cin % 64 == 0; Cout % 160 == 0 or Cout % 128 == 0; out below 4 GiB.
+ * Everything else stays with sta_conv3x3_nhwc(up2 = 1).
+ */
+int sta_conv3x3_up2_nhwc_supported(int B, int H, int W, int Cin, int Cout);
+int sta_conv3x3_up2_stats_slots(int H, int W);
+size_t sta_conv3x3_up2_packed_w_bytes(int Cin, int Cout);
+int sta_conv3x3_up2_pack_w(const void* w, long so, long si, long sy, long sx, void* packed, int Cin, int Cout, int dtype, void* stream);
+int sta_conv3x3_up2_nhwc(const void* x, const void* packed_w, const void* zeros, const void* bias, const void* res, void* out, float* stats, int B,
+                         int H, int W, int Cin, int Cout, int dtype, void* stream);
+
+/*
  * The Linear layers / 1x1 convolutions of the transformer blocks and ResBlock skips as one row GEMM (csrc/sta_gemm.hip; reference
  * CrossAttention.to_q / to_k / to_v / to_out attention.py:158-215, FeedForward :48-69, SpatialTransformer.proj_in / proj_out :322-333,
  * ResBlock.skip_connection openaimodel.py:196-206):
