@@ -156,3 +156,6 @@ int sta_sampler_step_bwd(const float* g_xn, const float* g_m, float* g_x, void* 
 
 // the latent update of attention-guided sampling (sta_latent_guide): same helpers, same flags, same pass through the hazard lint
 #include "sta_guide.hip"
+
+// wide canvases as overlapping windows (sta_window_split / sta_window_fuse / sta_sampler_step_windows): same helpers, same flags
+#include "sta_window.hip"

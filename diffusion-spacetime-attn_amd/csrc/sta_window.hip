@@ -1,0 +1,242 @@
+// sta_window.hip — wide canvases sampled as overlapping square windows (gfx950). C-ABI in include/sta_unet.h (sta_window_split /
+// sta_window_fuse / sta_sampler_step_windows). #included at the end of sta_sampler.hip (its V8T / F4 / load8 / store8 / StepCoef, its
+// flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division).
+// Conventions of sta_sampler.hip: 256-lane groups, grid-stride, a lane owns 8 consecutive elements of one CANVAS row, 16-byte loads and
+// stores, fp32 arithmetic. Window sides, offsets and canvas sides are multiples of 8, so a lane's vector lies inside or outside a window
+// as a whole. The offset tables travel by value in the kernel arguments: nothing device-side to fill, the launches are capturable.
+// A canvas element is owned by exactly one lane, which visits the windows that cover it in ascending w = j nx + i: no atomics, no LDS,
+// one writer per output element, the same bits from launch to launch.
+
+namespace {
+
+struct WinGrid {
+  int ny, nx, s;
+  int oy[STA_MAX_WINDOW_OFFSETS], ox[STA_MAX_WINDOW_OFFSETS];
+};
+
+// vector v of a [rows][C][Hc][Wc] tensor -> its row (image), channel and the position of its first element
+struct CanvasPos {
+  long row;
+  int c, y, x;
+};
+
+__device__ __forceinline__ CanvasPos canvas_pos(long v, int C, int Hc, int wvec) {
+  CanvasPos p;
+  const long line = v / wvec;
+  p.x = (int)(v - line * wvec) * 8;
+  const long plane = line / Hc;
+  p.y = (int)(line - plane * Hc);
+  p.row = plane / C;
+  p.c = (int)(plane - p.row * C);
+  return p;
+}
+
+// first element of the lane's vector inside image `img` of a [.][C][s][s] window tensor; (dy, dx) = position inside the window
+__device__ __forceinline__ long window_at(long img, int C, int c, int s, int dy, int dx) {
+  return ((img * C + c) * s + dy) * (long)s + dx;
+}
+
+// sum over the covering windows of pair row r (ascending w, fp32, starting from the first one's value) -> count
+template <typename T>
+__device__ __forceinline__ int gather_sum(const T* __restrict__ eps, const WinGrid& g, long p, int r, int C, const CanvasPos& q, float* acc) {
+  using V8 = typename V8T<T>::type;
+  const long T_ = (long)g.ny * g.nx;
+  int n = 0;
+  for (int j = 0; j < g.ny; ++j) {
+    const int dy = q.y - g.oy[j];
+    if ((unsigned)dy >= (unsigned)g.s) continue;
+    for (int i = 0; i < g.nx; ++i) {
+      const int dx = q.x - g.ox[i];
+      if ((unsigned)dx >= (unsigned)g.s) continue;
+      const V8 e = *(const V8*)(eps + window_at(2 * (p * T_ + j * g.nx + i) + r, C, q.c, g.s, dy, dx));
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = n ? acc[k] + (float)e[k] : (float)e[k];
+      ++n;
+    }
+  }
+  return n;
+}
+
+// o -> rows r0 .. r1 of the pair of every covering window
+template <typename T>
+__device__ __forceinline__ void scatter(T* __restrict__ xin, const WinGrid& g, long p, int r0, int r1, int C, const CanvasPos& q,
+                                        const typename V8T<T>::type o) {
+  using V8 = typename V8T<T>::type;
+  const long T_ = (long)g.ny * g.nx;
+  for (int j = 0; j < g.ny; ++j) {
+    const int dy = q.y - g.oy[j];
+    if ((unsigned)dy >= (unsigned)g.s) continue;
+    for (int i = 0; i < g.nx; ++i) {
+      const int dx = q.x - g.ox[i];
+      if ((unsigned)dx >= (unsigned)g.s) continue;
+      for (int r = r0; r <= r1; ++r) *(V8*)(xin + window_at(2 * (p * T_ + j * g.nx + i) + r, C, q.c, g.s, dy, dx)) = o;
+    }
+  }
+}
+
+// src [P rows][C][Hc][Wc] (S = float or T) -> xin [2 P T][C][s][s]; rows == 1: the canvas state goes to both rows of every pair
+template <typename S, typename T>
+__global__ __launch_bounds__(256) void window_split_kernel(const S* __restrict__ src, T* __restrict__ xin, long nvec, int rows, int C, int Hc,
+                                                           int Wc, WinGrid g) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
+    V8 o;
+    if constexpr (sizeof(S) == 4) {
+      float f[8];
+      load8((const float*)src + 8 * v, f);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = (T)f[k];
+    } else {
+      o = ((const V8*)src)[v];
+    }
+    const int r = rows == 2 ? (int)(q.row & 1) : 0;
+    scatter<T>(xin, g, rows == 2 ? q.row >> 1 : q.row, r, rows == 2 ? r : 1, C, q, o);
+  }
+}
+
+// eps [2 P T][C][s][s] -> out [2 P][C][Hc][Wc]: the mean over the covering windows, fp32 sum / count, rounded once
+template <typename T>
+__global__ __launch_bounds__(256) void window_fuse_kernel(const T* __restrict__ eps, T* __restrict__ out, long nvec, int C, int Hc, int Wc,
+                                                          WinGrid g) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
+    float acc[8] = {};
+    const float cnt = (float)gather_sum<T>(eps, g, q.row >> 1, (int)(q.row & 1), C, q, acc);
+    V8 o;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = (T)(acc[k] / cnt);
+    ((V8*)out)[v] = o;
+  }
+}
+
+// sampler_step_kernel on the overlap means of the windows' UNet output (fp32, not rounded): the same expressions in the same order;
+// xin (null = not written): the rounded x_next to both rows of every covering window, the next call's input
+template <typename T>
+__global__ __launch_bounds__(256) void sampler_step_windows_kernel(const T* __restrict__ eps, const float* __restrict__ x,
+                                                                   const float* __restrict__ m_prev, const float* __restrict__ noise,
+                                                                   float* __restrict__ x_next, float* __restrict__ m, T* __restrict__ xin,
+                                                                   long nvec, int C, int Hc, int Wc, WinGrid g, StepCoef c) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
+    float eu[8] = {}, ec[8] = {};
+    const float cnt = (float)gather_sum<T>(eps, g, q.row, 0, C, q, eu);
+    gather_sum<T>(eps, g, q.row, 1, C, q, ec);
+    float xv[8], mp[8], nz[8], xn[8], mv[8];
+    load8(x + 8 * v, xv);
+    if (m_prev) load8(m_prev + 8 * v, mp);
+    if (noise) load8(noise + 8 * v, nz);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float u = eu[k] / cnt;
+      const float e = u + c.scale * (ec[k] / cnt - u);
+      mv[k] = (xv[k] - c.sigma_t * e) / c.alpha_t;
+      float t = c.c_x * xv[k] + c.c_m * mv[k] + c.c_e * e;
+      if (m_prev) t += c.c_p * mp[k];
+      if (noise) t += c.c_n * nz[k];
+      xn[k] = t;
+    }
+    store8(x_next + 8 * v, xn);
+    store8(m + 8 * v, mv);
+    if (xin) {
+      V8 o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = (T)xn[k];
+      scatter<T>(xin, g, q.row, 0, 1, C, q, o);
+    }
+  }
+}
+
+// offsets along one axis of length L: 0 first, multiples of 8, ascending, no gap (step <= s), the last window ends at L
+int window_axis_ok(const char* what, const char* axis, int n, const int* o, int s, int L) {
+  if (n < 1 || n > STA_MAX_WINDOW_OFFSETS) return sta_fail(STA_E_ARG, "%s: n%s=%d (need 1 .. %d offsets)", what, axis, n, STA_MAX_WINDOW_OFFSETS);
+  for (int k = 0; k < n; ++k) {
+    const int prev = k ? o[k - 1] : 0;
+    if (o[k] % 8) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d is not a multiple of 8", what, axis, k, o[k]);
+    if (o[k] < 0 || (long)o[k] + s > L) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d out of range (s=%d, length %d)", what, axis, k, o[k], s, L);
+    if (k ? o[k] <= prev : o[k] != 0) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d unsorted (after %d; the first offset is 0)", what, axis, k, o[k], prev);
+    if (o[k] - prev > s) return sta_fail(STA_E_ARG, "%s: gap between o%s[%d]=%d and o%s[%d]=%d (s=%d)", what, axis, k - 1, prev, axis, k, o[k], s);
+  }
+  if (o[n - 1] + s != L) return sta_fail(STA_E_ARG, "%s: gap behind o%s[%d]=%d (s=%d, length %d)", what, axis, n - 1, o[n - 1], s, L);
+  return STA_OK;
+}
+
+int window_grid_ok(const char* what, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, WinGrid* g) {
+  if (!oy || !ox) return sta_fail(STA_E_ARG, "null pointer");
+  if (P <= 0 || C <= 0) return sta_fail(STA_E_ARG, "%s: P=%ld C=%d", what, P, C);
+  if (s < 8 || Hc < s || Wc < s || s % 8 || Hc % 8 || Wc % 8)
+    return sta_fail(STA_E_ARG, "%s: s=%d Hc=%d Wc=%d (need multiples of 8 and 8 <= s <= Hc, Wc)", what, s, Hc, Wc);
+  if (const int rc = window_axis_ok(what, "y", ny, oy, s, Hc)) return rc;
+  if (const int rc = window_axis_ok(what, "x", nx, ox, s, Wc)) return rc;
+  *g = WinGrid{};
+  g->ny = ny, g->nx = nx, g->s = s;
+  for (int k = 0; k < ny; ++k) g->oy[k] = oy[k];
+  for (int k = 0; k < nx; ++k) g->ox[k] = ox[k];
+  return STA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                     int src_dtype, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!src || !xin) return sta_fail(STA_E_ARG, "null pointer");
+  WinGrid g;
+  if (const int rc = window_grid_ok("window_split", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
+  if (rows != 1 && rows != 2) return sta_fail(STA_E_ARG, "window_split: rows=%d (1: canvas states, 2: input pairs)", rows);
+  if (!sta_aligned16(src) || !sta_aligned16(xin)) return sta_fail(STA_E_ARG, "window_split: every tensor must be 16-byte aligned");
+  if (src_dtype != STA_SRC_F32 && src_dtype != dtype)
+    return sta_fail(STA_E_UNSUP, "window_split: src_dtype %d (float32 = %d, or the output's dtype %d)", src_dtype, STA_SRC_F32, dtype);
+  const long nvec = P * rows * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    if (src_dtype == STA_SRC_F32)
+      return sta_launch<window_split_kernel<float, T>>("window_split", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
+                                                       (const float*)src, (T*)xin, nvec, rows, C, Hc, Wc, g);
+    return sta_launch<window_split_kernel<T, T>>("window_split", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)src,
+                                                 (T*)xin, nvec, rows, C, Hc, Wc, g);
+  });
+}
+
+int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int dtype,
+                    void* stream) {
+  g_sta_err[0] = 0;
+  if (!eps || !out) return sta_fail(STA_E_ARG, "null pointer");
+  WinGrid g;
+  if (const int rc = window_grid_ok("window_fuse", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
+  if (!sta_aligned16(eps) || !sta_aligned16(out)) return sta_fail(STA_E_ARG, "window_fuse: every tensor must be 16-byte aligned");
+  const long nvec = 2 * P * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<window_fuse_kernel<T>>("window_fuse", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)eps, (T*)out,
+                                             nvec, C, Hc, Wc, g);
+  });
+}
+
+int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin, long P,
+                             int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t,
+                             float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!eps || !x || !x_next || !m) return sta_fail(STA_E_ARG, "null pointer");
+  WinGrid g;
+  if (const int rc = window_grid_ok("sampler_step_windows", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
+  if (!sta_aligned16(eps) || !sta_aligned16(x) || !sta_aligned16(m_prev) || !sta_aligned16(noise) || !sta_aligned16(x_next) || !sta_aligned16(m) || !sta_aligned16(xin))
+    return sta_fail(STA_E_ARG, "sampler_step_windows: every tensor must be 16-byte aligned");
+  if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_windows: alpha_t == 0");
+  const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
+  const long nvec = P * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<sampler_step_windows_kernel<T>>("sampler_step_windows", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
+                                                      (const T*)eps, x, m_prev, noise, x_next, m, (T*)xin, nvec, C, Hc, Wc, g, c);
+  });
+}
+
+}  // extern "C"

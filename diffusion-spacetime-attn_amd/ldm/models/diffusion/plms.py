@@ -317,6 +317,88 @@ class PLMSSampler(object):
                            object_names=list(object_names), local_conditionings=list(local_conditionings), batched=True)
         return None
 
+    _canvas = None               # the sta.canvas.Grid while sample_canvas runs (set like _start / _inpaint, cleared in `finally`)
+    canvas_fused_step = True     # step-kernel samplers on a canvas: one sta_sampler_step_windows launch per call (False: fuse + step + split)
+
+    def sample_canvas(self, S, canvas, window, stride=None, conditionings=None, unconditional_conditionings=None, bboxs=None,
+                      object_names=None, local_conditionings=None, x_T=None, unconditional_guidance_scale=7.5, eta=0.0, seed=1,
+                      prompt_indices=None, curr_texts=None, mask=None, x0=None, channels=4, verbose=False):
+        """P wide or tall canvases (same number of objects), each sampled as T overlapping square windows (sta.canvas): every UNet call
+        sees the 2 P T window rows as one CFG batch — an ordinary batch of P T images for the blocks, graph replay included —, the T
+        predictions are averaged where windows overlap and the sampler step runs on the canvas.
+        canvas = (Hc, Wc), window = s, stride (default s / 2): latent pixels, the grid rules of sta.canvas.window_grid. The other
+        arguments are per-canvas lists as in `sample_batch`; `bboxs` are normalised to the canvas (every window's blocks get them
+        re-expressed in its own coordinates: a disc has radius 0.2 s latent pixels everywhere); the prompt, the unconditional context,
+        the local contexts and the blend weights W[p] belong to the canvas and are repeated per window. x_T: [P, channels, Hc, Wc].
+        `last_result`: x0 [P, channels, Hc, Wc], image [P, 3, 8 Hc, 8 Wc] from ONE decode of the whole canvas, W [P, K, S].
+        Fixed weights only. ValueError before any UNet call for opt_epochs > 1 (the loss front end takes square images:
+        sta.clip.check_view_shapes), an attached attn_capture, attn_loss or latent_guidance, mask= / x0= (inpainting) and a non-zero
+        `_start` (img2img decodes): none of them is defined on a canvas yet."""
+        from sta import canvas as _cv
+        if self.opt_epochs > 1:
+            raise ValueError("sample_canvas samples with fixed blend weights: opt_epochs = %d tracks epochs, and the loss front end "
+                             "takes square images (use opt_epochs 0)" % self.opt_epochs)
+        for name in ("attn_capture", "attn_loss", "latent_guidance"):
+            if getattr(self, name) is not None:
+                raise ValueError("sample_canvas: an attached %s reads one square image's attention maps; detach it for canvases" % name)
+        if mask is not None or x0 is not None:
+            raise ValueError("sample_canvas: mask= / x0= (inpainting) is not defined on a canvas")
+        if getattr(self, "_start", 0):
+            raise ValueError("sample_canvas: a trajectory that starts at call %d (img2img) is not defined on a canvas" % self._start)
+        Hc, Wc = canvas
+        grid = _cv.window_grid(Hc, Wc, window, window // 2 if stride is None else stride)
+        P = len(conditionings)
+        if not (len(bboxs) == len(object_names) == len(local_conditionings) == P):
+            raise ValueError("sample_canvas takes per-canvas lists of equal length (%d conditionings, %d bboxs, %d object_names, %d "
+                             "local_conditionings)" % (P, len(bboxs), len(object_names), len(local_conditionings)))
+        if x_T is not None and tuple(x_T.shape) != (P, channels, grid.Hc, grid.Wc):
+            raise ValueError("x_T %s must be [%d, %d, %d, %d]" % (tuple(x_T.shape), P, channels, grid.Hc, grid.Wc))
+        cond = torch.cat(list(conditionings))
+        uncond = torch.cat(list(unconditional_conditionings)) if isinstance(unconditional_conditionings, (list, tuple)) \
+            else unconditional_conditionings.expand(P, -1, -1)
+        self._canvas = grid
+        try:
+            self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+            # the blocks see P T images: the canvas's local contexts once per window
+            self.plms_sampling(cond, (P, channels, grid.Hc, grid.Wc), x_T=x_T, unconditional_guidance_scale=unconditional_guidance_scale,
+                               unconditional_conditioning=uncond, text_index=0,
+                               curr_text=list(curr_texts) if curr_texts is not None else [""] * P, bboxs_curr=list(bboxs), seed=seed,
+                               prompt_idx=list(prompt_indices) if prompt_indices is not None else list(range(P)),
+                               object_names=list(object_names),
+                               local_conditionings=[loc for loc in local_conditionings for _ in range(grid.T)], batched=True)
+        finally:
+            self._canvas = None
+        return None
+
+    def _window_unet(self, cond, uncond, scale, bboxs_curr, text_index, graph, img):
+        """The canvas trajectory's UNet call -> (grid, unet(xin, t, coef)): xin the [2 P T] window input pairs, t [P] and coef [P, K] of
+        the canvases (repeated per window here), the result the UNet's raw [2 P T] output. It is the ordinary eps function of a batch
+        of P T images — repeated contexts, every window's own centres —, so graph replay and the fused kernels run as they are."""
+        from sta import canvas as _cv
+        grid = self._canvas
+        P, T = img.shape[0], grid.T
+        rep = lambda v: v.repeat_interleave(T, dim=0)
+        boxes = [wc for bx in bboxs_curr for wc in _cv.window_centres(bx, grid)]
+        inner = self._make_eps_fn(rep(cond), rep(uncond.expand(P, -1, -1)), scale, boxes, text_index, graph, img.new_empty((P * T, 0)),
+                                  raw=True)
+        return grid, lambda xin, t, coef: inner(xin, rep(t), rep(coef))
+
+    def _canvas_eps_fn(self, cond, uncond, scale, bboxs_curr, text_index, graph, img):
+        """eps(x, t, coef) of a canvas state x [P, C, Hc, Wc] with classifier-free guidance: split into windows, one UNet call, overlap
+        mean (sta.canvas) — what _plms_update and _x_prev need to run on canvas tensors unchanged."""
+        from sta import canvas as _cv
+        grid, unet = self._window_unet(cond, uncond, scale, bboxs_curr, text_index, graph, img)
+        wdtype = next(self.model.model.parameters()).dtype
+        P = img.shape[0]
+
+        def eps(x, t, coef):
+            # the UNet answers in its input's type: `sample` hands it the float32 state, so the guidance arithmetic below runs in x's type
+            out = _cv.window_fuse(unet(_cv.window_split(x, grid, wdtype), t, coef), grid).to(x.dtype)
+            out = out.reshape(P, 2, *out.shape[1:])
+            e_u, e_c = out[:, 0], out[:, 1]
+            return e_u + scale * (e_c - e_u)
+        return eps
+
     # --------------------------------------------------------------------------------------------------
     def plms_sampling(self, cond, shape, x_T=None, temperature=1.0, unconditional_guidance_scale=1.0,
                       unconditional_conditioning=None, text_index=None, curr_text="", bboxs_curr=None, seed=None,
@@ -512,7 +594,10 @@ class PLMSSampler(object):
         keep = self._calls_to_keep(S + 1, b) if call_recompute and torch.is_grad_enabled() else 0
         if call_recompute and torch.is_grad_enabled():
             self.last_kept_calls = keep
-        eps_fn = self._make_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute, keep_last=keep, n_calls=S + 1)
+        if self._canvas is not None:
+            eps_fn = self._canvas_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img)
+        else:
+            eps_fn = self._make_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute, keep_last=keep, n_calls=S + 1)
         guide = self._guide(eps_fn)
         old_eps = []
         for i, step in enumerate(time_range):
@@ -754,6 +839,8 @@ class SolverSamplerBase(PLMSSampler):
 
     def _trajectory(self, img, cond, uncond, scale, time_range, W, bboxs_curr, text_index, graph=False, call_recompute=False):
         from sta import solver
+        if self._canvas is not None:
+            return self._canvas_trajectory(img, cond, uncond, scale, time_range, W, bboxs_curr, text_index, graph)
         S, b, device = len(time_range), img.shape[0], img.device
         self._call_key = (tuple(img.shape[1:]), int(W.shape[-2]))
         grad = torch.is_grad_enabled()
@@ -788,4 +875,29 @@ class SolverSamplerBase(PLMSSampler):
                 x, m_prev, xin = solver.solver_step_masked(out, x, m_prev, noise, c, self._blend(i + 1, x), dtype=wdtype, want_xin=fast)
             else:            # no blend after the last step (the reference has none either)
                 x, m_prev, xin = solver.solver_step(out, x, m_prev, noise, c, dtype=wdtype, want_xin=fast and i + 1 < S)
+        return x
+
+    def _canvas_trajectory(self, img, cond, uncond, scale, time_range, W, bboxs_curr, text_index, graph):
+        """The S calls of a canvas (sample_canvas: fixed weights, no autograd, from call 0). The first call's window inputs come from
+        window_split; after every UNet call ONE sta_sampler_step_windows launch reads the windows' output, forms the overlap means,
+        steps the canvas state and writes the next call's window inputs: x and m_prev stay canvas-shaped, and nothing but the
+        (graph-replayed) UNet call and that launch runs per step. `canvas_fused_step = False` takes window_fuse + solver_step +
+        window_split instead (three launches; the means are then rounded to the UNet's type before the step)."""
+        from sta import canvas as _cv
+        from sta import solver
+        grid, unet = self._window_unet(cond, uncond, scale, bboxs_curr, text_index, graph, img)
+        wdtype = next(self.model.model.parameters()).dtype
+        S, P, device = len(time_range), img.shape[0], img.device
+        x, m_prev = img, None
+        xin = _cv.window_split(x, grid, wdtype)
+        for i in range(S):
+            t_val = float(time_range[i]) if self.t_dtype.is_floating_point else int(time_range[i])
+            out = unet(xin, torch.full((P,), t_val, device=device, dtype=self.t_dtype), W[..., i])
+            c = self._coef(i, scale)
+            noise = self._noise(i, x) if c.c_n else None
+            if self.canvas_fused_step:
+                x, m_prev, xin = _cv.sampler_step_windows(out, x, m_prev, noise, c, grid, dtype=wdtype, want_xin=i + 1 < S)
+            else:
+                x, m_prev, _ = solver.solver_step(_cv.window_fuse(out, grid), x, m_prev, noise, c, dtype=wdtype)
+                xin = _cv.window_split(x, grid, wdtype) if i + 1 < S else None
         return x

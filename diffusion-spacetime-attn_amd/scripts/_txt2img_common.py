@@ -7,7 +7,9 @@ ignores, accepted for compatibility). Added: --layout (JSON replacing the layout
 --dataset (path override), --opt_epochs (0 = fixed weights), --limit/--start, --dtype, --synthetic,
 --clip (the fidelity-loss model; checked BEFORE sampling), --clip_tokenizer (vocabulary of the text encoder),
 --attn_guidance ETA / --attn_guidance_steps / --attn_guidance_iters (attention-guided latent updates, sta.guidance; shared with
-img2img.py and inpaint.py through add_guidance_arguments / check_guidance_option / make_guidance / report_guidance).
+img2img.py and inpaint.py through add_guidance_arguments / check_guidance_option / make_guidance / report_guidance),
+--canvas HxW / --canvas_stride PX (a wide or tall canvas sampled as overlapping --H x --W windows, sta.canvas; the layout's centres are
+then normalised to the canvas; fixed blend weights only).
 With torch.distributed.run the prompts are sharded round-robin over the ranks (one GPU each).
 """
 import argparse
@@ -87,6 +89,14 @@ def build_parser(default_dataset):
                    help="add LAMBDA x the attention-layout loss (sta.attnloss: (1 - in-disc share of each object's token maps)^2, recorded "
                         "at --attn_res inside the tracked UNet calls) to the loss of --opt_epochs > 1; without --clip it is the only loss "
                         "and the tracked epochs neither need CLIP weights nor decode")
+    p.add_argument("--canvas", type=str, default=None, metavar="HxW",
+                   help="sample a canvas of H x W pixels as overlapping --H x --W windows (which must be square) in one CFG batch per UNet "
+                        "call, averaged where they overlap (sta.canvas); a multiple of 8 x --f and at least the window; the centres of "
+                        "--layout are then normalised to the canvas; fixed blend weights only (--opt_epochs 0 or 1), no --attn_maps / "
+                        "--attn_loss / --attn_guidance")
+    p.add_argument("--canvas_stride", type=int, default=None, metavar="PX",
+                   help="distance between neighbouring windows of --canvas in pixels: a multiple of 8 x --f, at most the window "
+                        "(default: half the window)")
     add_guidance_arguments(p)
     return p
 
@@ -184,6 +194,36 @@ def report_guidance(sampler, indices, tag=""):
               % (tag, i, res["energy"][0, j].item(), res["energy"][-1, j].item(), len(res["calls"]), res["skipped"]))
 
 
+def canvas_grid(opt):
+    """The sta.canvas.Grid of --canvas / --canvas_stride in latent pixels, or None without --canvas; every refusal that needs no GPU."""
+    if opt.canvas is None:
+        if opt.canvas_stride is not None:
+            raise SystemExit("--canvas_stride %d needs --canvas HxW" % opt.canvas_stride)
+        return None
+    parts = opt.canvas.lower().split("x")
+    if len(parts) != 2 or not all(v.isdigit() for v in parts):
+        raise SystemExit("--canvas %s: expected HxW in pixels, e.g. 512x2048" % opt.canvas)
+    Hpx, Wpx = int(parts[0]), int(parts[1])
+    unit = 8 * opt.f
+    if opt.H != opt.W:
+        raise SystemExit("--canvas is sampled as square windows: --H %d and --W %d differ" % (opt.H, opt.W))
+    stride = opt.H // 2 if opt.canvas_stride is None else opt.canvas_stride
+    for name, v in (("--canvas height", Hpx), ("--canvas width", Wpx), ("--H / --W", opt.H), ("--canvas_stride", stride)):
+        if v <= 0 or v % unit:
+            raise SystemExit("%s %d is not a positive multiple of %d pixels (8 x --f %d)" % (name, v, unit, opt.f))
+    if opt.opt_epochs > 1:
+        raise SystemExit("--canvas samples with fixed blend weights: --opt_epochs %d tracks epochs, and the loss front end takes square "
+                         "images (use --opt_epochs 0)" % opt.opt_epochs)
+    for flag, on in (("--attn_maps", opt.attn_maps), ("--attn_loss", opt.attn_loss is not None), ("--attn_guidance", opt.attn_guidance is not None)):
+        if on:
+            raise SystemExit("%s reads one square image's attention maps and is not defined on a --canvas" % flag)
+    from sta import canvas
+    try:
+        return canvas.window_grid(Hpx // opt.f, Wpx // opt.f, opt.H // opt.f, stride // opt.f)
+    except ValueError as e:
+        raise SystemExit("--canvas %s (latent pixels): %s" % (opt.canvas, e))
+
+
 def builtin_clip(opt):
     """What follows `builtin:` in --clip when the fidelity loss will be evaluated (opt_epochs > 1), else None."""
     if opt.opt_epochs > 1 and opt.clip and opt.clip.startswith("builtin:"):
@@ -237,6 +277,7 @@ def check_options(opt):
         raise SystemExit("--mxfp8 and --fp8 are exclusive")
     if opt.mxfp8 and opt.opt_epochs > 0:
         raise SystemExit("--mxfp8 is an inference option: use --opt_epochs 0")
+    canvas_grid(opt)
     check_clip_option(opt, (opt.H, opt.W))
     check_attn_option(opt)
 
@@ -378,7 +419,26 @@ def run(kind, default_dataset):
         report_attn(group)
         report_guidance(sampler, [i for i, _, _ in group], "[rank %d] " % rank)
 
+    grid = canvas_grid(opt)
+
+    def run_canvases(group):
+        """--canvas: the prompts of `group` (same object count) as P canvases in one CFG batch of 2 P T window rows per UNet call; every
+        canvas keeps the per-prompt start (seed_everything(1) then randn)."""
+        torch.manual_seed(seed)
+        x1 = torch.randn([1, opt.C, grid.Hc, grid.Wc], device=dev)
+        conds = [conditionings(model, p, list(l.keys()), dtype) for _, p, l in group]
+        print("[rank %d] Start inference for prompts %s on a %s canvas (%d windows each)" % (rank, [i for i, _, _ in group], opt.canvas, grid.T))
+        sampler.sample_canvas(S=opt.ddim_steps, canvas=(grid.Hc, grid.Wc), window=grid.s, stride=grid.stride,
+                              conditionings=[c[1] for c in conds], unconditional_conditionings=[c[0] for c in conds],
+                              bboxs=[[l[n] for n in l] for _, _, l in group], object_names=[list(l.keys()) for _, _, l in group],
+                              local_conditionings=[c[2] for c in conds], curr_texts=[p for _, p, _ in group],
+                              x_T=x1.expand(len(group), -1, -1, -1).contiguous(), unconditional_guidance_scale=opt.scale, eta=eta, seed=seed,
+                              prompt_indices=[i for i, _, _ in group], channels=opt.C)
+
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}) for i, p in mine]
+    if grid is not None:
+        run_one = lambda i, p, l: run_canvases([(i, p, l)])
+        run_group = run_canvases
     if opt.batch_prompts <= 1:
         for i, p, l in items:
             run_one(i, p, l)

@@ -1,0 +1,202 @@
+"""Wide and tall canvases sampled as overlapping square windows (MultiDiffusion), host side of csrc/sta_window.hip.
+
+The canvas latent is [P, C, Hc, Wc]. Every UNet call sees T = ny nx square windows of side s of each canvas as T images of one CFG
+batch; the T predictions are averaged where windows overlap and the sampler step runs on the canvas.
+
+Grid: offsets along an axis of length L are 0, stride, 2 stride, ... while o + s <= L, plus L - s if that is not already the last one
+(the last window is clamped to the edge). s, stride, Hc and Wc are multiples of 8 (every window's 2x / 4x / 8x coarser levels lie on the
+canvas's coarse grid, and a lane's 8-element vector never straddles a window edge), s <= Hc, s <= Wc, 8 <= stride <= s (no gaps), at
+most MAX_WINDOW_OFFSETS offsets per axis. Window w = j nx + i has its corner at (oy[j], ox[i]). The UNet batch is canvas-major, then
+window, then (uncond, cond): row 2 (p T + w) + r, the pair layout of PLMSSampler._make_eps_fn and the fused kernels.
+
+Layout: centres are normalised to the canvas (x in [0, 1] of the width, y of the height); window (j, i) gets
+((x Wc - ox[i]) / s, (y Hc - oy[j]) / s), in Python floats, and its blocks rasterise that with the unchanged disc rule (sta.ops.disc_masks):
+the disc has radius 0.2 s latent pixels everywhere, and an object outside a window sets no mask bit there.
+
+Fuse: per canvas element the covering windows are summed in ascending w in fp32, starting from the first one's value, and divided by their
+count with an IEEE fp32 division; a 16-bit result is rounded to nearest even once. One writer per element: bit-reproducible.
+
+`window_split`, `window_fuse` and `sampler_step_windows` run the HIP kernels for CUDA tensors (there is no other GPU path) and the torch
+restatements `window_split_reference`, `window_fuse_reference`, `step_windows_reference` for CPU tensors (explicit loops over the windows
+in ascending order): the restatements are what the kernels are tested against and what the CPU suite's sampler tests run on.
+"""
+import ctypes
+from collections import namedtuple
+
+import torch
+
+from sta import lib, solver
+
+MAX_WINDOW_OFFSETS = lib.MAX_WINDOW_OFFSETS
+Grid = namedtuple("Grid", "Hc Wc s stride oy ox ny nx T")
+_DT = solver._DT
+
+
+# ---------------------------------------------------------------------------------------------------- grid and layout
+def _offsets(L, s, stride):
+    o = list(range(0, L - s + 1, stride))
+    if o[-1] != L - s:
+        o.append(L - s)
+    return tuple(o)
+
+
+def window_grid(Hc, Wc, s, stride):
+    """The window grid of an Hc x Wc canvas latent (sides in latent pixels) -> Grid(Hc, Wc, s, stride, oy, ox, ny, nx, T)."""
+    Hc, Wc, s, stride = int(Hc), int(Wc), int(s), int(stride)
+    for name, v in (("window side s", s), ("stride", stride), ("canvas height Hc", Hc), ("canvas width Wc", Wc)):
+        if v <= 0 or v % 8:
+            raise ValueError("%s = %d is not a positive multiple of 8 (canvas %d x %d, window %d, stride %d)" % (name, v, Hc, Wc, s, stride))
+    if s > Hc or s > Wc:
+        raise ValueError("the canvas %d x %d is smaller than the window %d" % (Hc, Wc, s))
+    if stride > s:
+        raise ValueError("stride %d > window %d would leave gaps between windows" % (stride, s))
+    oy, ox = _offsets(Hc, s, stride), _offsets(Wc, s, stride)
+    if len(oy) > MAX_WINDOW_OFFSETS or len(ox) > MAX_WINDOW_OFFSETS:
+        raise ValueError("canvas %d x %d with window %d and stride %d needs %d x %d window offsets; at most %d per axis"
+                         % (Hc, Wc, s, stride, len(oy), len(ox), MAX_WINDOW_OFFSETS))
+    return Grid(Hc, Wc, s, stride, oy, ox, len(oy), len(ox), len(oy) * len(ox))
+
+
+def windows(grid):
+    """[(oy[j], ox[i])] in window order w = j nx + i."""
+    return [(y0, x0) for y0 in grid.oy for x0 in grid.ox]
+
+
+def window_centres(centres, grid):
+    """Canvas-normalised centres [(x, y)] -> per window (in window order) the list of that window's centres."""
+    return [[[(float(x) * grid.Wc - x0) / grid.s, (float(y) * grid.Hc - y0) / grid.s] for x, y in centres] for y0, x0 in windows(grid)]
+
+
+def cover_count(grid):
+    """[Hc, Wc] int32: how many windows cover each canvas element (>= 1 everywhere)."""
+    n = torch.zeros((grid.Hc, grid.Wc), dtype=torch.int32)
+    for y0, x0 in windows(grid):
+        n[y0:y0 + grid.s, x0:x0 + grid.s] += 1
+    return n
+
+
+# ---------------------------------------------------------------------------------------------------- torch restatements
+def _canvases(n_rows, rows, what):
+    if n_rows % rows:
+        raise ValueError("%s holds %d images, not a multiple of %d" % (what, n_rows, rows))
+    return n_rows // rows
+
+
+def window_split_reference(src, grid, dtype=None, rows=1):
+    """src [P rows, C, Hc, Wc] -> [2 P T, C, s, s] in `dtype` (default: src's). rows = 1: canvas states, to both rows of each window's
+    pair; rows = 2: input pairs, row r to row r."""
+    if rows not in (1, 2) or tuple(src.shape[-2:]) != (grid.Hc, grid.Wc):
+        raise ValueError("window_split: src %s, rows %s for a %d x %d canvas" % (tuple(src.shape), rows, grid.Hc, grid.Wc))
+    P, C, s = _canvases(src.shape[0], rows, "src"), src.shape[1], grid.s
+    v = src.to(dtype or src.dtype).reshape(P, rows, C, grid.Hc, grid.Wc)
+    out = torch.empty((P, grid.T, 2, C, s, s), dtype=v.dtype, device=src.device)
+    for w, (y0, x0) in enumerate(windows(grid)):
+        for r in range(2):
+            out[:, w, r] = v[:, r if rows == 2 else 0, :, y0:y0 + s, x0:x0 + s]
+    return out.reshape(2 * P * grid.T, C, s, s)
+
+
+def _fuse32(eps, grid):
+    """eps [2 P T, C, s, s] -> the overlap mean [2 P, C, Hc, Wc] in fp32, not rounded."""
+    s = grid.s
+    if tuple(eps.shape[-2:]) != (s, s):
+        raise ValueError("window_fuse: eps %s for windows of side %d" % (tuple(eps.shape), s))
+    P, C = _canvases(eps.shape[0], 2 * grid.T, "eps"), eps.shape[1]
+    e = eps.reshape(P, grid.T, 2, C, s, s)
+    acc = torch.zeros((P, 2, C, grid.Hc, grid.Wc), dtype=torch.float32, device=eps.device)
+    seen = torch.zeros((grid.Hc, grid.Wc), dtype=torch.bool, device=eps.device)
+    for w, (y0, x0) in enumerate(windows(grid)):
+        v = e[:, w].to(torch.float32)
+        region = acc[..., y0:y0 + s, x0:x0 + s]
+        region.copy_(torch.where(seen[y0:y0 + s, x0:x0 + s], region + v, v))      # the first covering window's value starts the sum
+        seen[y0:y0 + s, x0:x0 + s] = True
+    return (acc / cover_count(grid).to(eps.device, torch.float32)).reshape(2 * P, C, grid.Hc, grid.Wc)
+
+
+def window_fuse_reference(eps, grid, dtype=None):
+    """eps [2 P T, C, s, s] -> [2 P, C, Hc, Wc] in `dtype` (default: eps's): fp32 sum in ascending w / count, rounded once."""
+    return _fuse32(eps, grid).to(dtype or eps.dtype)
+
+
+def step_windows_reference(eps, x, m_prev, noise, c, grid, dtype=None, want_xin=False):
+    """solver.step_reference on the fp32 overlap means of the windows' UNet output -> (x_next, m, xin): x, m_prev, noise, x_next, m are
+    canvas tensors [P, C, Hc, Wc]; xin (want_xin) = window_split_reference(x_next) in `dtype` (default: eps's)."""
+    x_next, m = solver.step_reference(_fuse32(eps, grid), x, m_prev, noise, c)
+    return x_next, m, (window_split_reference(x_next, grid, dtype or eps.dtype) if want_xin else None)
+
+
+# ---------------------------------------------------------------------------------------------------- HIP entry points
+_TABLES = {}
+
+
+def _grid_args(grid):
+    """(ny, nx, oy, ox, s) as the C-ABI takes them; the host offset arrays are kept per grid."""
+    key = (grid.oy, grid.ox)
+    if key not in _TABLES:
+        _TABLES[key] = ((ctypes.c_int * grid.ny)(*grid.oy), (ctypes.c_int * grid.nx)(*grid.ox))
+    oy, ox = _TABLES[key]
+    return grid.ny, grid.nx, ctypes.addressof(oy), ctypes.addressof(ox), grid.s
+
+
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def window_split(src, grid, dtype=None, rows=1):
+    """window_split_reference on the GPU (sta_window_split): src float32 or already `dtype`, the UNet's 16-bit type."""
+    if not src.is_cuda:
+        return window_split_reference(src, grid, dtype, rows)
+    dtype = dtype or src.dtype
+    if dtype not in _DT or src.dtype not in (torch.float32, dtype):
+        raise TypeError("sta_window_split writes 16-bit window inputs from float32 or the same 16-bit type (src %s, dtype %s)" % (src.dtype, dtype))
+    if rows not in (1, 2) or src.dim() != 4 or tuple(src.shape[-2:]) != (grid.Hc, grid.Wc):
+        raise ValueError("window_split: src %s, rows %s for a %d x %d canvas" % (tuple(src.shape), rows, grid.Hc, grid.Wc))
+    P, C = _canvases(src.shape[0], rows, "src"), src.shape[1]
+    src = src.detach().contiguous()
+    xin = torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=src.device)
+    lib.check(lib.load().sta_window_split(src.data_ptr(), xin.data_ptr(), P, rows, C, grid.Hc, grid.Wc, *_grid_args(grid),
+                                          lib.STA_SRC_F32 if src.dtype == torch.float32 else _DT[dtype], _DT[dtype], _stream(src)),
+              "sta_window_split")
+    return xin
+
+
+def window_fuse(eps, grid):
+    """window_fuse_reference on the GPU (sta_window_fuse): eps 16-bit, the result in the same type."""
+    if not eps.is_cuda:
+        return window_fuse_reference(eps, grid)
+    if eps.dtype not in _DT:
+        raise TypeError("sta_window_fuse takes the UNet's 16-bit output, got %s" % eps.dtype)
+    if eps.dim() != 4 or tuple(eps.shape[-2:]) != (grid.s, grid.s):
+        raise ValueError("window_fuse: eps %s for windows of side %d" % (tuple(eps.shape), grid.s))
+    P, C = _canvases(eps.shape[0], 2 * grid.T, "eps"), eps.shape[1]
+    eps = eps.detach().contiguous()
+    out = torch.empty((2 * P, C, grid.Hc, grid.Wc), dtype=eps.dtype, device=eps.device)
+    lib.check(lib.load().sta_window_fuse(eps.data_ptr(), out.data_ptr(), P, C, grid.Hc, grid.Wc, *_grid_args(grid), _DT[eps.dtype],
+                                         _stream(eps)), "sta_window_fuse")
+    return out
+
+
+def sampler_step_windows(eps, x, m_prev, noise, c, grid, dtype=None, want_xin=False):
+    """One sampler step on a canvas after a CFG UNet call on its windows -> (x_next, m, xin): eps [2 P T, C, s, s] 16-bit, x / m_prev /
+    noise [P, C, Hc, Wc] float32 (m_prev / noise may be None), c a solver.StepCoef; xin (want_xin): the next call's window input pairs.
+    CUDA: one sta_sampler_step_windows launch (no autograd: canvases are sampled with fixed weights); CPU: step_windows_reference."""
+    if not x.is_cuda:
+        return step_windows_reference(eps, x, m_prev, noise, c, grid, dtype, want_xin)
+    if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
+        raise ValueError("sampler_step_windows: the state must be a float32 [P, C, %d, %d] canvas, got %s %s" % (grid.Hc, grid.Wc, x.dtype, tuple(x.shape)))
+    if eps.dtype not in _DT:
+        raise TypeError("sta_sampler_step_windows takes the UNet's 16-bit output, got %s" % eps.dtype)
+    P, C = x.shape[0], x.shape[1]
+    if tuple(eps.shape) != (2 * P * grid.T, C, grid.s, grid.s):
+        raise ValueError("eps %s must be the window pair batch [%d, %d, %d, %d] of x %s" % (tuple(eps.shape), 2 * P * grid.T, C, grid.s, grid.s, tuple(x.shape)))
+    if c.c_p and m_prev is None or c.c_n and noise is None:
+        raise ValueError("c_p / c_n != 0 need m_prev / noise")
+    f = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+    eps, x, m_prev, noise = eps.detach().contiguous(), x.detach().contiguous(), f(m_prev if c.c_p else None), f(noise if c.c_n else None)
+    x_next, m = torch.empty_like(x), torch.empty_like(x)
+    xin = torch.empty_like(eps) if want_xin else None
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    lib.check(lib.load().sta_sampler_step_windows(eps.data_ptr(), x.data_ptr(), ptr(m_prev), ptr(noise), x_next.data_ptr(), m.data_ptr(),
+                                                  ptr(xin), P, C, grid.Hc, grid.Wc, *_grid_args(grid), c.scale, c.sigma_t, c.alpha_t, c.c_x,
+                                                  c.c_m, c.c_p, c.c_e, c.c_n, _DT[eps.dtype], _stream(x)), "sta_sampler_step_windows")
+    return x_next, m, xin

@@ -22,7 +22,10 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # shares its flags (-ffinite-math-only) and its pass through the hazard lint. sta_xattn_maps_bwd.hip (sta_xattn_token_maps_bwd) is the
 # backward of the token-map readout and is built with the cross-attention backward; sta_guide.hip (sta_latent_guide) is the latent update of
 # attention-guided sampling and is built with the sampler step, whose helpers it uses (no -ffinite-math-only there: it tests for Inf / NaN).
-INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip"}
+# sta_window.hip (sta_window_split / sta_window_fuse / sta_sampler_step_windows: canvases sampled as overlapping windows) repeats the sampler
+# step's arithmetic on overlap means and is built with it for the same reason: same helpers, and no fast-math flag (its mean is a
+# correctly rounded fp32 division).
+INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_window.hip": "sta_sampler.hip"}
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -39,7 +42,10 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 # Kernels built to the last register of their occupancy: {translation unit: substrings of the kernel names}. build() refuses a toolchain
 # that spills one (a spilled B fragment is a scratch round trip per MFMA: the pass would be slower than the pair it replaces).
 # (sta_conv.hip: the sub-pixel instantiations conv3x3_nhwc_kernel<T, GEO, NTW, true> — "Lb1E" is the mangled `true`)
-NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",)}
+# (sta_sampler.hip: the window kernels index offset tables that arrive by value in the kernel arguments; a toolchain that copies the
+# tables to scratch to index them is refused)
+NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",),
+                    "sta_sampler.hip": ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel")}
 
 STA_BF16, STA_F16 = 0, 1
 STA_MX8_GEGLU, STA_MX8_MX_OUT = 1, 2
@@ -48,6 +54,7 @@ FWD_STAGED, FWD_SPLIT = 1, 2
 MAX_KEYS, MAX_HEAD_DIM, MAX_OBJECTS = 80, 160, 8
 P3_STATS_WORDS = 8
 MAX_READOUTS = 16
+MAX_WINDOW_OFFSETS, STA_SRC_F32 = 16, 2
 
 # every symbol include/sta_xattn.h and include/sta_unet.h declare: (restype, argtypes)
 _vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
@@ -143,6 +150,9 @@ SYMBOLS = {
     "sta_image_composite": (_i, [_vp] * 4 + [_l, _l, _i, _vp]),
     "sta_image_composite_bwd": (_i, [_vp] * 4 + [_l, _l, _i, _vp]),
     "sta_latent_guide": (_i, [_vp] * 7 + [_l, _l, _l, _i, _f, _i, _vp]),
+    "sta_window_split": (_i, [_vp, _vp, _l] + [_i] * 6 + [_vp, _vp] + [_i] * 3 + [_vp]),
+    "sta_window_fuse": (_i, [_vp, _vp, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp]),
+    "sta_sampler_step_windows": (_i, [_vp] * 7 + [_l] + [_i] * 5 + [_vp, _vp, _i] + [_f] * 8 + [_i, _vp]),
 }
 
 

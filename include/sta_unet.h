@@ -365,6 +365,34 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
                      long hw, int normalize, float inv_scale, int dtype, void* stream);
 
 /*
+ * Wide canvases sampled as overlapping square windows, the MultiDiffusion way (csrc/sta_window.hip). The canvas latent is [P][C][Hc][Wc];
+ * every UNet call sees T = ny nx square windows of side s of each canvas as T images of one CFG batch. Window w = j nx + i has its corner
+ * at (oy[j], ox[i]); the UNet batch is canvas-major, then window, then (uncond, cond): row 2 (p T + w) + r.
+ *   ny, nx, oy, ox, s: the grid; oy / ox are HOST arrays of ny / nx offsets (copied into the kernel arguments: no device-side table).
+ * Rules (STA_E_ARG with text, nothing launched): non-NULL 16-byte aligned tensors, non-NULL oy / ox; s, Hc, Wc and every offset multiples
+ * of 8 (a lane's 8 elements never straddle a window edge), 8 <= s <= Hc, Wc; 1 .. STA_MAX_WINDOW_OFFSETS offsets per axis, the first 0,
+ * ascending, consecutive ones at most s apart and the last window ending at the canvas edge (no gap); dtype STA_BF16 / STA_F16.
+ * Every canvas element is owned by one lane that visits its covering windows in ascending w: no atomics, no LDS, bit-reproducible.
+ *
+ * sta_window_split: src [P rows][C][Hc][Wc] -> xin [2 P T][C][s][s] dtype. rows = 1: canvas states, written to both rows of every window's
+ *   pair; rows = 2: an input pair tensor, row r to row r. src_dtype: STA_SRC_F32 (rounded to nearest even once) or dtype itself (copied).
+ * sta_window_fuse: eps [2 P T][C][s][s] dtype -> out [2 P][C][Hc][Wc] dtype: per element the covering windows' values summed in fp32 in
+ *   ascending w, starting from the first one's value, divided by their count (IEEE fp32 division), rounded to nearest even once.
+ * sta_sampler_step_windows: sta_sampler_step on the two overlap means of eps (fp32, NOT rounded to dtype), the same expressions in the
+ *   same order; x, m_prev, noise, x_next, m: [P][C][Hc][Wc] fp32 (m_prev / noise may be NULL); xin: NULL, or [2 P T][C][s][s] dtype =
+ *   the rounded x_next in both rows of every covering window, the next UNet call's input. With T = 1 bit-equal to sta_sampler_step.
+ */
+#define STA_MAX_WINDOW_OFFSETS 16
+#define STA_SRC_F32 2
+int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                     int src_dtype, int dtype, void* stream);
+int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int dtype,
+                    void* stream);
+int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin, long P,
+                             int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t,
+                             float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream);
+
+/*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
  * of its patch-embedding GEMM, and the gradient of the image from the gradient of those rows.
  *   img:   [B][3][H][W] fp32 in [0, 1] (the clamped decoder output);
