@@ -9,6 +9,7 @@
 #include "sta_xattn.h"
 #include "sta_unet.h"
 #include "sta_internal.h"
+#include "sta_blend_dev.h"      // blend1: shared with the canvas kernels of sta_window.hip
 
 namespace {
 
@@ -38,12 +39,6 @@ __device__ __forceinline__ void store8(float* p, const float* v) {
   }
   *(F4*)p = a;
   *(F4*)(p + 4) = b;
-}
-
-// keep (q_a x0 + q_b n) + (1 - keep) x; keep == 0 hands x through untouched (bit-equal to the unmasked step, signed zeros included)
-__device__ __forceinline__ float blend1(float kp, float x0, float n, float x, float q_a, float q_b) {
-  const float q = q_a * x0 + q_b * n;
-  return kp == 0.f ? x : kp * q + (1.0f - kp) * x;
 }
 
 // sta_sampler_step's arithmetic for call i (same expressions, same order), then the blend of call i + 1 on x_next.

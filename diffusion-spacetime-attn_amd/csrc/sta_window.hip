@@ -1,11 +1,15 @@
 // sta_window.hip — wide canvases sampled as overlapping square windows (gfx950). C-ABI in include/sta_unet.h (sta_window_split /
-// sta_window_fuse / sta_sampler_step_windows). #included at the end of sta_sampler.hip (its V8T / F4 / load8 / store8 / StepCoef, its
+// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend). #included at the end of sta_sampler.hip (its V8T / F4 / load8 / store8 / StepCoef, its
 // flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division).
 // Conventions of sta_sampler.hip: 256-lane groups, grid-stride, a lane owns 8 consecutive elements of one CANVAS row, 16-byte loads and
 // stores, fp32 arithmetic. Window sides, offsets and canvas sides are multiples of 8, so a lane's vector lies inside or outside a window
 // as a whole. The offset tables travel by value in the kernel arguments: nothing device-side to fill, the launches are capturable.
 // A canvas element is owned by exactly one lane, which visits the windows that cover it in ascending w = j nx + i: no atomics, no LDS,
 // one writer per output element, the same bits from launch to launch.
+// Inpainting on a canvas (sta_sampler_step_windows_masked / sta_window_blend): the blend is blend1 of sta_blend_dev.h, the definition
+// sta_inpaint.hip uses for square images.
+
+#include "sta_blend_dev.h"
 
 namespace {
 
@@ -152,6 +156,82 @@ __global__ __launch_bounds__(256) void sampler_step_windows_kernel(const T* __re
   }
 }
 
+// first element of the lane's vector in a [P][Hc][Wc] mask, broadcast over the channels
+__device__ __forceinline__ long mask_at(const CanvasPos& q, int Hc, int Wc) { return (q.row * Hc + q.y) * (long)Wc + q.x; }
+
+// sampler_step_windows_kernel for call i (the same expressions in the same order), then the inpainting blend of call i + 1 on x_next
+// (blend1 of sta_blend_dev.h, as sampler_step_masked_kernel): x0 / qnoise canvas-shaped, keep [P][Hc][Wc]; m is the unblended data
+// prediction; xin (null = not written): the rounded BLENDED x_next to both rows of every covering window. MP / NZ: m_prev / noise are
+// given — compile-time here, since the three extra streams leave no scalar registers for the run-time tests' masks
+template <typename T, bool MP, bool NZ>
+__global__ __launch_bounds__(256) void sampler_step_windows_masked_kernel(const T* __restrict__ eps, const float* __restrict__ x,
+                                                                          const float* __restrict__ m_prev, const float* __restrict__ noise,
+                                                                          const float* __restrict__ x0, const float* __restrict__ keep,
+                                                                          const float* __restrict__ qnoise, float* __restrict__ x_next,
+                                                                          float* __restrict__ m, T* __restrict__ xin, long nvec, int C, int Hc,
+                                                                          int Wc, WinGrid g, StepCoef c, float q_a, float q_b) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
+    float eu[8] = {}, ec[8] = {};
+    const float cnt = (float)gather_sum<T>(eps, g, q.row, 0, C, q, eu);
+    gather_sum<T>(eps, g, q.row, 1, C, q, ec);
+    float xv[8], mp[8], nz[8], xn[8], mv[8], z0[8], kp[8], qn[8];
+    load8(x + 8 * v, xv);
+    if constexpr (MP) load8(m_prev + 8 * v, mp);
+    if constexpr (NZ) load8(noise + 8 * v, nz);
+    load8(x0 + 8 * v, z0);
+    load8(qnoise + 8 * v, qn);
+    load8(keep + mask_at(q, Hc, Wc), kp);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float u = eu[k] / cnt;
+      const float e = u + c.scale * (ec[k] / cnt - u);
+      mv[k] = (xv[k] - c.sigma_t * e) / c.alpha_t;
+      float t = c.c_x * xv[k] + c.c_m * mv[k] + c.c_e * e;
+      if constexpr (MP) t += c.c_p * mp[k];
+      if constexpr (NZ) t += c.c_n * nz[k];
+      xn[k] = blend1(kp[k], z0[k], qn[k], t, q_a, q_b);
+    }
+    store8(x_next + 8 * v, xn);
+    store8(m + 8 * v, mv);
+    if (xin) {
+      V8 o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = (T)xn[k];
+      scatter<T>(xin, g, q.row, 0, 1, C, q, o);
+    }
+  }
+}
+
+// the blend of the first call on a canvas, then the split: latent_blend_kernel and window_split_kernel (rows = 1) in one pass
+template <typename T>
+__global__ __launch_bounds__(256) void window_blend_kernel(const float* __restrict__ x, const float* __restrict__ x0,
+                                                           const float* __restrict__ keep, const float* __restrict__ noise,
+                                                           float* __restrict__ x_out, T* __restrict__ xin, long nvec, int C, int Hc, int Wc,
+                                                           WinGrid g, float q_a, float q_b) {
+  using V8 = typename V8T<T>::type;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
+    float xv[8], z0[8], kp[8], qn[8], xo[8];
+    load8(x + 8 * v, xv);
+    load8(x0 + 8 * v, z0);
+    load8(noise + 8 * v, qn);
+    load8(keep + mask_at(q, Hc, Wc), kp);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) xo[k] = blend1(kp[k], z0[k], qn[k], xv[k], q_a, q_b);
+    store8(x_out + 8 * v, xo);
+    if (xin) {
+      V8 o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = (T)xo[k];
+      scatter<T>(xin, g, q.row, 0, 1, C, q, o);
+    }
+  }
+}
+
 // offsets along one axis of length L: 0 first, multiples of 8, ascending, no gap (step <= s), the last window ends at L
 int window_axis_ok(const char* what, const char* axis, int n, const int* o, int s, int L) {
   if (n < 1 || n > STA_MAX_WINDOW_OFFSETS) return sta_fail(STA_E_ARG, "%s: n%s=%d (need 1 .. %d offsets)", what, axis, n, STA_MAX_WINDOW_OFFSETS);
@@ -236,6 +316,50 @@ int sta_sampler_step_windows(const void* eps, const float* x, const float* m_pre
     using T = decltype(tag);
     return sta_launch<sampler_step_windows_kernel<T>>("sampler_step_windows", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
                                                       (const T*)eps, x, m_prev, noise, x_next, m, (T*)xin, nvec, C, Hc, Wc, g, c);
+  });
+}
+
+int sta_sampler_step_windows_masked(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
+                                    const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc,
+                                    int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t, float alpha_t, float c_x,
+                                    float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!eps || !x || !x_next || !m) return sta_fail(STA_E_ARG, "null pointer");
+  if (!x0 || !keep || !qnoise) return sta_fail(STA_E_ARG, "sampler_step_windows_masked: x0, keep and qnoise are required (null pointer)");
+  WinGrid g;
+  if (const int rc = window_grid_ok("sampler_step_windows_masked", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
+  if (!sta_aligned16(eps) || !sta_aligned16(x) || !sta_aligned16(m_prev) || !sta_aligned16(noise) || !sta_aligned16(x0) || !sta_aligned16(keep) ||
+      !sta_aligned16(qnoise) || !sta_aligned16(x_next) || !sta_aligned16(m) || !sta_aligned16(xin))
+    return sta_fail(STA_E_ARG, "sampler_step_windows_masked: every tensor must be 16-byte aligned");
+  if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_windows_masked: alpha_t == 0");
+  const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
+  const long nvec = P * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    auto launch = [&](auto mp, auto nz) {
+      return sta_launch<sampler_step_windows_masked_kernel<T, decltype(mp)::value, decltype(nz)::value>>(
+          "sampler_step_windows_masked", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)eps, x, m_prev, noise, x0, keep,
+          qnoise, x_next, m, (T*)xin, nvec, C, Hc, Wc, g, c, q_a, q_b);
+    };
+    using Yes = std::true_type;
+    using No = std::false_type;
+    return m_prev ? (noise ? launch(Yes{}, Yes{}) : launch(Yes{}, No{})) : (noise ? launch(No{}, Yes{}) : launch(No{}, No{}));
+  });
+}
+
+int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
+                     int Wc, int ny, int nx, const int* oy, const int* ox, int s, float q_a, float q_b, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!x || !x0 || !keep || !noise || !x_out) return sta_fail(STA_E_ARG, "window_blend: null pointer");
+  WinGrid g;
+  if (const int rc = window_grid_ok("window_blend", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
+  if (!sta_aligned16(x) || !sta_aligned16(x0) || !sta_aligned16(keep) || !sta_aligned16(noise) || !sta_aligned16(x_out) || !sta_aligned16(xin))
+    return sta_fail(STA_E_ARG, "window_blend: every tensor must be 16-byte aligned");
+  const long nvec = P * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return sta_launch<window_blend_kernel<T>>("window_blend", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, x, x0, keep, noise,
+                                              x_out, (T*)xin, nvec, C, Hc, Wc, g, q_a, q_b);
   });
 }
 

@@ -39,6 +39,7 @@ class DDIMSampler(SolverSamplerBase):
         if ddim_discretize != "uniform":
             raise NotImplementedError("only the uniform DDIM discretisation is on this path")
         self.tables = solver.ddim_tables(self.model.alphas_cumprod, ddim_num_steps, eta=ddim_eta)
+        self._acp_host = self.model.alphas_cumprod.detach().to("cpu", torch.float32)      # _blend_coefs: no device read per call
         self.ddim_timesteps = self.tables["timesteps"]
         self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas = self.tables["a"], self.tables["a_prev"], self.tables["sigma"]
         if verbose:
@@ -48,7 +49,7 @@ class DDIMSampler(SolverSamplerBase):
         return solver.ddim_coefs(self.tables, i, scale)
 
     def _blend_coefs(self, i):
-        return solver.blend_coefs(self.model.alphas_cumprod, int(self.tables["t_in"][i]))     # q_sample at the call's integer timestep
+        return solver.blend_coefs(self._acp_host, int(self.tables["t_in"][i]))     # q_sample at the call's integer timestep
 
     def _noise(self, i, x):
         if self.noise is None:

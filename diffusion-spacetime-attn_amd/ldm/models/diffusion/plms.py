@@ -317,7 +317,7 @@ class PLMSSampler(object):
                            object_names=list(object_names), local_conditionings=list(local_conditionings), batched=True)
         return None
 
-    _canvas = None               # the sta.canvas.Grid while sample_canvas runs (set like _start / _inpaint, cleared in `finally`)
+    _canvas = None               # the sta.canvas.Grid while sample_canvas / inpaint_canvas runs (set like _start / _inpaint, cleared in `finally`)
     canvas_fused_step = True     # step-kernel samplers on a canvas: one sta_sampler_step_windows launch per call (False: fuse + step + split)
 
     def sample_canvas(self, S, canvas, window, stride=None, conditionings=None, unconditional_conditionings=None, bboxs=None,
@@ -333,29 +333,46 @@ class PLMSSampler(object):
         `last_result`: x0 [P, channels, Hc, Wc], image [P, 3, 8 Hc, 8 Wc] from ONE decode of the whole canvas, W [P, K, S].
         Fixed weights only. ValueError before any UNet call for opt_epochs > 1 (the loss front end takes square images:
         sta.clip.check_view_shapes), an attached attn_capture, attn_loss or latent_guidance, mask= / x0= (inpainting) and a non-zero
-        `_start` (img2img decodes): none of them is defined on a canvas yet."""
+        `_start` (img2img decodes): none of them is defined on a canvas by this method (inpainting: `inpaint_canvas` of the step-kernel
+        samplers)."""
+        if mask is not None or x0 is not None:
+            raise ValueError("sample_canvas: mask= / x0= (inpainting) is not defined on a canvas (see inpaint_canvas)")
+        return self._sample_canvas("sample_canvas", S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
+                                   local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices, curr_texts, channels,
+                                   verbose)
+
+    def inpaint_canvas(self, S, canvas, window, stride=None, *, mask=None, x0=None, image=None, mask_px=None, **kwargs):
+        """Inpainting / outpainting on a canvas: the step-kernel samplers only (SolverSamplerBase.inpaint_canvas), as `sample(mask=)`."""
+        raise NotImplementedError("inpainting / quantisation / score correction are not on this path (masked PLMS is not supported: "
+                                  "inpaint_canvas runs on DDIMSampler and DPMSolverSampler)")
+
+    def _sample_canvas(self, what, S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
+                       local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices, curr_texts, channels, verbose,
+                       prepare=None):
+        """The body of sample_canvas and inpaint_canvas: every refusal, then the epoch loop on the canvas with `_canvas` set.
+        prepare(P, channels, grid): the caller's own checks and state once the canvas is known (inpaint_canvas: the inpaint state)."""
         from sta import canvas as _cv
         if self.opt_epochs > 1:
-            raise ValueError("sample_canvas samples with fixed blend weights: opt_epochs = %d tracks epochs, and the loss front end "
-                             "takes square images (use opt_epochs 0)" % self.opt_epochs)
+            raise ValueError("%s samples with fixed blend weights: opt_epochs = %d tracks epochs, and the loss front end "
+                             "takes square images (use opt_epochs 0)" % (what, self.opt_epochs))
         for name in ("attn_capture", "attn_loss", "latent_guidance"):
             if getattr(self, name) is not None:
-                raise ValueError("sample_canvas: an attached %s reads one square image's attention maps; detach it for canvases" % name)
-        if mask is not None or x0 is not None:
-            raise ValueError("sample_canvas: mask= / x0= (inpainting) is not defined on a canvas")
+                raise ValueError("%s: an attached %s reads one square image's attention maps; detach it for canvases" % (what, name))
         if getattr(self, "_start", 0):
-            raise ValueError("sample_canvas: a trajectory that starts at call %d (img2img) is not defined on a canvas" % self._start)
+            raise ValueError("%s: a trajectory that starts at call %d (img2img) is not defined on a canvas" % (what, self._start))
         Hc, Wc = canvas
         grid = _cv.window_grid(Hc, Wc, window, window // 2 if stride is None else stride)
         P = len(conditionings)
         if not (len(bboxs) == len(object_names) == len(local_conditionings) == P):
-            raise ValueError("sample_canvas takes per-canvas lists of equal length (%d conditionings, %d bboxs, %d object_names, %d "
-                             "local_conditionings)" % (P, len(bboxs), len(object_names), len(local_conditionings)))
+            raise ValueError("%s takes per-canvas lists of equal length (%d conditionings, %d bboxs, %d object_names, %d "
+                             "local_conditionings)" % (what, P, len(bboxs), len(object_names), len(local_conditionings)))
         if x_T is not None and tuple(x_T.shape) != (P, channels, grid.Hc, grid.Wc):
             raise ValueError("x_T %s must be [%d, %d, %d, %d]" % (tuple(x_T.shape), P, channels, grid.Hc, grid.Wc))
         cond = torch.cat(list(conditionings))
         uncond = torch.cat(list(unconditional_conditionings)) if isinstance(unconditional_conditionings, (list, tuple)) \
             else unconditional_conditionings.expand(P, -1, -1)
+        if prepare is not None:
+            prepare(P, channels, grid)
         self._canvas = grid
         try:
             self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
@@ -733,6 +750,7 @@ class SolverSamplerBase(PLMSSampler):
     Inpainting (`mask=` / `x0=`): sta_latent_blend re-noises the kept region before the first call, and the step of calls
     start .. S - 2 is sta_sampler_step_masked, which blends for the NEXT call in the same launch (tracked: SolverStepMaskedFn); the
     last call takes the plain step. Draw order: blend draw of call i, eta draw of call i, blend draw of call i + 1, ...
+    On a canvas (`inpaint_canvas`) the same with sta_window_blend and sta_sampler_step_windows_masked on canvas-shaped tensors.
     A trajectory may start at call `_start` > 0 (DDIMSampler.decode: img2img): calls _start .. S - 1 run, with columns _start .. S - 1,
     and `_xin0` (if set) is the first call's 16-bit input pair, written by the fused encode step."""
     t_dtype = torch.float32
@@ -828,6 +846,39 @@ class SolverSamplerBase(PLMSSampler):
         finally:
             self._inpaint = None
 
+    def inpaint_canvas(self, S, canvas, window, stride=None, *, mask=None, x0=None, image=None, mask_px=None, conditionings=None,
+                       unconditional_conditionings=None, bboxs=None, object_names=None, local_conditionings=None, x_T=None,
+                       unconditional_guidance_scale=7.5, eta=0.0, seed=1, prompt_indices=None, curr_texts=None, channels=4, verbose=False):
+        """`sample_canvas` with the kept region (mask == 1) of every canvas re-noised from x0 before every UNet call: outpainting (x0 holds
+        an existing picture's latent on its footprint, mask is 1 there) and the repaint of a region of a canvas sampled earlier.
+        mask [P, 1, Hc, Wc] in [0, 1], 1 = keep; x0 [P, channels, Hc, Wc]; image [P, 3, 8 Hc, 8 Wc] in [0, 1] / mask_px [P, 1, 8 Hc, 8 Wc]:
+        the original and its keep mask for the pixel-space paste over the ONE decode of the whole canvas (sta_image_composite); the other
+        keywords are sample_canvas's. On the GPU one sta_window_blend launch runs before call 0, one sta_sampler_step_windows_masked
+        launch after calls 0 .. S - 2 and the plain sta_sampler_step_windows after the last call. The blend draws are canvas-shaped, in
+        the order of `sample(mask=)`: blend draw of call i, eta draw of call i, blend draw of call i + 1, ...
+        ValueError before any UNet call: what sample_canvas refuses, a missing mask or x0, shapes that are not the canvas's, mask values
+        outside [0, 1], image without mask_px or the reverse."""
+        if mask is None or x0 is None:
+            raise ValueError("inpaint_canvas needs both mask= and x0=")
+        if (image is None) != (mask_px is None):
+            raise ValueError("inpaint_canvas: the pixel-space paste needs both image= and mask_px=")
+
+        def prepare(P, channels, grid):
+            self._set_inpaint(mask, x0, image, mask_px, batch=P)
+            inp = self._inpaint
+            want = dict(x0=(P, channels, grid.Hc, grid.Wc), keep=(P, 1, grid.Hc, grid.Wc), image=(P, 3, 8 * grid.Hc, 8 * grid.Wc),
+                        keep_px=(P, 1, 8 * grid.Hc, 8 * grid.Wc))
+            for name, shape in want.items():
+                if inp[name] is not None and tuple(inp[name].shape) != shape:
+                    raise ValueError("inpaint_canvas: %s %s must be [%d, %d, %d, %d] on this canvas"
+                                     % (dict(keep="mask", keep_px="mask_px").get(name, name), tuple(inp[name].shape), *shape))
+        try:
+            return self._sample_canvas("inpaint_canvas", S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs,
+                                       object_names, local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices,
+                                       curr_texts, channels, verbose, prepare=prepare)
+        finally:
+            self._inpaint = None
+
     def _time_range(self):
         return self.tables["t_in"]
 
@@ -882,22 +933,38 @@ class SolverSamplerBase(PLMSSampler):
         window_split; after every UNet call ONE sta_sampler_step_windows launch reads the windows' output, forms the overlap means,
         steps the canvas state and writes the next call's window inputs: x and m_prev stay canvas-shaped, and nothing but the
         (graph-replayed) UNet call and that launch runs per step. `canvas_fused_step = False` takes window_fuse + solver_step +
-        window_split instead (three launches; the means are then rounded to the UNet's type before the step)."""
+        window_split instead (three launches; the means are then rounded to the UNet's type before the step).
+        Inpainting (inpaint_canvas: `_inpaint` set): sta_window_blend re-noises the kept region and writes the first window inputs, and
+        the launch after calls 0 .. S - 2 is sta_sampler_step_windows_masked, which blends for the NEXT call; the last call takes the
+        plain step. Unfused: latent_blend + window_split, then window_fuse + solver_step_masked + window_split."""
         from sta import canvas as _cv
         from sta import solver
         grid, unet = self._window_unet(cond, uncond, scale, bboxs_curr, text_index, graph, img)
         wdtype = next(self.model.model.parameters()).dtype
         S, P, device = len(time_range), img.shape[0], img.device
+        fused, masked = self.canvas_fused_step, self._inpaint is not None
         x, m_prev = img, None
-        xin = _cv.window_split(x, grid, wdtype)
+        if masked and fused:
+            x, xin = _cv.window_blend(x, self._blend(0, x), grid, dtype=wdtype, want_xin=True)
+        else:
+            if masked:
+                x, _ = solver.latent_blend(x, self._blend(0, x), dtype=wdtype)
+            xin = _cv.window_split(x, grid, wdtype)
         for i in range(S):
             t_val = float(time_range[i]) if self.t_dtype.is_floating_point else int(time_range[i])
             out = unet(xin, torch.full((P,), t_val, device=device, dtype=self.t_dtype), W[..., i])
             c = self._coef(i, scale)
-            noise = self._noise(i, x) if c.c_n else None
-            if self.canvas_fused_step:
+            noise = self._noise(i, x) if c.c_n else None           # the eta draw of call i, then the blend draw of call i + 1
+            bl = self._blend(i + 1, x) if masked and i + 1 < S else None       # no blend after the last step
+            if fused and bl is not None:
+                x, m_prev, xin = _cv.sampler_step_windows_masked(out, x, m_prev, noise, c, bl, grid, dtype=wdtype, want_xin=True)
+            elif fused:
                 x, m_prev, xin = _cv.sampler_step_windows(out, x, m_prev, noise, c, grid, dtype=wdtype, want_xin=i + 1 < S)
             else:
-                x, m_prev, _ = solver.solver_step(_cv.window_fuse(out, grid), x, m_prev, noise, c, dtype=wdtype)
+                mean = _cv.window_fuse(out, grid)
+                if bl is not None:
+                    x, m_prev, _ = solver.solver_step_masked(mean, x, m_prev, noise, c, bl, dtype=wdtype)
+                else:
+                    x, m_prev, _ = solver.solver_step(mean, x, m_prev, noise, c, dtype=wdtype)
                 xin = _cv.window_split(x, grid, wdtype) if i + 1 < S else None
         return x

@@ -19,6 +19,10 @@ count with an IEEE fp32 division; a 16-bit result is rounded to nearest even onc
 `window_split`, `window_fuse` and `sampler_step_windows` run the HIP kernels for CUDA tensors (there is no other GPU path) and the torch
 restatements `window_split_reference`, `window_fuse_reference`, `step_windows_reference` for CPU tensors (explicit loops over the windows
 in ascending order): the restatements are what the kernels are tested against and what the CPU suite's sampler tests run on.
+
+Inpainting and outpainting (a solver.Blend with canvas-shaped x0 / noise and keep [P, 1, Hc, Wc]): `window_blend` is the first call's
+blend and the split in one launch (sta_window_blend), `sampler_step_windows_masked` the step of call i with the blend of call i + 1 on
+x_next (sta_sampler_step_windows_masked); restatements `window_blend_reference` and `step_windows_masked_reference`.
 """
 import ctypes
 from collections import namedtuple
@@ -125,6 +129,22 @@ def step_windows_reference(eps, x, m_prev, noise, c, grid, dtype=None, want_xin=
     return x_next, m, (window_split_reference(x_next, grid, dtype or eps.dtype) if want_xin else None)
 
 
+def step_windows_masked_reference(eps, x, m_prev, noise, c, bl, grid, dtype=None, want_xin=False):
+    """step_windows_reference for call i, then solver.blend_reference with the blend `bl` of call i + 1 on x_next -> (blended x_next, the
+    unblended m, xin): bl a solver.Blend with canvas-shaped x0 / noise and keep [P, 1, Hc, Wc]; xin (want_xin) = the split of the
+    BLENDED state."""
+    x_next, m, _ = step_windows_reference(eps, x, m_prev, noise, c, grid)
+    x_next = solver.blend_reference(x_next, bl)
+    return x_next, m, (window_split_reference(x_next, grid, dtype or eps.dtype) if want_xin else None)
+
+
+def window_blend_reference(x, bl, grid, dtype=None, want_xin=False):
+    """The blend of the first call on a canvas state x [P, C, Hc, Wc] -> (x', xin): solver.blend_reference, xin (want_xin) = the split
+    of x' in `dtype` (default: x's)."""
+    xb = solver.blend_reference(x, bl)
+    return xb, (window_split_reference(xb, grid, dtype or x.dtype) if want_xin else None)
+
+
 # ---------------------------------------------------------------------------------------------------- HIP entry points
 _TABLES = {}
 
@@ -182,21 +202,69 @@ def sampler_step_windows(eps, x, m_prev, noise, c, grid, dtype=None, want_xin=Fa
     CUDA: one sta_sampler_step_windows launch (no autograd: canvases are sampled with fixed weights); CPU: step_windows_reference."""
     if not x.is_cuda:
         return step_windows_reference(eps, x, m_prev, noise, c, grid, dtype, want_xin)
+    eps, x, m_prev, noise = _prep_step("sampler_step_windows", eps, x, m_prev, noise, c, grid)
+    P, C = x.shape[0], x.shape[1]
+    x_next, m = torch.empty_like(x), torch.empty_like(x)
+    xin = torch.empty_like(eps) if want_xin else None
+    lib.check(lib.load().sta_sampler_step_windows(eps.data_ptr(), x.data_ptr(), _ptr(m_prev), _ptr(noise), x_next.data_ptr(), m.data_ptr(),
+                                                  _ptr(xin), P, C, grid.Hc, grid.Wc, *_grid_args(grid), c.scale, c.sigma_t, c.alpha_t, c.c_x,
+                                                  c.c_m, c.c_p, c.c_e, c.c_n, _DT[eps.dtype], _stream(x)), "sta_sampler_step_windows")
+    return x_next, m, xin
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def _prep_step(what, eps, x, m_prev, noise, c, grid):
+    """The shape and dtype checks of a step on a canvas -> (eps, x, m_prev, noise) as the kernel takes them (m_prev / noise None where
+    their coefficient is 0)."""
     if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
-        raise ValueError("sampler_step_windows: the state must be a float32 [P, C, %d, %d] canvas, got %s %s" % (grid.Hc, grid.Wc, x.dtype, tuple(x.shape)))
+        raise ValueError("%s: the state must be a float32 [P, C, %d, %d] canvas, got %s %s" % (what, grid.Hc, grid.Wc, x.dtype, tuple(x.shape)))
     if eps.dtype not in _DT:
-        raise TypeError("sta_sampler_step_windows takes the UNet's 16-bit output, got %s" % eps.dtype)
+        raise TypeError("sta_%s takes the UNet's 16-bit output, got %s" % (what, eps.dtype))
     P, C = x.shape[0], x.shape[1]
     if tuple(eps.shape) != (2 * P * grid.T, C, grid.s, grid.s):
         raise ValueError("eps %s must be the window pair batch [%d, %d, %d, %d] of x %s" % (tuple(eps.shape), 2 * P * grid.T, C, grid.s, grid.s, tuple(x.shape)))
     if c.c_p and m_prev is None or c.c_n and noise is None:
         raise ValueError("c_p / c_n != 0 need m_prev / noise")
     f = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
-    eps, x, m_prev, noise = eps.detach().contiguous(), x.detach().contiguous(), f(m_prev if c.c_p else None), f(noise if c.c_n else None)
+    return eps.detach().contiguous(), x.detach().contiguous(), f(m_prev if c.c_p else None), f(noise if c.c_n else None)
+
+
+def sampler_step_windows_masked(eps, x, m_prev, noise, c, bl, grid, dtype=None, want_xin=False):
+    """sampler_step_windows for call i with the inpainting blend `bl` of call i + 1 applied to x_next -> (blended x_next, the unblended m,
+    xin of the blended state): bl a solver.Blend with canvas-shaped x0 / noise [P, C, Hc, Wc] and keep [P, 1, Hc, Wc] (1 = keep the
+    original). CUDA: one sta_sampler_step_windows_masked launch; CPU: step_windows_masked_reference."""
+    if not x.is_cuda:
+        return step_windows_masked_reference(eps, x, m_prev, noise, c, bl, grid, dtype, want_xin)
+    eps, x, m_prev, noise = _prep_step("sampler_step_windows_masked", eps, x, m_prev, noise, c, grid)
+    x0, keep, qn, _ = solver._prep_blend(x, bl)
+    P, C = x.shape[0], x.shape[1]
     x_next, m = torch.empty_like(x), torch.empty_like(x)
     xin = torch.empty_like(eps) if want_xin else None
-    ptr = lambda t: 0 if t is None else t.data_ptr()
-    lib.check(lib.load().sta_sampler_step_windows(eps.data_ptr(), x.data_ptr(), ptr(m_prev), ptr(noise), x_next.data_ptr(), m.data_ptr(),
-                                                  ptr(xin), P, C, grid.Hc, grid.Wc, *_grid_args(grid), c.scale, c.sigma_t, c.alpha_t, c.c_x,
-                                                  c.c_m, c.c_p, c.c_e, c.c_n, _DT[eps.dtype], _stream(x)), "sta_sampler_step_windows")
+    lib.check(lib.load().sta_sampler_step_windows_masked(eps.data_ptr(), x.data_ptr(), _ptr(m_prev), _ptr(noise), x0.data_ptr(), keep.data_ptr(),
+                                                         qn.data_ptr(), x_next.data_ptr(), m.data_ptr(), _ptr(xin), P, C, grid.Hc, grid.Wc,
+                                                         *_grid_args(grid), c.scale, c.sigma_t, c.alpha_t, c.c_x, c.c_m, c.c_p, c.c_e, c.c_n,
+                                                         bl.q_a, bl.q_b, _DT[eps.dtype], _stream(x)), "sta_sampler_step_windows_masked")
     return x_next, m, xin
+
+
+def window_blend(x, bl, grid, dtype=None, want_xin=False):
+    """The inpainting blend of the first call on a canvas state x [P, C, Hc, Wc] float32 -> (x', xin): xin (want_xin) the window input
+    pairs of x' in `dtype`, the UNet's 16-bit type. CUDA: one sta_window_blend launch (sta_latent_blend and sta_window_split in one);
+    CPU: window_blend_reference."""
+    if not x.is_cuda:
+        return window_blend_reference(x, bl, grid, dtype, want_xin)
+    if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
+        raise ValueError("window_blend: the state must be a float32 [P, C, %d, %d] canvas, got %s %s" % (grid.Hc, grid.Wc, x.dtype, tuple(x.shape)))
+    if dtype not in _DT:
+        raise TypeError("sta_window_blend writes 16-bit window inputs (dtype %s)" % dtype)
+    x0, keep, qn, _ = solver._prep_blend(x, bl)
+    x = x.detach().contiguous()
+    P, C = x.shape[0], x.shape[1]
+    out = torch.empty_like(x)
+    xin = torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=x.device) if want_xin else None
+    lib.check(lib.load().sta_window_blend(x.data_ptr(), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(), out.data_ptr(), _ptr(xin), P, C,
+                                          grid.Hc, grid.Wc, *_grid_args(grid), bl.q_a, bl.q_b, _DT[dtype], _stream(x)), "sta_window_blend")
+    return out, xin

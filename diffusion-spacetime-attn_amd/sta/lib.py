@@ -22,7 +22,8 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # shares its flags (-ffinite-math-only) and its pass through the hazard lint. sta_xattn_maps_bwd.hip (sta_xattn_token_maps_bwd) is the
 # backward of the token-map readout and is built with the cross-attention backward; sta_guide.hip (sta_latent_guide) is the latent update of
 # attention-guided sampling and is built with the sampler step, whose helpers it uses (no -ffinite-math-only there: it tests for Inf / NaN).
-# sta_window.hip (sta_window_split / sta_window_fuse / sta_sampler_step_windows: canvases sampled as overlapping windows) repeats the sampler
+# sta_window.hip (sta_window_split / sta_window_fuse / sta_sampler_step_windows and their inpainting forms sta_sampler_step_windows_masked /
+# sta_window_blend: canvases sampled as overlapping windows) repeats the sampler
 # step's arithmetic on overlap means and is built with it for the same reason: same helpers, and no fast-math flag (its mean is a
 # correctly rounded fp32 division).
 INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_window.hip": "sta_sampler.hip"}
@@ -45,7 +46,8 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 # (sta_sampler.hip: the window kernels index offset tables that arrive by value in the kernel arguments; a toolchain that copies the
 # tables to scratch to index them is refused)
 NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",),
-                    "sta_sampler.hip": ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel")}
+                    "sta_sampler.hip": ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel",
+                                        "sampler_step_windows_masked_kernel", "window_blend_kernel")}
 
 STA_BF16, STA_F16 = 0, 1
 STA_MX8_GEGLU, STA_MX8_MX_OUT = 1, 2
@@ -153,6 +155,8 @@ SYMBOLS = {
     "sta_window_split": (_i, [_vp, _vp, _l] + [_i] * 6 + [_vp, _vp] + [_i] * 3 + [_vp]),
     "sta_window_fuse": (_i, [_vp, _vp, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp]),
     "sta_sampler_step_windows": (_i, [_vp] * 7 + [_l] + [_i] * 5 + [_vp, _vp, _i] + [_f] * 8 + [_i, _vp]),
+    "sta_sampler_step_windows_masked": (_i, [_vp] * 10 + [_l] + [_i] * 5 + [_vp, _vp, _i] + [_f] * 10 + [_i, _vp]),
+    "sta_window_blend": (_i, [_vp] * 6 + [_l] + [_i] * 5 + [_vp, _vp, _i, _f, _f, _i, _vp]),
 }
 
 

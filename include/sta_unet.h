@@ -381,6 +381,16 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  * sta_sampler_step_windows: sta_sampler_step on the two overlap means of eps (fp32, NOT rounded to dtype), the same expressions in the
  *   same order; x, m_prev, noise, x_next, m: [P][C][Hc][Wc] fp32 (m_prev / noise may be NULL); xin: NULL, or [2 P T][C][s][s] dtype =
  *   the rounded x_next in both rows of every covering window, the next UNet call's input. With T = 1 bit-equal to sta_sampler_step.
+ *
+ * Inpainting and outpainting on a canvas: the blend of sta_sampler_step_masked / sta_latent_blend (one device definition, csrc/
+ * sta_blend_dev.h) with canvas-shaped constants: x0, qnoise / noise [P][C][Hc][Wc] fp32, keep [P][Hc][Wc] fp32 in [0, 1] (1 = keep the
+ * original), broadcast over the channels. All three are required (STA_E_ARG when NULL) and 16-byte aligned like every other tensor.
+ * sta_sampler_step_windows_masked: sta_sampler_step_windows for call i, then the blend OF CALL i + 1 (q_a, q_b, qnoise of that call) on
+ *   x_next: x_next = keep (q_a x0 + q_b qnoise) + (1 - keep) t, and where keep == 0 the unblended t bit for bit (= sta_sampler_step_windows).
+ *   m is the unblended data prediction. xin: NULL, or the rounded BLENDED x_next in both rows of every covering window. With T = 1
+ *   bit-equal to sta_sampler_step_masked. The last call of a trajectory takes sta_sampler_step_windows (no blend after the last step).
+ * sta_window_blend: the blend of the first call, x_out = keep (q_a x0 + q_b noise) + (1 - keep) x on [P][C][Hc][Wc] fp32, and xin (NULL =
+ *   not written) = the windows of the rounded result: sta_latent_blend and sta_window_split (rows = 1) in one launch.
  */
 #define STA_MAX_WINDOW_OFFSETS 16
 #define STA_SRC_F32 2
@@ -391,6 +401,12 @@ int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, i
 int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin, long P,
                              int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t,
                              float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream);
+int sta_sampler_step_windows_masked(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
+                                    const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc,
+                                    int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t, float alpha_t, float c_x,
+                                    float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream);
+int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
+                     int Wc, int ny, int nx, const int* oy, const int* ox, int s, float q_a, float q_b, int dtype, void* stream);
 
 /*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
