@@ -1,7 +1,7 @@
 // sta_guide.hip — the latent update of attention-guided sampling (gfx950). C-ABI in include/sta_unet.h (sta_latent_guide).
-// #included at the end of sta_sampler.hip (its V8T / F4 / load8 / store8, its flags: no -ffinite-math-only, a non-finite gradient must be
-// seen). Conventions of sta_sampler.hip / sta_inpaint.hip: a lane owns 8 consecutive elements of one image, 16-byte loads and stores, fp32
-// arithmetic, the mask [b][hw] read as 32 contiguous bytes at (8 col) % hw.
+// #included at the end of sta_sampler.hip (its flags: no -ffinite-math-only, a non-finite gradient must be seen); V8T / F4 / load8 /
+// store8 / store_pair are those of sta_step_dev.h. Conventions of sta_sampler.hip / sta_inpaint.hip: a lane owns 8 consecutive elements
+// of one image, 16-byte loads and stores, fp32 arithmetic, the mask [b][hw] read as 32 contiguous bytes at (8 col) % hw.
 //
 // The step needs the root mean square of an image's whole gradient before its first element can move. One launch, no atomics and no
 // hand-off between workgroups: an image is shared by `parts` workgroups, and EVERY one of them reduces the whole image's gradient itself,
@@ -9,6 +9,8 @@
 // rms_i without talking to each other; each then updates its own slice of the image. The gradient of one image is 4 n bytes (64 KB at
 // 512^2): the repeated reads and the second read of the slice are served by L2 / the Infinity Cache, HBM sees g once.
 // The result depends on nothing but the image's own inputs: bit-reproducible from launch to launch, images independent of each other.
+
+#include "sta_step_dev.h"
 
 namespace {
 
@@ -70,13 +72,7 @@ __global__ __launch_bounds__(256) void latent_guide_kernel(const T* __restrict__
       for (int k = 0; k < 8; ++k) xv[k] = xv[k] - s * d[k];
     }
     store8(x_out + 8 * (img * rowvec + v), xv);
-    if (xin) {
-      V8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (T)xv[k];
-      ((V8*)xin)[2 * img * rowvec + v] = o;
-      ((V8*)xin)[(2 * img + 1) * rowvec + v] = o;
-    }
+    if (xin) store_pair(xin, img, rowvec, v, xv);
   }
   if (stats && part == 0 && tid == 0) stats[img] = rms;
 }

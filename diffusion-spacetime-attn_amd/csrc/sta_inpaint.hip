@@ -10,38 +10,11 @@
 #include "sta_unet.h"
 #include "sta_internal.h"
 #include "sta_blend_dev.h"      // blend1: shared with the canvas kernels of sta_window.hip
+#include "sta_step_dev.h"       // V8T / F4 / load8 / store8 / StepCoef, the step per element: shared with sta_sampler.hip
 
 namespace {
 
-template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
-typedef float F4 __attribute__((ext_vector_type(4)));
-
-struct StepCoef {
-  float scale, sigma_t, alpha_t;
-  float c_x, c_m, c_p, c_e, c_n;
-};
-
-__device__ __forceinline__ void load8(const float* p, float* v) {
-  const F4 a = *(const F4*)p, b = *(const F4*)(p + 4);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    v[e] = a[e];
-    v[4 + e] = b[e];
-  }
-}
-
-__device__ __forceinline__ void store8(float* p, const float* v) {
-  F4 a, b;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    a[e] = v[e];
-    b[e] = v[4 + e];
-  }
-  *(F4*)p = a;
-  *(F4*)(p + 4) = b;
-}
-
-// sta_sampler_step's arithmetic for call i (same expressions, same order), then the blend of call i + 1 on x_next.
+// sta_sampler_step's step for call i (step1 of sta_step_dev.h), then the blend of call i + 1 on x_next.
 template <typename T>
 __global__ __launch_bounds__(256) void sampler_step_masked_kernel(const T* __restrict__ eps, const float* __restrict__ x,
                                                                   const float* __restrict__ m_prev, const float* __restrict__ noise,
@@ -53,8 +26,8 @@ __global__ __launch_bounds__(256) void sampler_step_masked_kernel(const T* __res
   const long stride = (long)gridDim.x * 256;
   for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
     const long img = v / rowvec, col = v - img * rowvec;
-    const V8 eu = ((const V8*)eps)[2 * img * rowvec + col];
-    const V8 ec = ((const V8*)eps)[(2 * img + 1) * rowvec + col];
+    const long iu = 2 * img * rowvec + col, ic = (2 * img + 1) * rowvec + col;      // rows 2 img, 2 img + 1 of eps and of xin
+    const V8 eu = ((const V8*)eps)[iu], ec = ((const V8*)eps)[ic];
     float xv[8], mp[8], nz[8], xn[8], mv[8], z0[8], kp[8], qn[8];
     load8(x + 8 * v, xv);
     if (m_prev) load8(m_prev + 8 * v, mp);
@@ -64,22 +37,15 @@ __global__ __launch_bounds__(256) void sampler_step_masked_kernel(const T* __res
     load8(keep + img * hw + (8 * col) % hw, kp);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const float u = (float)eu[k];
-      const float e = u + c.scale * ((float)ec[k] - u);
-      mv[k] = (xv[k] - c.sigma_t * e) / c.alpha_t;
-      float t = c.c_x * xv[k] + c.c_m * mv[k] + c.c_e * e;
-      if (m_prev) t += c.c_p * mp[k];
-      if (noise) t += c.c_n * nz[k];
+      const float t = step1((float)eu[k], (float)ec[k], xv[k], mp + k, nz + k, m_prev, noise, c, mv[k]);
       xn[k] = blend1(kp[k], z0[k], qn[k], t, q_a, q_b);
     }
     store8(x_next + 8 * v, xn);
     store8(m + 8 * v, mv);
-    if (xin) {
-      V8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (T)xn[k];
-      ((V8*)xin)[2 * img * rowvec + col] = o;
-      ((V8*)xin)[(2 * img + 1) * rowvec + col] = o;
+    if (xin) {      // not store_pair: it would form the row indices of the eps loads again (profiles/step_one_definition.md)
+      const V8 o = round8<T>(xn);
+      ((V8*)xin)[iu] = o;
+      ((V8*)xin)[ic] = o;
     }
   }
 }
@@ -102,15 +68,7 @@ __global__ __launch_bounds__(256) void sampler_step_masked_bwd_kernel(const floa
     load8(keep + img * hw + (8 * col) % hw, kp);
     V8 gu, gc;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float g = (1.0f - kp[k]) * gn[k];
-      const float Gm = (g_m ? gm[k] : 0.f) + c.c_m * g;
-      gx[k] = c.c_x * g + Gm * inv_a;
-      const float ge = c.c_e * g - c.sigma_t * inv_a * Gm;
-      gu[k] = (T)((1.0f - c.scale) * ge);
-      gc[k] = (T)(c.scale * ge);
-      gp[k] = c.c_p * g;
-    }
+    for (int k = 0; k < 8; ++k) step1_bwd<T>((1.0f - kp[k]) * gn[k], gm, g_m, inv_a, c, k, gx, gu, gc, gp);
     store8(g_x + 8 * v, gx);
     ((V8*)g_eps)[2 * img * rowvec + col] = gu;
     ((V8*)g_eps)[(2 * img + 1) * rowvec + col] = gc;
@@ -135,13 +93,7 @@ __global__ __launch_bounds__(256) void latent_blend_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < 8; ++k) xo[k] = blend1(kp[k], z0[k], qn[k], xv[k], q_a, q_b);
     store8(x_out + 8 * v, xo);
-    if (xin) {
-      V8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (T)xo[k];
-      ((V8*)xin)[2 * img * rowvec + col] = o;
-      ((V8*)xin)[(2 * img + 1) * rowvec + col] = o;
-    }
+    if (xin) store_pair(xin, img, rowvec, col, xo);
   }
 }
 
@@ -207,13 +159,9 @@ int sta_sampler_step_masked(const void* eps, const float* x, const float* m_prev
                             float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype,
                             void* stream) {
   g_sta_err[0] = 0;
-  if (!eps || !x || !x_next || !m) return sta_fail(STA_E_ARG, "null pointer");
-  if (!x0 || !keep || !qnoise) return sta_fail(STA_E_ARG, "sampler_step_masked: x0, keep and qnoise are required (null pointer)");
-  if (check_sizes("sampler_step_masked", b, n, hw)) return STA_E_ARG;
-  if (!sta_aligned16(eps) || !sta_aligned16(x) || !sta_aligned16(m_prev) || !sta_aligned16(noise) || !sta_aligned16(x0) || !sta_aligned16(keep) ||
-      !sta_aligned16(qnoise) || !sta_aligned16(x_next) || !sta_aligned16(m) || !sta_aligned16(xin))
-    return sta_fail(STA_E_ARG, "sampler_step_masked: every tensor must be 16-byte aligned");
-  if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_masked: alpha_t == 0");
+  if (const int rc = sta_step_args_ok("sampler_step_masked", eps, x, m_prev, noise, x_next, m, xin, true, x0, keep, qnoise, alpha_t,
+                                      [&] { return check_sizes("sampler_step_masked", b, n, hw); }))
+    return rc;
   const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
   const long rowvec = n / 8, nvec = b * rowvec;
   return sta_by_dtype(dtype, [&](auto tag) {
@@ -227,12 +175,9 @@ int sta_sampler_step_masked_bwd(const float* g_xn, const float* g_m, const float
                                 long n, long hw, float scale, float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e,
                                 int dtype, void* stream) {
   g_sta_err[0] = 0;
-  if (!g_xn || !g_x || !g_eps) return sta_fail(STA_E_ARG, "null pointer");
-  if (!keep) return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: keep is required (null pointer)");
-  if (check_sizes("sampler_step_masked_bwd", b, n, hw)) return STA_E_ARG;
-  if (!sta_aligned16(g_xn) || !sta_aligned16(g_m) || !sta_aligned16(keep) || !sta_aligned16(g_x) || !sta_aligned16(g_eps) || !sta_aligned16(g_mprev))
-    return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: every tensor must be 16-byte aligned");
-  if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_masked_bwd: alpha_t == 0");
+  if (const int rc = sta_step_bwd_args_ok("sampler_step_masked_bwd", g_xn, g_m, g_x, g_eps, g_mprev, true, keep, alpha_t,
+                                          [&] { return check_sizes("sampler_step_masked_bwd", b, n, hw); }))
+    return rc;
   const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, 0.f};
   const long rowvec = n / 8, nvec = b * rowvec;
   return sta_by_dtype(dtype, [&](auto tag) {

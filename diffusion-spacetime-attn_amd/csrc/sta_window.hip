@@ -1,6 +1,7 @@
 // sta_window.hip — wide canvases sampled as overlapping square windows (gfx950). C-ABI in include/sta_unet.h (sta_window_split /
-// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend). #included at the end of sta_sampler.hip (its V8T / F4 / load8 / store8 / StepCoef, its
-// flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division).
+// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend). #included at the end of sta_sampler.hip (its
+// flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division). The step on the overlap means
+// is step1 of sta_step_dev.h, the definition the square kernels use, with that header's V8T / F4 / load8 / store8 / round8 / StepCoef.
 // Conventions of sta_sampler.hip: 256-lane groups, grid-stride, a lane owns 8 consecutive elements of one CANVAS row, 16-byte loads and
 // stores, fp32 arithmetic. Window sides, offsets and canvas sides are multiples of 8, so a lane's vector lies inside or outside a window
 // as a whole. The offset tables travel by value in the kernel arguments: nothing device-side to fill, the launches are capturable.
@@ -10,6 +11,7 @@
 // sta_inpaint.hip uses for square images.
 
 #include "sta_blend_dev.h"
+#include "sta_step_dev.h"
 
 namespace {
 
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void window_fuse_kernel(const T* __restrict__ 
   }
 }
 
-// sampler_step_kernel on the overlap means of the windows' UNet output (fp32, not rounded): the same expressions in the same order;
+// sampler_step_kernel on the overlap means of the windows' UNet output (fp32, not rounded): the same step1;
 // xin (null = not written): the rounded x_next to both rows of every covering window, the next call's input
 template <typename T>
 __global__ __launch_bounds__(256) void sampler_step_windows_kernel(const T* __restrict__ eps, const float* __restrict__ x,
@@ -136,30 +138,17 @@ __global__ __launch_bounds__(256) void sampler_step_windows_kernel(const T* __re
     if (m_prev) load8(m_prev + 8 * v, mp);
     if (noise) load8(noise + 8 * v, nz);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float u = eu[k] / cnt;
-      const float e = u + c.scale * (ec[k] / cnt - u);
-      mv[k] = (xv[k] - c.sigma_t * e) / c.alpha_t;
-      float t = c.c_x * xv[k] + c.c_m * mv[k] + c.c_e * e;
-      if (m_prev) t += c.c_p * mp[k];
-      if (noise) t += c.c_n * nz[k];
-      xn[k] = t;
-    }
+    for (int k = 0; k < 8; ++k) xn[k] = step1(eu[k] / cnt, ec[k] / cnt, xv[k], mp + k, nz + k, m_prev, noise, c, mv[k]);
     store8(x_next + 8 * v, xn);
     store8(m + 8 * v, mv);
-    if (xin) {
-      V8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (T)xn[k];
-      scatter<T>(xin, g, q.row, 0, 1, C, q, o);
-    }
+    if (xin) scatter<T>(xin, g, q.row, 0, 1, C, q, round8<T>(xn));
   }
 }
 
 // first element of the lane's vector in a [P][Hc][Wc] mask, broadcast over the channels
 __device__ __forceinline__ long mask_at(const CanvasPos& q, int Hc, int Wc) { return (q.row * Hc + q.y) * (long)Wc + q.x; }
 
-// sampler_step_windows_kernel for call i (the same expressions in the same order), then the inpainting blend of call i + 1 on x_next
+// sampler_step_windows_kernel for call i (the same step1), then the inpainting blend of call i + 1 on x_next
 // (blend1 of sta_blend_dev.h, as sampler_step_masked_kernel): x0 / qnoise canvas-shaped, keep [P][Hc][Wc]; m is the unblended data
 // prediction; xin (null = not written): the rounded BLENDED x_next to both rows of every covering window. MP / NZ: m_prev / noise are
 // given — compile-time here, since the three extra streams leave no scalar registers for the run-time tests' masks
@@ -186,22 +175,12 @@ __global__ __launch_bounds__(256) void sampler_step_windows_masked_kernel(const 
     load8(keep + mask_at(q, Hc, Wc), kp);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const float u = eu[k] / cnt;
-      const float e = u + c.scale * (ec[k] / cnt - u);
-      mv[k] = (xv[k] - c.sigma_t * e) / c.alpha_t;
-      float t = c.c_x * xv[k] + c.c_m * mv[k] + c.c_e * e;
-      if constexpr (MP) t += c.c_p * mp[k];
-      if constexpr (NZ) t += c.c_n * nz[k];
+      const float t = step1(eu[k] / cnt, ec[k] / cnt, xv[k], mp + k, nz + k, MP, NZ, c, mv[k]);
       xn[k] = blend1(kp[k], z0[k], qn[k], t, q_a, q_b);
     }
     store8(x_next + 8 * v, xn);
     store8(m + 8 * v, mv);
-    if (xin) {
-      V8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (T)xn[k];
-      scatter<T>(xin, g, q.row, 0, 1, C, q, o);
-    }
+    if (xin) scatter<T>(xin, g, q.row, 0, 1, C, q, round8<T>(xn));
   }
 }
 
@@ -223,12 +202,7 @@ __global__ __launch_bounds__(256) void window_blend_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < 8; ++k) xo[k] = blend1(kp[k], z0[k], qn[k], xv[k], q_a, q_b);
     store8(x_out + 8 * v, xo);
-    if (xin) {
-      V8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (T)xo[k];
-      scatter<T>(xin, g, q.row, 0, 1, C, q, o);
-    }
+    if (xin) scatter<T>(xin, g, q.row, 0, 1, C, q, round8<T>(xo));
   }
 }
 
@@ -304,12 +278,10 @@ int sta_sampler_step_windows(const void* eps, const float* x, const float* m_pre
                              int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t,
                              float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream) {
   g_sta_err[0] = 0;
-  if (!eps || !x || !x_next || !m) return sta_fail(STA_E_ARG, "null pointer");
   WinGrid g;
-  if (const int rc = window_grid_ok("sampler_step_windows", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
-  if (!sta_aligned16(eps) || !sta_aligned16(x) || !sta_aligned16(m_prev) || !sta_aligned16(noise) || !sta_aligned16(x_next) || !sta_aligned16(m) || !sta_aligned16(xin))
-    return sta_fail(STA_E_ARG, "sampler_step_windows: every tensor must be 16-byte aligned");
-  if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_windows: alpha_t == 0");
+  if (const int rc = sta_step_args_ok("sampler_step_windows", eps, x, m_prev, noise, x_next, m, xin, false, nullptr, nullptr, nullptr, alpha_t,
+                                      [&] { return window_grid_ok("sampler_step_windows", P, C, Hc, Wc, ny, nx, oy, ox, s, &g); }))
+    return rc;
   const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
   const long nvec = P * C * Hc * (Wc / 8);
   return sta_by_dtype(dtype, [&](auto tag) {
@@ -324,14 +296,10 @@ int sta_sampler_step_windows_masked(const void* eps, const float* x, const float
                                     int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t, float alpha_t, float c_x,
                                     float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream) {
   g_sta_err[0] = 0;
-  if (!eps || !x || !x_next || !m) return sta_fail(STA_E_ARG, "null pointer");
-  if (!x0 || !keep || !qnoise) return sta_fail(STA_E_ARG, "sampler_step_windows_masked: x0, keep and qnoise are required (null pointer)");
   WinGrid g;
-  if (const int rc = window_grid_ok("sampler_step_windows_masked", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
-  if (!sta_aligned16(eps) || !sta_aligned16(x) || !sta_aligned16(m_prev) || !sta_aligned16(noise) || !sta_aligned16(x0) || !sta_aligned16(keep) ||
-      !sta_aligned16(qnoise) || !sta_aligned16(x_next) || !sta_aligned16(m) || !sta_aligned16(xin))
-    return sta_fail(STA_E_ARG, "sampler_step_windows_masked: every tensor must be 16-byte aligned");
-  if (alpha_t == 0.f) return sta_fail(STA_E_ARG, "sampler_step_windows_masked: alpha_t == 0");
+  if (const int rc = sta_step_args_ok("sampler_step_windows_masked", eps, x, m_prev, noise, x_next, m, xin, true, x0, keep, qnoise, alpha_t,
+                                      [&] { return window_grid_ok("sampler_step_windows_masked", P, C, Hc, Wc, ny, nx, oy, ox, s, &g); }))
+    return rc;
   const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
   const long nvec = P * C * Hc * (Wc / 8);
   return sta_by_dtype(dtype, [&](auto tag) {

@@ -202,14 +202,7 @@ def sampler_step_windows(eps, x, m_prev, noise, c, grid, dtype=None, want_xin=Fa
     CUDA: one sta_sampler_step_windows launch (no autograd: canvases are sampled with fixed weights); CPU: step_windows_reference."""
     if not x.is_cuda:
         return step_windows_reference(eps, x, m_prev, noise, c, grid, dtype, want_xin)
-    eps, x, m_prev, noise = _prep_step("sampler_step_windows", eps, x, m_prev, noise, c, grid)
-    P, C = x.shape[0], x.shape[1]
-    x_next, m = torch.empty_like(x), torch.empty_like(x)
-    xin = torch.empty_like(eps) if want_xin else None
-    lib.check(lib.load().sta_sampler_step_windows(eps.data_ptr(), x.data_ptr(), _ptr(m_prev), _ptr(noise), x_next.data_ptr(), m.data_ptr(),
-                                                  _ptr(xin), P, C, grid.Hc, grid.Wc, *_grid_args(grid), c.scale, c.sigma_t, c.alpha_t, c.c_x,
-                                                  c.c_m, c.c_p, c.c_e, c.c_n, _DT[eps.dtype], _stream(x)), "sta_sampler_step_windows")
-    return x_next, m, xin
+    return _step_windows(eps, x, m_prev, noise, c, None, grid, want_xin)
 
 
 def _ptr(t):
@@ -232,22 +225,31 @@ def _prep_step(what, eps, x, m_prev, noise, c, grid):
     return eps.detach().contiguous(), x.detach().contiguous(), f(m_prev if c.c_p else None), f(noise if c.c_n else None)
 
 
+def _step_windows(eps, x, m_prev, noise, c, bl, grid, want_xin):
+    """The CUDA side of sampler_step_windows (bl None) and sampler_step_windows_masked (bl a solver.Blend): one launch."""
+    what = "sampler_step_windows" if bl is None else "sampler_step_windows_masked"
+    eps, x, m_prev, noise = _prep_step(what, eps, x, m_prev, noise, c, grid)
+    x_next, m = torch.empty_like(x), torch.empty_like(x)
+    xin = torch.empty_like(eps) if want_xin else None
+    blend, q = (), ()
+    if bl is not None:
+        x0, keep, qn, _ = solver._prep_blend(x, bl)
+        blend, q = (x0.data_ptr(), keep.data_ptr(), qn.data_ptr()), (bl.q_a, bl.q_b)
+    args = (eps.data_ptr(), x.data_ptr(), _ptr(m_prev), _ptr(noise)) + blend + (x_next.data_ptr(), m.data_ptr(), _ptr(xin))
+    args += (x.shape[0], x.shape[1], grid.Hc, grid.Wc) + _grid_args(grid) + tuple(c) + q + (_DT[eps.dtype], _stream(x))
+    lib.check(getattr(lib.load(), "sta_" + what)(*args), "sta_" + what)
+    return x_next, m, xin
+
+
 def sampler_step_windows_masked(eps, x, m_prev, noise, c, bl, grid, dtype=None, want_xin=False):
     """sampler_step_windows for call i with the inpainting blend `bl` of call i + 1 applied to x_next -> (blended x_next, the unblended m,
     xin of the blended state): bl a solver.Blend with canvas-shaped x0 / noise [P, C, Hc, Wc] and keep [P, 1, Hc, Wc] (1 = keep the
     original). CUDA: one sta_sampler_step_windows_masked launch; CPU: step_windows_masked_reference."""
+    if bl is None:
+        raise ValueError("sampler_step_windows_masked needs a Blend")
     if not x.is_cuda:
         return step_windows_masked_reference(eps, x, m_prev, noise, c, bl, grid, dtype, want_xin)
-    eps, x, m_prev, noise = _prep_step("sampler_step_windows_masked", eps, x, m_prev, noise, c, grid)
-    x0, keep, qn, _ = solver._prep_blend(x, bl)
-    P, C = x.shape[0], x.shape[1]
-    x_next, m = torch.empty_like(x), torch.empty_like(x)
-    xin = torch.empty_like(eps) if want_xin else None
-    lib.check(lib.load().sta_sampler_step_windows_masked(eps.data_ptr(), x.data_ptr(), _ptr(m_prev), _ptr(noise), x0.data_ptr(), keep.data_ptr(),
-                                                         qn.data_ptr(), x_next.data_ptr(), m.data_ptr(), _ptr(xin), P, C, grid.Hc, grid.Wc,
-                                                         *_grid_args(grid), c.scale, c.sigma_t, c.alpha_t, c.c_x, c.c_m, c.c_p, c.c_e, c.c_n,
-                                                         bl.q_a, bl.q_b, _DT[eps.dtype], _stream(x)), "sta_sampler_step_windows_masked")
-    return x_next, m, xin
+    return _step_windows(eps, x, m_prev, noise, c, bl, grid, want_xin)
 
 
 def window_blend(x, bl, grid, dtype=None, want_xin=False):

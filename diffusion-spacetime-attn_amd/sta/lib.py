@@ -21,11 +21,11 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # csrc/*.hip files that are not translation units of their own: each is #included at the end of the source named here and so
 # shares its flags (-ffinite-math-only) and its pass through the hazard lint. sta_xattn_maps_bwd.hip (sta_xattn_token_maps_bwd) is the
 # backward of the token-map readout and is built with the cross-attention backward; sta_guide.hip (sta_latent_guide) is the latent update of
-# attention-guided sampling and is built with the sampler step, whose helpers it uses (no -ffinite-math-only there: it tests for Inf / NaN).
+# attention-guided sampling and is built with the sampler step (no -ffinite-math-only there: it tests for Inf / NaN).
 # sta_window.hip (sta_window_split / sta_window_fuse / sta_sampler_step_windows and their inpainting forms sta_sampler_step_windows_masked /
-# sta_window_blend: canvases sampled as overlapping windows) repeats the sampler
-# step's arithmetic on overlap means and is built with it for the same reason: same helpers, and no fast-math flag (its mean is a
-# correctly rounded fp32 division).
+# sta_window_blend: canvases sampled as overlapping windows) runs the sampler step on overlap means and is built with it for the same
+# reason: no fast-math flag (its mean is a correctly rounded fp32 division). The step itself and the helpers of all three are defined
+# once, in csrc/sta_step_dev.h, which sta_inpaint.hip includes as well.
 INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_window.hip": "sta_sampler.hip"}
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the

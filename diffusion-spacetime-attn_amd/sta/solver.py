@@ -20,7 +20,7 @@ Inpainting (csrc/sta_inpaint.hip): before UNet call i at integer timestep t_i th
     x <- keep (q_a x0 + q_b n_i) + (1 - keep) x,   q_a = sqrt(acp[t_i]), q_b = sqrt(1 - acp[t_i])   (reference ddim.py:144-147),
 with keep [b, 1, h, w] in [0, 1] (1 = keep the original), x0 and n_i constants of the graph. A `Blend` carries one call's
 (x0, keep, noise, q_a, q_b). `latent_blend` is the blend alone (first call); `solver_step_masked` is the step of call i followed by the
-blend of call i + 1 in the same launch (sta_sampler_step_masked; `SolverStepMaskedFn` under autograd, backward =
+blend of call i + 1 in the same launch (sta_sampler_step_masked; under autograd `SolverStepFn` with the blend, backward =
 sta_sampler_step_masked_bwd). `image_composite` pastes the original image over the decoded one in pixel space (sta_image_composite).
 """
 from collections import namedtuple
@@ -152,15 +152,22 @@ def step_reference(eps, x, m_prev, noise, c):
     return x_next, m
 
 
-def _launch_fwd(eps16, x, m_prev, noise, c, want_xin):
+def _launch_fwd(eps16, x, m_prev, noise, c, want_xin, blend=None):
+    """One forward launch: sta_sampler_step, or sta_sampler_step_masked with blend = (x0, keep, qn, hw, q_a, q_b) as _blend_args
+    prepares it."""
     b, n = x.shape[0], x[0].numel()
     x_next, m = torch.empty_like(x), torch.empty_like(x)
     xin = torch.empty((2 * b, *x.shape[1:]), dtype=eps16.dtype, device=x.device) if want_xin else None
     ptr = lambda t: 0 if t is None else t.data_ptr()
-    lib.check(lib.load().sta_sampler_step(eps16.data_ptr(), x.data_ptr(), ptr(m_prev if c.c_p else None), ptr(noise if c.c_n else None),
-                                          x_next.data_ptr(), m.data_ptr(), ptr(xin), b, n, c.scale, c.sigma_t, c.alpha_t, c.c_x, c.c_m,
-                                          c.c_p, c.c_e, c.c_n, _DT[eps16.dtype], torch.cuda.current_stream(x.device).cuda_stream),
-              "sta_sampler_step")
+    ins = (eps16.data_ptr(), x.data_ptr(), ptr(m_prev if c.c_p else None), ptr(noise if c.c_n else None))
+    outs = (x_next.data_ptr(), m.data_ptr(), ptr(xin), b, n)
+    tail = (_DT[eps16.dtype], torch.cuda.current_stream(x.device).cuda_stream)
+    if blend is None:
+        name, args = "sta_sampler_step", ins + outs + tuple(c) + tail
+    else:
+        x0, keep, qn, hw, q_a, q_b = blend
+        name, args = "sta_sampler_step_masked", ins + (x0.data_ptr(), keep.data_ptr(), qn.data_ptr()) + outs + (hw,) + tuple(c) + (q_a, q_b) + tail
+    lib.check(getattr(lib.load(), name)(*args), name)
     return x_next, m, xin
 
 
@@ -179,13 +186,19 @@ def _prep(eps, x, m_prev, noise, c, dtype):
 
 
 class SolverStepFn(torch.autograd.Function):
-    """(x_next, m) = step(eps, x, m_prev) on the HIP kernels; backward = sta_sampler_step_bwd (no gradient for the noise)."""
+    """(x_next, m) = step(eps, x, m_prev) on the HIP kernels; backward = sta_sampler_step_bwd (no gradient for the noise).
+    With a blend `bl`: (blended x_next, m) of the masked step; backward = sta_sampler_step_masked_bwd: (1 - keep) of the gradient of the
+    blended state flows on, x0 / keep / the noises get none."""
 
     @staticmethod
-    def forward(ctx, eps, x, m_prev, noise, c, dtype):
+    def forward(ctx, eps, x, m_prev, noise, c, dtype, bl=None):
         e16, xc, mp, nz = _prep(eps, x, m_prev, noise, c, dtype)
-        x_next, m, _ = _launch_fwd(e16, xc, mp, nz, c, False)
+        blend = _blend_args(xc, bl)
+        x_next, m, _ = _launch_fwd(e16, xc, mp, nz, c, False, blend)
         ctx.c, ctx.dt, ctx.eps_dtype, ctx.has_mprev = c, e16.dtype, eps.dtype, m_prev is not None
+        ctx.hw = None if blend is None else blend[3]
+        if blend is not None:
+            ctx.save_for_backward(blend[1])      # keep
         return x_next, m
 
     @staticmethod
@@ -197,11 +210,32 @@ class SolverStepFn(torch.autograd.Function):
         g_x = torch.empty_like(g_xn)
         g_eps = torch.empty((2 * b, *g_xn.shape[1:]), dtype=ctx.dt, device=g_xn.device)
         g_mp = torch.empty_like(g_xn) if ctx.has_mprev and ctx.needs_input_grad[2] else None
-        lib.check(lib.load().sta_sampler_step_bwd(g_xn.data_ptr(), 0 if g_m is None else g_m.data_ptr(), g_x.data_ptr(), g_eps.data_ptr(),
-                                                  0 if g_mp is None else g_mp.data_ptr(), b, n, c.scale, c.sigma_t, c.alpha_t, c.c_x,
-                                                  c.c_m, c.c_p, c.c_e, _DT[ctx.dt], torch.cuda.current_stream(g_xn.device).cuda_stream),
-                  "sta_sampler_step_bwd")
-        return g_eps.to(ctx.eps_dtype), g_x, g_mp, None, None, None
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        outs = (g_x.data_ptr(), g_eps.data_ptr(), ptr(g_mp), b, n)
+        tail = tuple(c[:7]) + (_DT[ctx.dt], torch.cuda.current_stream(g_xn.device).cuda_stream)      # scale .. c_e: no c_n
+        if ctx.hw is None:
+            name, args = "sta_sampler_step_bwd", (g_xn.data_ptr(), ptr(g_m)) + outs + tail
+        else:
+            keep, = ctx.saved_tensors
+            name, args = "sta_sampler_step_masked_bwd", (g_xn.data_ptr(), ptr(g_m), keep.data_ptr()) + outs + (ctx.hw,) + tail
+        lib.check(getattr(lib.load(), name)(*args), name)
+        return g_eps.to(ctx.eps_dtype), g_x, g_mp, None, None, None, None
+
+
+SolverStepMaskedFn = SolverStepFn      # the masked step is the same Function with a blend
+
+
+def _step(eps, x, m_prev, noise, c, bl, dtype, want_xin):
+    """solver_step (bl None) and solver_step_masked (bl a Blend): one dispatch."""
+    if not x.is_cuda:
+        x_next, m = step_reference(eps, x, m_prev, noise, c) if bl is None else step_reference_masked(eps, x, m_prev, noise, c, bl)
+        xin = _pair(x_next).to(dtype or eps.dtype) if want_xin else None
+        return x_next, m, xin
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (eps, x, m_prev)):
+        x_next, m = SolverStepFn.apply(eps, x, m_prev, noise, c, dtype, bl)
+        return x_next, m, (_pair(x_next.detach()).to(dtype or eps.dtype) if want_xin else None)
+    e16, xc, mp, nz = _prep(eps, x, m_prev, noise, c, dtype)
+    return _launch_fwd(e16, xc, mp, nz, c, want_xin, _blend_args(xc, bl))
 
 
 def solver_step(eps, x, m_prev, noise, c, dtype=None, want_xin=False):
@@ -209,15 +243,7 @@ def solver_step(eps, x, m_prev, noise, c, dtype=None, want_xin=False):
     eps [2b, ...] (16-bit, or float32 holding 16-bit values with `dtype` the UNet's 16-bit type), x [b, ...] float32, m_prev /
     noise [b, ...] or None, c a StepCoef. xin (want_xin): (x_next, x_next) per image in the UNet's dtype, the next call's input.
     CUDA: the HIP kernel (SolverStepFn under autograd); CPU: step_reference."""
-    if not x.is_cuda:
-        x_next, m = step_reference(eps, x, m_prev, noise, c)
-        xin = _pair(x_next).to(dtype or eps.dtype) if want_xin else None
-        return x_next, m, xin
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (eps, x, m_prev)):
-        x_next, m = SolverStepFn.apply(eps, x, m_prev, noise, c, dtype)
-        return x_next, m, (_pair(x_next.detach()).to(dtype or eps.dtype) if want_xin else None)
-    e16, xc, mp, nz = _prep(eps, x, m_prev, noise, c, dtype)
-    return _launch_fwd(e16, xc, mp, nz, c, want_xin)
+    return _step(eps, x, m_prev, noise, c, None, dtype, want_xin)
 
 
 # ---------------------------------------------------------------------------------------------------- inpainting
@@ -253,6 +279,11 @@ def _prep_blend(x, bl):
     return f(bl.x0), f(bl.keep), f(bl.noise), hw
 
 
+def _blend_args(x, bl):
+    """(x0, keep, noise, hw, q_a, q_b) as the masked kernels take them, None for no blend."""
+    return None if bl is None else _prep_blend(x, bl) + (bl.q_a, bl.q_b)
+
+
 def latent_blend(x, bl, dtype=None, want_xin=False):
     """The blend of the first call -> (x', xin). CUDA: sta_latent_blend (dtype: the UNet's 16-bit type of xin); CPU: blend_reference.
     No backward: the start latent is a constant."""
@@ -274,64 +305,12 @@ def latent_blend(x, bl, dtype=None, want_xin=False):
     return out, xin
 
 
-def _launch_fwd_masked(eps16, x, m_prev, noise, c, blend, want_xin):
-    x0, keep, qn, hw, q_a, q_b = blend
-    b, n = x.shape[0], x[0].numel()
-    x_next, m = torch.empty_like(x), torch.empty_like(x)
-    xin = torch.empty((2 * b, *x.shape[1:]), dtype=eps16.dtype, device=x.device) if want_xin else None
-    ptr = lambda t: 0 if t is None else t.data_ptr()
-    lib.check(lib.load().sta_sampler_step_masked(eps16.data_ptr(), x.data_ptr(), ptr(m_prev if c.c_p else None),
-                                                 ptr(noise if c.c_n else None), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(),
-                                                 x_next.data_ptr(), m.data_ptr(), ptr(xin), b, n, hw, c.scale, c.sigma_t, c.alpha_t, c.c_x,
-                                                 c.c_m, c.c_p, c.c_e, c.c_n, q_a, q_b, _DT[eps16.dtype],
-                                                 torch.cuda.current_stream(x.device).cuda_stream), "sta_sampler_step_masked")
-    return x_next, m, xin
-
-
-class SolverStepMaskedFn(torch.autograd.Function):
-    """(blended x_next, m) = masked step(eps, x, m_prev) on the HIP kernels; backward = sta_sampler_step_masked_bwd: (1 - keep) of the
-    gradient of the blended state flows on, x0 / keep / the noises get none."""
-
-    @staticmethod
-    def forward(ctx, eps, x, m_prev, noise, c, bl, dtype):
-        e16, xc, mp, nz = _prep(eps, x, m_prev, noise, c, dtype)
-        x0, keep, qn, hw = _prep_blend(xc, bl)
-        x_next, m, _ = _launch_fwd_masked(e16, xc, mp, nz, c, (x0, keep, qn, hw, bl.q_a, bl.q_b), False)
-        ctx.c, ctx.dt, ctx.eps_dtype, ctx.has_mprev, ctx.hw = c, e16.dtype, eps.dtype, m_prev is not None, hw
-        ctx.save_for_backward(keep)
-        return x_next, m
-
-    @staticmethod
-    def backward(ctx, g_xn, g_m):
-        c = ctx.c
-        keep, = ctx.saved_tensors
-        g_xn = g_xn.to(torch.float32).contiguous()
-        g_m = None if g_m is None else g_m.to(torch.float32).contiguous()
-        b, n = g_xn.shape[0], g_xn[0].numel()
-        g_x = torch.empty_like(g_xn)
-        g_eps = torch.empty((2 * b, *g_xn.shape[1:]), dtype=ctx.dt, device=g_xn.device)
-        g_mp = torch.empty_like(g_xn) if ctx.has_mprev and ctx.needs_input_grad[2] else None
-        lib.check(lib.load().sta_sampler_step_masked_bwd(g_xn.data_ptr(), 0 if g_m is None else g_m.data_ptr(), keep.data_ptr(),
-                                                         g_x.data_ptr(), g_eps.data_ptr(), 0 if g_mp is None else g_mp.data_ptr(), b, n,
-                                                         ctx.hw, c.scale, c.sigma_t, c.alpha_t, c.c_x, c.c_m, c.c_p, c.c_e, _DT[ctx.dt],
-                                                         torch.cuda.current_stream(g_xn.device).cuda_stream),
-                  "sta_sampler_step_masked_bwd")
-        return g_eps.to(ctx.eps_dtype), g_x, g_mp, None, None, None, None
-
-
 def solver_step_masked(eps, x, m_prev, noise, c, bl, dtype=None, want_xin=False):
     """solver_step for call i with the blend `bl` of call i + 1 applied to x_next -> (blended x_next, m, xin of the blended state).
-    Same dispatch as solver_step: CPU: step_reference_masked; CUDA under autograd: SolverStepMaskedFn; otherwise the raw launch."""
-    if not x.is_cuda:
-        x_next, m = step_reference_masked(eps, x, m_prev, noise, c, bl)
-        xin = _pair(x_next).to(dtype or eps.dtype) if want_xin else None
-        return x_next, m, xin
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (eps, x, m_prev)):
-        x_next, m = SolverStepMaskedFn.apply(eps, x, m_prev, noise, c, bl, dtype)
-        return x_next, m, (_pair(x_next.detach()).to(dtype or eps.dtype) if want_xin else None)
-    e16, xc, mp, nz = _prep(eps, x, m_prev, noise, c, dtype)
-    x0, keep, qn, hw = _prep_blend(xc, bl)
-    return _launch_fwd_masked(e16, xc, mp, nz, c, (x0, keep, qn, hw, bl.q_a, bl.q_b), want_xin)
+    Same dispatch as solver_step: CPU: step_reference_masked; CUDA under autograd: SolverStepFn with the blend; otherwise the raw launch."""
+    if bl is None:
+        raise ValueError("solver_step_masked needs a Blend")
+    return _step(eps, x, m_prev, noise, c, bl, dtype, want_xin)
 
 
 def image_composite_reference(dec, orig, keep_px):

@@ -182,6 +182,31 @@ def test_abi_symbols_and_refusals_reach_no_launch():
     assert _call(L, "sta_sampler_step_windows_masked", dtype=7, noise=0)[1] == "dtype 7"
 
 
+def test_the_sampler_step_is_defined_once():
+    """The element step, forward and backward, and the helpers of the elementwise kernels have one definition, csrc/sta_step_dev.h; the
+    square, masked and canvas kernels use it and define none of it themselves (sta_guide.hip has no step: it uses the helpers)."""
+    from sta import lib
+    csrc = lambda n: open(os.path.join(lib.CSRC, n)).read()
+    header = csrc("sta_step_dev.h")
+    step_defs = ("float step1(", "void step1_bwd(")
+    helper_defs = ("struct V8T", "typedef float F4", "struct StepCoef", "void load8(", "void store8(", " round8(const float", "void store_pair(")
+    for d in step_defs + helper_defs:
+        assert header.count(d) == 1, d
+    for n in ("sta_sampler.hip", "sta_inpaint.hip", "sta_window.hip", "sta_guide.hip"):
+        text = csrc(n)
+        assert '#include "sta_step_dev.h"' in text, n
+        for d in step_defs + helper_defs:
+            assert d not in text, (n, d)
+        assert "load8(" in text and "store8(" in text and "V8T<T>" in text, n
+    assert all("step1(" in csrc(n) for n in ("sta_sampler.hip", "sta_inpaint.hip", "sta_window.hip"))
+    assert all("step1_bwd<T>(" in csrc(n) for n in ("sta_sampler.hip", "sta_inpaint.hip"))
+    assert "step1" not in csrc("sta_guide.hip")
+    # no kernel restates the step's arithmetic: sigma_t and the c_* coefficients are read in the header alone
+    for n in ("sta_sampler.hip", "sta_inpaint.hip", "sta_window.hip"):
+        for field in ("c.sigma_t", "c.c_x", "c.c_m", "c.c_p", "c.c_e", "c.c_n", "c.scale"):
+            assert field not in csrc(n), (n, field)
+
+
 # ---------------------------------------------------------------------------------------------------
 # inpaint_canvas on the host miniature
 # ---------------------------------------------------------------------------------------------------

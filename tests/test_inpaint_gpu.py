@@ -148,6 +148,43 @@ def test_masked_step_grid_stride_case():
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("with_gm", [True, False])
+@pytest.mark.parametrize("with_gmprev", [True, False])
+def test_masked_bwd_with_keep_zero_is_the_unmasked_bwd_bit_for_bit(dtype, with_gm, with_gmprev):
+    """keep == 0 everywhere: g_x, g_eps and g_mprev of sta_sampler_step_masked_bwd carry the bits of sta_sampler_step_bwd's (both run the
+    one step1_bwd of csrc/sta_step_dev.h; (1 - 0) g is g). b = 2, latent [4, 8, 8]: 32 lanes per image, so one wavefront spans both
+    images, and hw = 64 wraps inside a row."""
+    from sta import lib
+    from sta.solver import _DT, StepCoef
+    L = lib.load()
+    b, lat = 2, (4, 8, 8)
+    n, hw = 4 * 8 * 8, 8 * 8
+    c = StepCoef(7.5, 0.95, 0.31, 0.997, 0.0417, -0.0133, 0.35, 0.0)        # every coefficient of the backward non-zero
+    gen = torch.Generator().manual_seed(11)
+    g_xn, g_m = torch.randn(b, *lat, generator=gen).cuda(), torch.randn(b, *lat, generator=gen).cuda()
+    keep = torch.zeros(b, 1, 8, 8, device="cuda")
+    ptr = lambda t: t.data_ptr() if t is not None else 0
+    st = torch.cuda.current_stream().cuda_stream
+
+    def outs():
+        return (torch.full((b, *lat), float("nan"), device="cuda"), torch.full((2 * b, *lat), float("nan"), dtype=dtype, device="cuda"),
+                torch.full((b, *lat), float("nan"), device="cuda") if with_gmprev else None)
+
+    px, pe, pp = outs()
+    lib.check(L.sta_sampler_step_bwd(ptr(g_xn), ptr(g_m if with_gm else None), ptr(px), ptr(pe), ptr(pp), b, n, *c[:7], _DT[dtype], st),
+              "sta_sampler_step_bwd")
+    mx, me, mp = outs()
+    lib.check(L.sta_sampler_step_masked_bwd(ptr(g_xn), ptr(g_m if with_gm else None), ptr(keep), ptr(mx), ptr(me), ptr(mp), b, n, hw, *c[:7],
+                                            _DT[dtype], st), "sta_sampler_step_masked_bwd")
+    torch.cuda.synchronize()
+    assert not torch.isnan(px).any() and not torch.isnan(pe.float()).any() and px.abs().max() > 0 and pe.float().abs().max() > 0
+    assert torch.equal(mx.view(torch.int32), px.view(torch.int32))
+    assert torch.equal(me.view(torch.int16), pe.view(torch.int16))
+    if with_gmprev:
+        assert not torch.isnan(pp).any() and torch.equal(mp.view(torch.int32), pp.view(torch.int32))
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("shape", [(2, 3, 16, 24), (1, 3, 64, 64)])
 def test_image_composite_vs_torch_autograd(dtype, shape):
     """sta_image_composite / _bwd against torch autograd in float64: dec with values below -1, above 1 and exactly +-1 (the clamp's
