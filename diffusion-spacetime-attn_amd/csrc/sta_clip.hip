@@ -27,8 +27,6 @@ constexpr int ROWS = GRID * GRID;    // 49 patch rows per view
 constexpr int COLS = 3 * PATCH * PATCH;   // 3072
 constexpr long VIEW_ELEMS = (long)ROWS * COLS;
 
-template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
-
 struct Box {
   int img, y1, y2, x1, x2;
 };

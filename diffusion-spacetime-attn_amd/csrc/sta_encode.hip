@@ -210,8 +210,6 @@ __global__ __launch_bounds__(64 * S2_NW, 2) void conv3x3_s2_nhwc_kernel(const S2
 }
 
 // ------------------------------------------------------------------------------------------------ encoder output -> first UNet input
-template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
-
 template <typename T>
 __global__ __launch_bounds__(256) void vae_encode_step_kernel(const T* __restrict__ h, const float* __restrict__ qw, const float* __restrict__ qb,
                                                               const float* __restrict__ n_post, const float* __restrict__ n_enc,
@@ -299,11 +297,9 @@ int sta_vae_encode_step(const void* h, const float* quant_w, const float* quant_
   if (B <= 0 || hw <= 0) return sta_fail(STA_E_ARG, "vae_encode_step: B=%ld hw=%ld", B, hw);
   if (((uintptr_t)h & 15) != 0) return sta_fail(STA_E_ARG, "vae_encode_step: h must be 16-byte aligned");
   const long npx = B * hw;
-  long blocks = (npx + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    return sta_launch<vae_encode_step_kernel<T>>("vae_encode_step", dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)h, quant_w,
+    return sta_launch<vae_encode_step_kernel<T>>("vae_encode_step", dim3(sta_grid_for(npx)), dim3(256), 0, (hipStream_t)stream, (const T*)h, quant_w,
                                                  quant_b, n_post, n_enc, x, z0, (T*)xin, npx, hw, scale_factor, sqrt_a, sqrt_1ma);
   });
 }

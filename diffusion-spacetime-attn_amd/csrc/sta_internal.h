@@ -69,7 +69,8 @@ STA_INLINE int sta_by_dtype(int dtype, F&& f) {
   return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
 }
 
-// the elementwise kernels: null or 16-byte aligned; 256-lane blocks over nvec vectors, grid-stride from 8192 blocks up
+// the elementwise kernels: a lane's 16 bytes of T; null or 16-byte aligned; 256-lane blocks over nvec vectors, grid-stride from 8192 blocks up
+template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
 inline bool sta_aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
 inline unsigned sta_grid_for(long nvec) {
   long blocks = (nvec + 255) / 256;

@@ -6,9 +6,9 @@
 // 524 288 rows); here y never exists in HBM: the pass reads x once and writes q|k [R][2C] row-major and V^T [C][R] — what
 // sta_selfattn_fwd* reads — 1.34 GB in all.
 //
-// LayerNorm: one wave per row, lane = 8-channel chunk, wave_sum — the per-row arithmetic, lane assignment and summation order of
+// LayerNorm: one wave per row, lane = 8-channel chunk — the row helpers of csrc/sta_trunk_dev.h and the lane assignment of
 // csrc/sta_unet.hip::add_layernorm_kernel (bit-identical y). A wave owns 32 rows per pass as two 16-row items; the normalised
-// chunks cross a wave-private LDS tile (272-byte chunk stride, as add_layernorm_qfrag_kernel) into 2 x 10 MFMA operand fragments
+// chunks cross a wave-private LDS tile (the query-fragment tile of sta_trunk_dev.h) into 2 x 10 MFMA operand fragments
 // that stay in registers for the whole pass. Item `it` holds the rows 8 (c >> 2) + 4 it + (c & 3), c = 0 .. 15, of the 32: in the
 // V part the operands are exchanged (V^T tile = y_frag x wv_frag: a lane's accumulator registers are consecutive ROWS of one
 // channel), and with this interleave the two items of a lane are 8 consecutive rows: one 16-byte store into V^T, 64 contiguous
@@ -30,6 +30,7 @@
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
 #include "sta_wring_dev.h"
+#include "sta_trunk_dev.h"
 
 namespace {
 
@@ -41,8 +42,7 @@ constexpr int LQ_SC_FR = 2 * LQ_NKS;           // 20 fragments per sub-chunk
 constexpr int LQ_NW = 8;
 using LqRing = WRing<LQ_NW, LQ_SC_FR>;         // 3 LDS-DMA instructions per wave per sub-chunk (4 padding copies), 24 KiB per slot
 constexpr int LQ_SLOT = LqRing::SLOT;
-constexpr int LQ_CHUNK = 272;                  // LDS bytes per 8-channel chunk of a 16-row item: 16 rows x 16 B + 16 B of padding
-constexpr int LQ_TILE = (LQ_C / 8) * LQ_CHUNK; // 10 880 bytes per wave
+constexpr int LQ_TILE = (LQ_C / 8) * QFRAG_CHUNK;      // a wave's query-fragment tile of one 16-row item (sta_trunk_dev.h): 10 880 bytes
 constexpr int LQ_LDS = 2 * LQ_SLOT + LQ_NW * LQ_TILE;
 
 // [Wq'; Wk] [2C][C] and Wv [C][C] -> [sub-chunk sc][t][k-step f] fragments. q|k (sc < 20): lane (g, c) holds
@@ -128,46 +128,33 @@ __global__ __launch_bounds__(64 * LQ_NW, 2) void ln_qkv_kernel(const LQ p) {
           const V8 a = raw[it][4 * j + r];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[r][e] = (float)a[e];
-          if (p.bias) {
+          if (p.bias) {      // (ln_add8, written out: through the helper this kernel allocates its registers differently)
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[r][e] += (float)bs[e];
           }
           if (p.s) {   // the residual stream continues in the activation dtype: normalise what is stored
-            V8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              o[e] = (T)v[r][e];
-              v[r][e] = (float)o[e];
-            }
+            const V8 o = ln_round8<T>(v[r]);
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), s_srd, xo[it][4 * j + r], 0, 0);
           }
-          float t = 0.f;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) t += v[r][e];
+          const float t = ln_sum8(0.f, v[r]);
           sum[r] = on ? t : 0.f;
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float mean = wave_sum(sum[r]) / (float)C;
+          const float mean = ln_mean(sum[r], C);
           float q = 0.f;
-          if (on) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float dlt = v[r][e] - mean;
-              q += dlt * dlt;
-            }
-          }
-          const float rstd = rsqrtf(wave_sum(q) / (float)C + p.eps);
+          if (on) q = ln_sq8(q, v[r], mean);
+          const float rstd = ln_rstd(q, C, p.eps);
           V8 o;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = (T)((v[r][e] - mean) * rstd * (float)gm[e] + (float)bt[e]);
-          if (on) *(V8*)(tile + lane * LQ_CHUNK + (4 * j + r) * 16) = o;
+          for (int e = 0; e < 8; ++e) o[e] = (T)ln_affine(v[r][e], mean, rstd, (float)gm[e], (float)bt[e]);
+          if (on) *(V8*)(tile + qfrag_tile_at(lane, 4 * j + r)) = o;
           if (p.y) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), y_srd, xo[it][4 * j + r], 0, 0);
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own tile: written by 40 lanes, read by 64
 #pragma unroll
-      for (int f = 0; f < LQ_NKS; ++f) b[it][f] = *(const V8*)(tile + (4 * f + g) * LQ_CHUNK + c16 * 16);
+      for (int f = 0; f < LQ_NKS; ++f) b[it][f] = *(const V8*)(tile + qfrag_tile_at(4 * f + g, c16));
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // ... before the next item overwrites it
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the sub-chunk 0 DMA, the s / y stores and the previous pass's last stores

@@ -9,7 +9,6 @@
 
 namespace {      // internal to each unit, like the kernels that take a StepCoef
 
-template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
 typedef float F4 __attribute__((ext_vector_type(4)));
 
 struct StepCoef {

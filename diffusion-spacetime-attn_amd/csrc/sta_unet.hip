@@ -8,11 +8,9 @@
 #include "sta_xattn.h"
 #include "sta_unet.h"
 #include "sta_internal.h"
-#include "sta_wring_dev.h"
+#include "sta_trunk_dev.h"
 
 namespace {
-
-template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
 
 // sum over the workgroup; `sh` holds NT/64 floats; every thread gets the result
 template <int NT>
@@ -28,7 +26,7 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
   return t;
 }
 
-__device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+__device__ __forceinline__ float silu_f(float v) { return v * sigmoid_f(v); }
 
 // --------------------------------------------------------------------------------------------------
 // GroupNorm (+ per-(b,c) pre-add) (+ SiLU), NCHW. One workgroup per (b, group) slab of Cg*HW contiguous
@@ -138,19 +136,17 @@ __global__ __launch_bounds__(NT) void gn_silu_kernel(const T* __restrict__ x, co
 // A (b, group) slab is strided here (Cg channels of every pixel), so the work is split the other way: a workgroup
 // takes a chunk of pixels of one image and ALL channels — fully coalesced rows — and a thread keeps one fixed
 // 8-channel column (16 bytes) of every R-th pixel. Kernel 1 writes per-chunk partial sums per group, kernel 2
-// folds them (tiny) and normalises. x is read twice (the second time mostly from L2 / Infinity Cache).
+// folds them (tiny) and normalises. x is read twice (the second time mostly from L2 / Infinity Cache). The split, the workspace
+// layout and a group's mean / rstd come from sta_trunk_dev.h, as in the backward (sta_unet_bwd.hip).
 // --------------------------------------------------------------------------------------------------
-constexpr int GN_NT = 512;          // threads per workgroup: C / 8 <= 512 columns
-constexpr int GN_MAXG = 64;
-
 template <typename T>
 __global__ __launch_bounds__(GN_NT) void gn_nhwc_stats_kernel(const T* __restrict__ x, const T* __restrict__ xb, int Ca, const float* __restrict__ add,
                                                              float* __restrict__ part, int C, int HW, int G, int chunk_px) {
   using V8 = typename V8T<T>::type;
   __shared__ float acc[2 * GN_MAXG];
-  const int CV = C >> 3, R = GN_NT / CV, Cg = C / G;
+  const GnSplit sp = gn_split(C, G);
+  const int R = sp.R, Cg = sp.Cg, row = sp.row, col = sp.col;
   const int b = blockIdx.y, chunk = blockIdx.x;
-  const int row = threadIdx.x / CV, col = threadIdx.x - row * CV;
   if (threadIdx.x < 2 * G) acc[threadIdx.x] = 0.f;
   __syncthreads();
   if (row < R) {
@@ -176,6 +172,7 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_stats_kernel(const T* __restric
       }
     }
     // fold the 8 channels into their (at most two: Cg >= 8 or Cg == 4) groups, then one LDS atomic per group and moment
+    // (gn_nhwc_bwd_kernel folds its two sums the same way)
     const int g0 = (col * 8) / Cg, g1 = (col * 8 + 7) / Cg;
     float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
 #pragma unroll
@@ -194,7 +191,7 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_stats_kernel(const T* __restric
     }
   }
   __syncthreads();
-  if (threadIdx.x < 2 * G) part[((size_t)b * gridDim.x + chunk) * 2 * G + threadIdx.x] = acc[threadIdx.x];
+  if (threadIdx.x < 2 * G) part[gn_part_at(b, gridDim.x, chunk, G, 0) + threadIdx.x] = acc[threadIdx.x];
 }
 
 template <typename T>
@@ -205,9 +202,9 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_apply_kernel(const T* __restric
                                                              int G, int chunk_px, float eps, int silu) {
   using V8 = typename V8T<T>::type;
   __shared__ float mean_s[GN_MAXG], rstd_s[GN_MAXG];
-  const int CV = C >> 3, R = GN_NT / CV, Cg = C / G;
+  const GnSplit sp = gn_split(C, G);
+  const int R = sp.R, Cg = sp.Cg, row = sp.row, col = sp.col;
   const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
-  const int row = threadIdx.x / CV, col = threadIdx.x - row * CV;
   if (threadIdx.x < G) {
     float s = 0.f, q = 0.f;
     if (cs_a) {
@@ -221,14 +218,11 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_apply_kernel(const T* __restric
         q += st[1] + 2.f * a * st[0] + (float)HW * a * a;
       }
     } else
-    for (int k = 0; k < nchunk; ++k) {
-      s += part[((size_t)b * nchunk + k) * 2 * G + 2 * threadIdx.x];
-      q += part[((size_t)b * nchunk + k) * 2 * G + 2 * threadIdx.x + 1];
-    }
-    const float inv_n = 1.0f / ((float)Cg * (float)HW);
-    const float mean = s * inv_n;
-    mean_s[threadIdx.x] = mean;
-    rstd_s[threadIdx.x] = rsqrtf(fmaxf(q * inv_n - mean * mean, 0.f) + eps);
+      for (int k = 0; k < nchunk; ++k) {      // in chunk order
+        s += part[gn_part_at(b, nchunk, k, G, threadIdx.x)];
+        q += part[gn_part_at(b, nchunk, k, G, threadIdx.x) + 1];
+      }
+    gn_mean_rstd(s, q, 1.0f / ((float)Cg * (float)HW), eps, mean_s[threadIdx.x], rstd_s[threadIdx.x]);
   }
   __syncthreads();
   if (row >= R) return;
@@ -311,19 +305,12 @@ __global__ __launch_bounds__(256) void add_bias_rows_kernel(const T* __restrict_
 // --------------------------------------------------------------------------------------------------
 // GEGLU: y[r][j] = x[r][j] * gelu(x[r][D + j])
 // --------------------------------------------------------------------------------------------------
-// exact-erf GELU with erf from Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7 absolute: 2000x below one ulp of the 16-bit
-// result around 1): a reciprocal, five fma and one exp2 instead of libm's branchy erff: 434 -> 410 us at [262144 x 2560] (4.9 TB/s
+// exact-erf GELU with the polynomial erf of sta_trunk_dev.h instead of libm's branchy erff: 434 -> 410 us at [262144 x 2560] (4.9 TB/s
 // of reads + writes), 216 -> 195 us at [65536 x 5120].
 __device__ __forceinline__ float gelu_erf(float g) {
-  const float x = fabsf(g) * 0.70710678118654752f;
-  const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, x, 1.0f));
-  float p = __builtin_fmaf(1.061405429f, t, -1.453152027f);
-  p = __builtin_fmaf(p, t, 1.421413741f);
-  p = __builtin_fmaf(p, t, -0.284496736f);
-  p = __builtin_fmaf(p, t, 0.254829592f);
-  const float e = p * t * __builtin_amdgcn_exp2f(-1.4426950408889634f * x * x);      // 1 - erf(|g| / sqrt 2)
-  const float phi = g >= 0.f ? 1.0f - 0.5f * e : 0.5f * e;                            // Phi(g)
-  return g * phi;
+  float er, ex;
+  gelu_gate_parts(g, er, ex);
+  return g * gelu_cdf(g, er);
 }
 
 template <typename T>
@@ -366,41 +353,18 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const T* __restrict_
       const V8 a = xr[idx];
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[j][e] = (float)a[e];
-      if (fr) {
-        const V8 b = fr[idx];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[j][e] += (float)b[e];
-      }
-      if (bias) {
-        const V8 c = ((const V8*)bias)[idx];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[j][e] += (float)c[e];
-      }
-      if (s_out) {   // the residual stream continues in the activation dtype: normalise what is stored
-        V8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          o[e] = (T)v[j][e];
-          v[j][e] = (float)o[e];
-        }
-        ((V8*)(s_out + row * C))[idx] = o;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sum += v[j][e];
+      if (fr) ln_add8<T>(v[j], fr[idx]);
+      if (bias) ln_add8<T>(v[j], ((const V8*)bias)[idx]);
+      if (s_out) ((V8*)(s_out + row * C))[idx] = ln_round8<T>(v[j]);
+      sum = ln_sum8(sum, v[j]);
     }
   }
-  const float mean = wave_sum(sum) / (float)C;
+  const float mean = ln_mean(sum, C);
   float q = 0.f;
 #pragma unroll
   for (int j = 0; j < NV; ++j)
-    if (lane + 64 * j < nvec) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float dlt = v[j][e] - mean;
-        q += dlt * dlt;
-      }
-    }
-  const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+    if (lane + 64 * j < nvec) q = ln_sq8(q, v[j], mean);
+  const float rstd = ln_rstd(q, C, eps);
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int idx = lane + 64 * j;
@@ -408,7 +372,7 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const T* __restrict_
       const V8 gm = ((const V8*)gamma)[idx], bt = ((const V8*)beta)[idx];
       V8 o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (T)((v[j][e] - mean) * rstd * (float)gm[e] + (float)bt[e]);
+      for (int e = 0; e < 8; ++e) o[e] = (T)ln_affine(v[j][e], mean, rstd, (float)gm[e], (float)bt[e]);
       ((V8*)(y + row * C))[idx] = o;
     }
   }
@@ -421,104 +385,24 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const T* __restrict_
 // instruction (the shape profiles/r03_vmem_shapes.txt prices at 1.5x the adjacent-lane one). Here the 16 rows of a pixel
 // group leave as C/32 fragments of 1 KiB: fragment s holds, at byte (16 g + c) * 16, channels 32 s + 8 g .. + 7 of row c —
 // a transpose of [16 rows][C/8 chunks] to [C/8 chunks][16 rows] in 16-byte units, (R/16) * (C/32) KiB in all (the same
-// bytes as row-major). One workgroup = one group of 16 rows, a wave takes 4 of them (same per-row arithmetic and lane
-// assignment as add_layernorm_kernel: bit-identical values); the chunks cross LDS (272-byte chunk stride: conflict-free
-// 16-byte writes and reads) so that the stores are 1-KiB contiguous per wave instruction.
+// bytes as row-major). One workgroup = one group of 16 rows, a wave takes 4 of them (the row helpers and lane assignment
+// of add_layernorm_kernel: bit-identical values); the chunks cross the LDS tile of sta_trunk_dev.h so that the stores are
+// 1-KiB contiguous per wave instruction. A lane holds NV chunks of each of its rows: NV = 1 for C <= 512 (SD-v1 level 0), NV = 2
+// for 512 < C <= 1024 (level 1, C = 640: norm2's output feeding the locals-from-L2 projection-fused kernel of csrc/sta_xattn_proj.hip).
 // --------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, int NV>
 __global__ __launch_bounds__(256) void add_layernorm_qfrag_kernel(const T* __restrict__ x, const T* __restrict__ f,
                                                                 const T* __restrict__ bias, const T* __restrict__ gamma,
                                                                 const T* __restrict__ beta, T* s_out, T* __restrict__ y,
                                                                 long R, int C, float eps) {
   using V8 = typename V8T<T>::type;
-  constexpr int CHUNK = 272;                              // LDS bytes per chunk: 16 rows x 16 B + 16 B of padding
-  __shared__ __attribute__((aligned(16))) char tile[64 * CHUNK];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nvec = C >> 3;
-  const long row0 = (long)blockIdx.x * 16 + 4 * wv;
-  const bool on = lane < nvec;
-  float v[4][8];
-  float sum[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {                           // every load of the wave's four rows is issued before the first use
-    const long row = row0 + r;
-    V8 a = {}, b = {};
-    if (on) {
-      a = ((const V8*)(x + row * C))[lane];
-      if (f) b = ((const V8*)(f + row * C))[lane];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[r][e] = (float)a[e];
-    if (f) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[r][e] += (float)b[e];
-    }
-  }
-  V8 bs = {}, gm = {}, bt = {};
-  if (on) {
-    if (bias) bs = ((const V8*)bias)[lane];
-    gm = ((const V8*)gamma)[lane];
-    bt = ((const V8*)beta)[lane];
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const long row = row0 + r;
-    if (bias) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[r][e] += (float)bs[e];
-    }
-    if (s_out) {
-      V8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        o[e] = (T)v[r][e];
-        v[r][e] = (float)o[e];
-      }
-      if (on) ((V8*)(s_out + row * C))[lane] = o;
-    }
-    float t = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t += v[r][e];
-    sum[r] = on ? t : 0.f;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float mean = wave_sum(sum[r]) / (float)C;
-    float q = 0.f;
-    if (on) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float dlt = v[r][e] - mean;
-        q += dlt * dlt;
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
-    V8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (T)((v[r][e] - mean) * rstd * (float)gm[e] + (float)bt[e]);
-    if (on) *(V8*)(tile + lane * CHUNK + (4 * wv + r) * 16) = o;
-  }
-  __syncthreads();
-  V8* yo = (V8*)y + (size_t)blockIdx.x * nvec * 16;
-  for (int t = threadIdx.x; t < nvec * 16; t += 256) yo[t] = *(const V8*)(tile + (t >> 4) * CHUNK + (t & 15) * 16);
-}
-
-// The same for 512 < C <= 1024 (SD-v1 level 1, C = 640: norm2's output feeding the locals-from-L2 projection-fused kernel of
-// csrc/sta_xattn_proj.hip): a lane holds chunks `lane` and `lane + 64` of its four rows — add_layernorm_kernel's own lane
-// assignment and summation order (chunk 0's eight values, then chunk 1's), so the values stay bit-identical to the row-major pass.
-template <typename T>
-__global__ __launch_bounds__(256) void add_layernorm_qfrag_wide_kernel(const T* __restrict__ x, const T* __restrict__ f,
-                                                                     const T* __restrict__ bias, const T* __restrict__ gamma,
-                                                                     const T* __restrict__ beta, T* s_out, T* __restrict__ y,
-                                                                     long R, int C, float eps) {
-  using V8 = typename V8T<T>::type;
-  constexpr int CHUNK = 272, NV = 2;
-  __shared__ __attribute__((aligned(16))) char tile[64 * NV * CHUNK];
+  __shared__ __attribute__((aligned(16))) char tile[64 * NV * QFRAG_CHUNK];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nvec = C >> 3;
   const long row0 = (long)blockIdx.x * 16 + 4 * wv;
   float v[4][NV][8];
-  float sum[4], sq[4];
+  float sum[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
+  for (int r = 0; r < 4; ++r) {                           // every load of the wave's four rows is issued before the first use
     const long row = row0 + r;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
@@ -530,10 +414,7 @@ __global__ __launch_bounds__(256) void add_layernorm_qfrag_wide_kernel(const T* 
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[r][j][e] = (float)a[e];
-      if (f) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[r][j][e] += (float)b[e];
-      }
+      if (f) ln_add8<T>(v[r][j], b);
     }
   }
   V8 bs[NV] = {}, gm[NV] = {}, bt[NV] = {};
@@ -553,53 +434,35 @@ __global__ __launch_bounds__(256) void add_layernorm_qfrag_wide_kernel(const T* 
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int idx = lane + 64 * j;
-      if (bias) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[r][j][e] += (float)bs[j][e];
-      }
+      if (bias) ln_add8<T>(v[r][j], bs[j]);
       if (s_out) {
-        V8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          o[e] = (T)v[r][j][e];
-          v[r][j][e] = (float)o[e];
-        }
+        const V8 o = ln_round8<T>(v[r][j]);
         if (idx < nvec) ((V8*)(s_out + row * C))[idx] = o;
       }
-      if (idx < nvec) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) t += v[r][j][e];
-      }
+      if (idx < nvec) t = ln_sum8(t, v[r][j]);
     }
     sum[r] = t;
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float mean = wave_sum(sum[r]) / (float)C;
+    const float mean = ln_mean(sum[r], C);
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < NV; ++j)
-      if (lane + 64 * j < nvec) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float dlt = v[r][j][e] - mean;
-          q += dlt * dlt;
-        }
-      }
-    sq[r] = q;
-    const float rstd = rsqrtf(wave_sum(sq[r]) / (float)C + eps);
+      if (lane + 64 * j < nvec) q = ln_sq8(q, v[r][j], mean);
+    const float rstd = ln_rstd(q, C, eps);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int idx = lane + 64 * j;
       V8 o;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (T)((v[r][j][e] - mean) * rstd * (float)gm[j][e] + (float)bt[j][e]);
-      if (idx < nvec) *(V8*)(tile + idx * CHUNK + (4 * wv + r) * 16) = o;
+      for (int e = 0; e < 8; ++e) o[e] = (T)ln_affine(v[r][j][e], mean, rstd, (float)gm[j][e], (float)bt[j][e]);
+      if (idx < nvec) *(V8*)(tile + qfrag_tile_at(idx, 4 * wv + r)) = o;
     }
   }
   __syncthreads();
   V8* yo = (V8*)y + (size_t)blockIdx.x * nvec * 16;
-  for (int t = threadIdx.x; t < nvec * 16; t += 256) yo[t] = *(const V8*)(tile + (t >> 4) * CHUNK + (t & 15) * 16);
+  for (int t = threadIdx.x; t < nvec * 16; t += 256) yo[t] = *(const V8*)(tile + qfrag_tile_at(t >> 4, t & 15));
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -668,12 +531,10 @@ int sta_geglu(const void* x, void* y, long R, int D, int dtype, void* stream) {
   if (!x || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (R <= 0 || D <= 0 || D % 8) return sta_fail(STA_E_ARG, "geglu: R=%ld D=%d (need D %% 8 == 0)", R, D);
   const long nvec = R * (D / 8);
-  long blocks = (nvec + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
   hipStream_t st = (hipStream_t)stream;
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    return sta_launch<geglu_kernel<T>>("geglu launch", dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, (T*)y, nvec, D / 8);
+    return sta_launch<geglu_kernel<T>>("geglu launch", dim3(sta_grid_for(nvec)), dim3(256), 0, st, (const T*)x, (T*)y, nvec, D / 8);
   });
 }
 
@@ -699,17 +560,13 @@ int sta_add_layernorm_qfrag(const void* x, const void* f, const void* bias, cons
     return sta_fail(STA_E_ARG, "add_layernorm_qfrag: R=%ld C=%d (need R %% 16 == 0, C %% 32 == 0, C <= 1024)", R, C);
   const unsigned blocks = (unsigned)(R / 16);
   hipStream_t st = (hipStream_t)stream;
-  if (C > 512) {      // two chunks per lane
-    return sta_by_dtype(dtype, [&](auto tag) {
-      using T = decltype(tag);
-      return sta_launch<add_layernorm_qfrag_wide_kernel<T>>("add_layernorm_qfrag launch", dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)f,
-                                                            (const T*)bias, (const T*)gamma, (const T*)beta, (T*)s, (T*)y, R, C, eps);
-    });
-  }
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    return sta_launch<add_layernorm_qfrag_kernel<T>>("add_layernorm_qfrag launch", dim3(blocks), dim3(256), 0, st, (const T*)x, (const T*)f,
-                                                     (const T*)bias, (const T*)gamma, (const T*)beta, (T*)s, (T*)y, R, C, eps);
+    const char* const what = "add_layernorm_qfrag launch";
+    const T *xt = (const T*)x, *ft = (const T*)f, *bs = (const T*)bias, *g = (const T*)gamma, *b = (const T*)beta;
+    if (C > 512)      // two chunks per lane
+      return sta_launch<add_layernorm_qfrag_kernel<T, 2>>(what, dim3(blocks), dim3(256), 0, st, xt, ft, bs, g, b, (T*)s, (T*)y, R, C, eps);
+    return sta_launch<add_layernorm_qfrag_kernel<T, 1>>(what, dim3(blocks), dim3(256), 0, st, xt, ft, bs, g, b, (T*)s, (T*)y, R, C, eps);
   });
 }
 
@@ -719,21 +576,12 @@ int sta_add_bias_nchw(const void* a, const void* b, const void* bias, void* y, i
   if (!a || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (B <= 0 || C <= 0 || HW <= 0 || HW % 8) return sta_fail(STA_E_ARG, "add_bias: B=%d C=%d HW=%d (need HW %% 8 == 0)", B, C, HW);
   const long nvec = (long)B * C * (HW / 8);
-  long blocks = (nvec + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
   hipStream_t st = (hipStream_t)stream;
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    return sta_launch<add_bias_nchw_kernel<T>>("add_bias_nchw launch", dim3((unsigned)blocks), dim3(256), 0, st, (const T*)a, (const T*)b,
+    return sta_launch<add_bias_nchw_kernel<T>>("add_bias_nchw launch", dim3(sta_grid_for(nvec)), dim3(256), 0, st, (const T*)a, (const T*)b,
                                                (const T*)bias, (T*)y, nvec, C, HW / 8);
   });
-}
-
-static int gn_nhwc_chunks(int HW) {
-  int n = HW / 8;
-  if (n > 32) n = 32;
-  if (n < 1) n = 1;
-  return n;
 }
 
 size_t sta_groupnorm_nhwc_workspace_bytes(int B, int HW, int G) {
@@ -745,9 +593,7 @@ static int groupnorm_silu_nhwc_impl(const void* x, const void* xb, int Ca, const
                                     void* workspace, int B, int C, int HW, int G, float eps, int silu, int dtype, void* stream) {
   g_sta_err[0] = 0;
   if (!x || !gamma || !beta || !y || !workspace) return sta_fail(STA_E_ARG, "null pointer");
-  if (B <= 0 || C <= 0 || HW <= 0 || G <= 0 || G > GN_MAXG || C % G || C % 8 || (C / G < 8 && C / G != 4) || C / 8 > GN_NT)
-    return sta_fail(STA_E_ARG, "groupnorm nhwc: B=%d C=%d HW=%d G=%d (need C %% 8 == 0, C/G >= 8 or == 4, C <= %d, G <= %d)", B, C, HW,
-                    G, 8 * GN_NT, GN_MAXG);
+  if (const int rc = gn_nhwc_shape_ok("groupnorm nhwc", B, C, HW, G)) return rc;
   if (xb && (Ca <= 0 || Ca >= C || Ca % 8)) return sta_fail(STA_E_ARG, "groupnorm nhwc cat: Ca=%d of C=%d (need 0 < Ca < C, Ca %% 8 == 0)", Ca, C);
   const int nchunk = gn_nhwc_chunks(HW), chunk_px = (HW + nchunk - 1) / nchunk;
   const dim3 grid(nchunk, B);
@@ -787,9 +633,7 @@ int sta_groupnorm_silu_nhwc_cstats(const void* xa, const void* xb, int Ca, const
                                    void* stream) {
   g_sta_err[0] = 0;
   if (!xa || !stats_a || !gamma || !beta || !y || (xb && !stats_b)) return sta_fail(STA_E_ARG, "null pointer");
-  if (B <= 0 || C <= 0 || HW <= 0 || G <= 0 || G > GN_MAXG || C % G || C % 8 || (C / G < 8 && C / G != 4) || C / 8 > GN_NT)
-    return sta_fail(STA_E_ARG, "groupnorm nhwc: B=%d C=%d HW=%d G=%d (need C %% 8 == 0, C/G >= 8 or == 4, C <= %d, G <= %d)", B, C, HW,
-                    G, 8 * GN_NT, GN_MAXG);
+  if (const int rc = gn_nhwc_shape_ok("groupnorm nhwc", B, C, HW, G)) return rc;
   if (xb && (Ca <= 0 || Ca >= C || Ca % 8)) return sta_fail(STA_E_ARG, "groupnorm nhwc cat: Ca=%d of C=%d (need 0 < Ca < C, Ca %% 8 == 0)", Ca, C);
   const int nchunk = gn_nhwc_chunks(HW), chunk_px = (HW + nchunk - 1) / nchunk;
   const dim3 grid(nchunk, B);
@@ -808,12 +652,10 @@ int sta_add_bias_rows(const void* a, const void* b, const void* bias, void* y, l
   if (!a || !y) return sta_fail(STA_E_ARG, "null pointer");
   if (rows <= 0 || C <= 0 || C % 8) return sta_fail(STA_E_ARG, "add_bias_rows: rows=%ld C=%d (need C %% 8 == 0)", rows, C);
   const long nvec = rows * (C / 8);
-  long blocks = (nvec + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
   hipStream_t st = (hipStream_t)stream;
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    return sta_launch<add_bias_rows_kernel<T>>("add_bias_rows launch", dim3((unsigned)blocks), dim3(256), 0, st, (const T*)a, (const T*)b,
+    return sta_launch<add_bias_rows_kernel<T>>("add_bias_rows launch", dim3(sta_grid_for(nvec)), dim3(256), 0, st, (const T*)a, (const T*)b,
                                                (const T*)bias, (T*)y, nvec, C / 8);
   });
 }

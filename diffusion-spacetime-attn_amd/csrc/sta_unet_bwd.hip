@@ -13,11 +13,9 @@
 #include "sta_xattn.h"
 #include "sta_unet.h"
 #include "sta_internal.h"
-#include "sta_wring_dev.h"
+#include "sta_trunk_dev.h"
 
 namespace {
-
-template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type(8))); };
 
 // --------------------------------------------------------------------------------------------------
 // GroupNorm (+ pre-add) (+ SiLU) backward on NHWC activations, same work split as the forward (sta_unet.hip): a workgroup
@@ -26,11 +24,9 @@ template <typename T> struct V8T { typedef T type __attribute__((ext_vector_type
 //   t  = dy * silu'(z) * gamma  (silu'(z) = s + z s (1 - s), s = sigmoid z);   per (b, group): m1 = mean t, m2 = mean t xh
 //   dx = rstd * (t - m1 - xh * m2)
 // Kernel 1 writes per-chunk partial sums of (t, t xh) per group, kernel 2 folds them and writes dx. mean / rstd are
-// rebuilt from the FORWARD's partial sums (its workspace, kept by the caller) exactly as the forward folded them.
+// rebuilt from the FORWARD's partial sums (its workspace, kept by the caller) as the forward folded them: the split, the
+// workspace layout and the fold are those of sta_trunk_dev.h in both directions.
 // --------------------------------------------------------------------------------------------------
-constexpr int GN_NT = 512;
-constexpr int GN_MAXG = 64;
-
 template <typename T, bool APPLY>
 __global__ __launch_bounds__(GN_NT) void gn_nhwc_bwd_kernel(const T* __restrict__ x, const float* __restrict__ add,
                                                            const T* __restrict__ gamma, const T* __restrict__ beta,
@@ -40,23 +36,21 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_bwd_kernel(const T* __restrict_
   using V8 = typename V8T<T>::type;
   __shared__ float mean_s[GN_MAXG], rstd_s[GN_MAXG], m1_s[GN_MAXG], m2_s[GN_MAXG];
   __shared__ float acc[2 * GN_MAXG];
-  const int CV = C >> 3, R = GN_NT / CV, Cg = C / G;
+  const GnSplit sp = gn_split(C, G);
+  const int R = sp.R, Cg = sp.Cg, row = sp.row, col = sp.col;
   const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
-  const int row = threadIdx.x / CV, col = threadIdx.x - row * CV;
   if (threadIdx.x < G) {
     float s = 0.f, q = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int k = 0; k < nchunk; ++k) {
-      s += part[((size_t)b * nchunk + k) * 2 * G + 2 * threadIdx.x];
-      q += part[((size_t)b * nchunk + k) * 2 * G + 2 * threadIdx.x + 1];
+    for (int k = 0; k < nchunk; ++k) {      // the forward's sums in the forward's order, and this pass's own
+      s += part[gn_part_at(b, nchunk, k, G, threadIdx.x)];
+      q += part[gn_part_at(b, nchunk, k, G, threadIdx.x) + 1];
       if (APPLY) {
-        s1 += partb[((size_t)b * nchunk + k) * 2 * G + 2 * threadIdx.x];
-        s2 += partb[((size_t)b * nchunk + k) * 2 * G + 2 * threadIdx.x + 1];
+        s1 += partb[gn_part_at(b, nchunk, k, G, threadIdx.x)];
+        s2 += partb[gn_part_at(b, nchunk, k, G, threadIdx.x) + 1];
       }
     }
     const float inv_n = 1.0f / ((float)Cg * (float)HW);
-    const float mean = s * inv_n;
-    mean_s[threadIdx.x] = mean;
-    rstd_s[threadIdx.x] = rsqrtf(fmaxf(q * inv_n - mean * mean, 0.f) + eps);
+    gn_mean_rstd(s, q, inv_n, eps, mean_s[threadIdx.x], rstd_s[threadIdx.x]);      // the forward's statistics, by the forward's fold
     m1_s[threadIdx.x] = s1 * inv_n;
     m2_s[threadIdx.x] = s2 * inv_n;
   }
@@ -89,7 +83,7 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_bwd_kernel(const T* __restrict_
         float t = (float)d[e];
         if (silu) {
           const float z = xh * gm[e] + bt[e];
-          const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+          const float sg = sigmoid_f(z);
           t *= sg * (1.0f + z * (1.0f - sg));
         }
         t *= gm[e];
@@ -102,7 +96,7 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_bwd_kernel(const T* __restrict_
       }
       if (APPLY) *(V8*)(dx + off) = o;
     }
-    if (!APPLY) {
+    if (!APPLY) {      // the fold of gn_nhwc_stats_kernel (sta_unet.hip), on this pass's two sums
       const int g0 = (col * 8) / Cg, g1 = (col * 8 + 7) / Cg;
       float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
 #pragma unroll
@@ -123,13 +117,13 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_bwd_kernel(const T* __restrict_
   }
   if (!APPLY) {
     __syncthreads();
-    if (threadIdx.x < 2 * G) partb[((size_t)b * nchunk + chunk) * 2 * G + threadIdx.x] = acc[threadIdx.x];
+    if (threadIdx.x < 2 * G) partb[gn_part_at(b, nchunk, chunk, G, 0) + threadIdx.x] = acc[threadIdx.x];
   }
 }
 
 // --------------------------------------------------------------------------------------------------
 // GEGLU backward: y = a * gelu(g), x = [a | g] per row:  da = dy * gelu(g);  dg = dy * a * (Phi(g) + g phi(g))
-// (the same Abramowitz & Stegun 7.1.26 erf as the forward)
+// (the forward's erf: gelu_gate_parts of sta_trunk_dev.h)
 // --------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void geglu_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dxo,
@@ -146,15 +140,9 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const T* __restrict__ x,
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float g = (float)gt[e];
-      const float ax = fabsf(g) * 0.70710678118654752f;
-      const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, ax, 1.0f));
-      float p = __builtin_fmaf(1.061405429f, t, -1.453152027f);
-      p = __builtin_fmaf(p, t, 1.421413741f);
-      p = __builtin_fmaf(p, t, -0.284496736f);
-      p = __builtin_fmaf(p, t, 0.254829592f);
-      const float ex = __builtin_amdgcn_exp2f(-1.4426950408889634f * ax * ax);     // exp(-g^2 / 2)
-      const float er = p * t * ex;                                                  // 1 - erf(|g| / sqrt 2)
-      const float phi = g >= 0.f ? 1.0f - 0.5f * er : 0.5f * er;                    // Phi(g)
+      float er, ex;
+      gelu_gate_parts(g, er, ex);
+      const float phi = gelu_cdf(g, er);
       const float dv = (float)d[e];
       oa[e] = (T)(dv * g * phi);
       og[e] = (T)(dv * (float)a[e] * (phi + g * 0.3989422804014327f * ex));
@@ -191,22 +179,22 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
       for (int e = 0; e < 8; ++e) {
         v[j][e] = (float)a[e];
         t[j][e] = (float)d[e] * (float)gm[e];
-        sum += v[j][e];
+        sum += v[j][e];      // ln_sum8's order, fused with the loads
       }
     }
   }
-  const float mean = wave_sum(sum) / (float)C;
+  const float mean = ln_mean(sum, C);
   float q = 0.f;
 #pragma unroll
   for (int j = 0; j < NV; ++j)
     if (lane + 64 * j < nvec) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        v[j][e] -= mean;
+        v[j][e] -= mean;      // ln_sq8's terms in its order; written out because xh below wants the centred value kept
         q += v[j][e] * v[j][e];
       }
     }
-  const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+  const float rstd = ln_rstd(q, C, eps);
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < NV; ++j)
@@ -218,7 +206,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
         s2 += t[j][e] * v[j][e];
       }
     }
-  const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+  const float m1 = ln_mean(s1, C), m2 = ln_mean(s2, C);
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int idx = lane + 64 * j;
@@ -239,17 +227,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
   }
 }
 
-int gn_nhwc_chunks_bwd(int HW) {      // must equal gn_nhwc_chunks of sta_unet.hip (the forward's workspace layout)
-  int n = HW / 8;
-  if (n > 32) n = 32;
-  if (n < 1) n = 1;
-  return n;
-}
-
 template <typename T>
 int gn_bwd_launch(const void* x, const float* add, const void* gamma, const void* beta, const float* part, const void* dy,
                    float* partb, void* dx, int B, int C, int HW, int G, float eps, int silu, hipStream_t st) {
-  const int nchunk = gn_nhwc_chunks_bwd(HW), chunk_px = (HW + nchunk - 1) / nchunk;
+  const int nchunk = gn_nhwc_chunks(HW), chunk_px = (HW + nchunk - 1) / nchunk;
   const dim3 grid(nchunk, B);
   const char* const what = "groupnorm_silu_nhwc_bwd launch";
   if (const int rc = sta_launch<gn_nhwc_bwd_kernel<T, false>>(what, grid, dim3(GN_NT), 0, st, (const T*)x, add, (const T*)gamma, (const T*)beta,
@@ -268,9 +249,7 @@ int sta_groupnorm_silu_nhwc_bwd(const void* x, const float* add, const void* gam
                                 int dtype, void* stream) {
   g_sta_err[0] = 0;
   if (!x || !gamma || !beta || !dy || !dx || !fwd_workspace || !bwd_workspace) return sta_fail(STA_E_ARG, "null pointer");
-  if (B <= 0 || C <= 0 || HW <= 0 || G <= 0 || G > GN_MAXG || C % G || C % 8 || (C / G < 8 && C / G != 4) || C / 8 > GN_NT)
-    return sta_fail(STA_E_ARG, "groupnorm nhwc bwd: B=%d C=%d HW=%d G=%d (need C %% 8 == 0, C/G >= 8 or == 4, C <= %d, G <= %d)", B, C, HW,
-                    G, 8 * GN_NT, GN_MAXG);
+  if (const int rc = gn_nhwc_shape_ok("groupnorm nhwc bwd", B, C, HW, G)) return rc;
   return sta_by_dtype(dtype, [&](auto tag) {
     return gn_bwd_launch<decltype(tag)>(x, add, gamma, beta, (const float*)fwd_workspace, dy, (float*)bwd_workspace, dx, B, C, HW, G, eps, silu,
                                         (hipStream_t)stream);
@@ -282,11 +261,9 @@ int sta_geglu_bwd(const void* x, const void* dy, void* dx, long R, int D, int dt
   if (!x || !dy || !dx) return sta_fail(STA_E_ARG, "null pointer");
   if (R <= 0 || D <= 0 || D % 8) return sta_fail(STA_E_ARG, "geglu bwd: R=%ld D=%d (need D %% 8 == 0)", R, D);
   const long nvec = R * (D / 8);
-  long blocks = (nvec + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    return sta_launch<geglu_bwd_kernel<T>>("geglu_bwd launch", dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+    return sta_launch<geglu_bwd_kernel<T>>("geglu_bwd launch", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)x,
                                            (const T*)dy, (T*)dx, nvec, D / 8);
   });
 }

@@ -24,7 +24,8 @@ constexpr unsigned SRD_DROP = 0xfffffff0u;
 __host__ __device__ constexpr int frag_sigma(int u, int rho) { return 32 * (u >> 1) + 8 * (rho >> 2) + 4 * (u & 1) + (rho & 3); }
 
 // Sum over the 64 lanes of a wave, result in every lane. ONE butterfly for every LayerNorm in the library: kernels that promise
-// bit-identical row statistics (sta_lnqkv.hip against sta_unet.hip::add_layernorm_kernel) get them by calling the same function.
+// bit-identical row statistics (sta_lnqkv.hip against sta_unet.hip::add_layernorm_kernel) get them by calling the same function
+// (the wave-per-row kernels through ln_mean / ln_rstd of sta_trunk_dev.h).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

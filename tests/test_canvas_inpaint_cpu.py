@@ -189,13 +189,13 @@ def test_the_sampler_step_is_defined_once():
     csrc = lambda n: open(os.path.join(lib.CSRC, n)).read()
     header = csrc("sta_step_dev.h")
     step_defs = ("float step1(", "void step1_bwd(")
-    helper_defs = ("struct V8T", "typedef float F4", "struct StepCoef", "void load8(", "void store8(", " round8(const float", "void store_pair(")
+    helper_defs = ("typedef float F4", "struct StepCoef", "void load8(", "void store8(", " round8(const float", "void store_pair(")
     for d in step_defs + helper_defs:
         assert header.count(d) == 1, d
     for n in ("sta_sampler.hip", "sta_inpaint.hip", "sta_window.hip", "sta_guide.hip"):
         text = csrc(n)
         assert '#include "sta_step_dev.h"' in text, n
-        for d in step_defs + helper_defs:
+        for d in step_defs + helper_defs + ("struct V8T",):      # V8T: once for the whole library, see the next test
             assert d not in text, (n, d)
         assert "load8(" in text and "store8(" in text and "V8T<T>" in text, n
     assert all("step1(" in csrc(n) for n in ("sta_sampler.hip", "sta_inpaint.hip", "sta_window.hip"))
@@ -205,6 +205,30 @@ def test_the_sampler_step_is_defined_once():
     for n in ("sta_sampler.hip", "sta_inpaint.hip", "sta_window.hip"):
         for field in ("c.sigma_t", "c.c_x", "c.c_m", "c.c_p", "c.c_e", "c.c_n", "c.scale"):
             assert field not in csrc(n), (n, field)
+
+
+def test_the_trunk_glue_arithmetic_is_defined_once():
+    """The LayerNorm row helpers, the query-fragment LDS tile and the NHWC GroupNorm geometry have one definition, csrc/sta_trunk_dev.h
+    (V8T: csrc/sta_internal.h); the forward, backward and fused-projection sources include it and restate none of its constants."""
+    import glob
+    import re
+    from sta import lib
+    texts = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(lib.CSRC, "*.hip")) + glob.glob(os.path.join(lib.CSRC, "*.h"))}
+    definitions = {"V8T": r"struct V8T\b", "GN_NT": r"constexpr int GN_NT\b", "GN_MAXG": r"constexpr int GN_MAXG\b",
+                   "gn_nhwc_chunks": r"\bint gn_nhwc_chunks\(int", "the 272-byte tile constant": r"constexpr int \w+ = 272\b"}
+    homes = {"V8T": "sta_internal.h"}
+    for what, pattern in definitions.items():
+        found = {n: len(re.findall(pattern, t)) for n, t in texts.items() if re.search(pattern, t)}
+        assert found == {homes.get(what, "sta_trunk_dev.h"): 1}, (what, found)
+    for n, t in texts.items():      # nor is 272 a factor of an offset anywhere else
+        if n != "sta_trunk_dev.h":
+            assert not re.search(r"\*\s*272\b|\b272\s*\*|CHUNK = 272", t), n
+        assert "gn_nhwc_chunks_bwd" not in t and "add_layernorm_qfrag_wide_kernel" not in t, n
+    for n in ("sta_unet.hip", "sta_unet_bwd.hip", "sta_lnqkv.hip"):
+        assert '#include "sta_trunk_dev.h"' in texts[n], n
+        assert "gn_part_at(" in texts[n] or n == "sta_lnqkv.hip", n
+    for n in ("sta_unet.hip", "sta_lnqkv.hip"):
+        assert "qfrag_tile_at(" in texts[n] and "QFRAG_CHUNK" in texts[n], n
 
 
 # ---------------------------------------------------------------------------------------------------
