@@ -240,3 +240,6 @@ int sta_to_out_ln_ofrag(const void* blended_ofrag, const void* packed_wo, const 
 }
 
 }  // extern "C"
+
+// The level-1 passes (C = 640): Linear + residual (+ LayerNorm) over row-major activations, built with this translation unit
+#include "sta_rows640.hip"

@@ -126,9 +126,10 @@ class CrossAttention(nn.Module):
         o = _ops.SelfAttentionQKV.apply(F.linear(x, _fused.cached_image(self, "wqkv", ws, cat)), self.heads, _ops.LN2)
         return self.to_out(o)
 
-    def _self_attention_hip(self, x, pre_to_out_sfrag=False):
+    def _self_attention_hip(self, x, pre_to_out_sfrag=False, pre_to_out=False):
         """attn1 without autograd: the flash-style HIP kernel (csrc/sta_selfattn.hip). `pre_to_out_sfrag`: return the kernel's
-        output BEFORE to_out, in its out-fragment order (the block then runs to_out + residual + norm2 as one pass). q and k come out of ONE
+        output BEFORE to_out, in its out-fragment order (the block then runs to_out + residual + norm2 as one pass); `pre_to_out`:
+        the same row-major (the level-1 pass, plain 16-bit Linears only). q and k come out of ONE
         GEMM against the concatenated [Wq; Wk] (the kernel takes a row stride), V is produced already
         transposed because the PV product wants keys contiguous per channel: ONE plain GEMM W_v . X^T over the
         flattened batch gives [C, B*N], which the kernel reads through (row, batch) strides. (A batched
@@ -142,7 +143,7 @@ class CrossAttention(nn.Module):
         b, n, _ = x.shape
         vt = torch.mm(self.to_v.weight, x.reshape(b * n, c).t()).view(c, b, n).permute(1, 0, 2)    # [B, C, N] view of [C, B*N]
         o = _ops.self_attention(qk[..., :c], qk[..., c:], vt, self.heads, _ops.LN2, sfrag=pre_to_out_sfrag)
-        return o if pre_to_out_sfrag else self.to_out(o)
+        return o if pre_to_out_sfrag or pre_to_out else self.to_out(o)
 
 
     def _wqk_cat(self):
@@ -335,6 +336,7 @@ class BasicTransformerBlock(nn.Module):
             # norm2's output has ONE consumer when to_q runs inside the attention kernel: the pass then writes it in the MFMA
             # operand order that kernel loads (query-fragment order, 1-KiB coalesced loads) instead of row-major
             qfrag = fused_q and cache.qfrag
+            to_out_c640 = big and _fused.TO_OUT_LN_C640 and x.shape[-1] == 640
             if sfrag:
                 # level 0: the self-attention kernel leaves its output in out-fragment order and attn1.to_out + the residual + norm2
                 # are ONE pass over it (csrc/sta_rowgemm.hip) — to_out's result never reaches HBM, y leaves in the order its consumer wants
@@ -344,6 +346,10 @@ class BasicTransformerBlock(nn.Module):
                 else:
                     o = a1._self_attention_hip(y, pre_to_out_sfrag=True)
                 x, y = _fused.to_out_add_layernorm_ofrag(x, o, self._wo1_fragments(), a1.to_out[0].bias, n2.weight, n2.bias, n2.eps, a1.heads, y_qfrag=qfrag)
+            elif to_out_c640 and isinstance(a1.to_q, nn.Linear) and not isinstance(a1.to_q, MxFp8Linear) and _fused.rows_c640_supported(x, a1.to_out[0]) \
+                    and _ops.self_attention_supported(y, a1.heads):
+                # level 1: attn1.to_out + the residual + norm2 as ONE pass over the kernel's row-major output (csrc/sta_rows640.hip)
+                x, y = _fused.linear_res_c640(x, a1._self_attention_hip(y, pre_to_out=True), a1.to_out[0], n2, y_qfrag=qfrag)
             else:
                 x, y = _fused.add_layernorm(x, a1(y), None, n2.weight, n2.bias, n2.eps, qfrag=qfrag)
             if fused_q:
@@ -363,7 +369,11 @@ class BasicTransformerBlock(nn.Module):
                 if cap is not None:
                     cap.record(self, q, cache)
                 blended = _ops.xattn_blend(q, c, cache.packed, cache.mask, self.attn2.scale)
-            x, y = _fused.add_layernorm(x, self.attn2.to_out(blended), None, n3.weight, n3.bias, n3.eps, qfrag=ffq)
+            if to_out_c640 and blended.is_contiguous() and _fused.rows_c640_supported(x, self.attn2.to_out[0]):
+                # level 1: attn2.to_out + the residual + norm3 as ONE pass (to_out[1] is Dropout(0))
+                x, y = _fused.linear_res_c640(x, blended, self.attn2.to_out[0], n3, y_qfrag=ffq)
+            else:
+                x, y = _fused.add_layernorm(x, self.attn2.to_out(blended), None, n3.weight, n3.bias, n3.eps, qfrag=ffq)
             return self._ff_tail(x, y, ffq)
         al = self._attn_loss                         # an AttnLayoutLoss records only while autograd is enabled: the two branches below
         if al is not None and not al.wants(x.shape[1]):
@@ -419,6 +429,9 @@ class BasicTransformerBlock(nn.Module):
         if self._ff_c640(x):
             w1 = _fused.cached_image(self, "w1", (proj.weight,), lambda: _fused.pack_geglu_c640_weight(proj.weight))
             h = _fused.ff_geglu_c640_qfrag(y, w1, proj.bias, proj.out_features // 2)
+            if _fused.FF_OUT_RES_C640 and _fused.rows_c640_supported(x, self.ff.net[2]):
+                # ... and the output Linear + the block's last residual as one pass over row-major h (net[1] is Dropout(0))
+                return _fused.linear_res_c640(x, h, self.ff.net[2])[0]
             return self.ff.net[2](self.ff.net[1](h)) + x
         w1 = _fused.cached_image(self, "w1", (proj.weight,), lambda: _fused.pack_geglu_weight(proj.weight))
         out = self.ff.net[2]

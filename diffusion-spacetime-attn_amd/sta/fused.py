@@ -300,6 +300,50 @@ def ff_out_res_hfrag(x, h_frag, w_packed, bias):
     return out
 
 
+TO_OUT_LN_C640 = True   # level 1 (C = 640): attn1 / attn2 .to_out + the residual + the next LayerNorm as one pass (csrc/sta_rows640.hip); False: library GEMM + sta_add_layernorm
+FF_OUT_RES_C640 = True  # level 1: ff.net[2] + the block's last residual as one pass (the same kernel at K = 2560); False: library GEMM + an elementwise add
+
+
+def rows_c640_supported(x, lin):
+    """`lin` is a plain nn.Linear [640 <- 640 | 2560] of x's dtype on x's device, x [.., 640] has a multiple of 16 rows, and the
+    [rows, in_features] input stays below what a launch addresses."""
+    C = x.shape[-1]
+    return (type(lin) is torch.nn.Linear and lin.weight.dtype == x.dtype and lin.weight.is_cuda and lin.out_features == C
+            and (x.numel() // C) % 16 == 0 and rows_addressable(x, lin.in_features)
+            and bool(lib.load().sta_rows_c640_packed_w_bytes(C, lin.in_features)))
+
+
+def pack_rows_c640_weight(weight):
+    """A Linear weight [640, K] (K = 640 | 2560) -> the fragment image sta_rows_c640 streams through LDS (uint8 tensor); once per model."""
+    C, K = weight.shape
+    return _pack_ff_weight(weight, C, K, "sta_rows_c640_packed_w_bytes", "sta_rows_c640_pack_w", "Linear + residual at C = 640: a CUDA weight [640, 640] or [640, 2560]")
+
+
+def rows_c640(x, a, w_packed, bias, ln_weight=None, ln_bias=None, eps=1e-5, y_qfrag=False, max_workgroups=0):
+    """s = x + a W^T + bias over row-major a [.., K] and x [.., 640]; with `ln_weight` (K = 640) also y = LayerNorm(s), row-major or
+    (`y_qfrag`) in query-fragment order. Returns (s, y); y is None without the LayerNorm (K = 2560). The Linear's result never exists
+    in HBM (csrc/sta_rows640.hip). `max_workgroups` > 0 caps the grid (tests)."""
+    C, K = x.shape[-1], a.shape[-1]
+    R = x.numel() // C
+    if a.numel() // K != R or a.dtype != x.dtype:
+        raise ValueError("rows_c640: a %s and x %s must have the same rows and dtype" % (tuple(a.shape), tuple(x.shape)))
+    x, a = x.contiguous(), a.contiguous()
+    s = torch.empty_like(x)
+    y = torch.empty_like(x) if ln_weight is not None else None
+    lib.check(lib.load().sta_rows_c640(a.data_ptr(), w_packed.data_ptr(), _ptr(bias), x.data_ptr(), _ptr(ln_weight), _ptr(ln_bias), s.data_ptr(), _ptr(y),
+                                       R, C, K, float(eps), int(bool(y_qfrag)), int(max_workgroups), _DT[x.dtype], _stream()), "sta_rows_c640")
+    return s, y
+
+
+def linear_res_c640(x, a, lin, norm=None, y_qfrag=False):
+    """x + lin(a) (and norm of it) for a Linear rows_c640_supported accepted; the packed weight is cached on `lin`."""
+    w = lin.weight
+    wp = cached_image(lin, "rows_c640", (w,), lambda: pack_rows_c640_weight(w))
+    if norm is None:
+        return rows_c640(x, a, wp, lin.bias)
+    return rows_c640(x, a, wp, lin.bias, norm.weight, norm.bias, norm.eps, y_qfrag=y_qfrag)
+
+
 LN_QKV = True           # level 0: norm1 + the q|k and V^T projections of attn1 as one pass (csrc/sta_lnqkv.hip); False: sta_add_layernorm + two library GEMMs
 
 

@@ -25,8 +25,10 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # sta_window.hip (sta_window_split / sta_window_fuse / sta_sampler_step_windows and their inpainting forms sta_sampler_step_windows_masked /
 # sta_window_blend: canvases sampled as overlapping windows) runs the sampler step on overlap means and is built with it for the same
 # reason: no fast-math flag (its mean is a correctly rounded fp32 division). The step itself and the helpers of all three are defined
-# once, in csrc/sta_step_dev.h, which sta_inpaint.hip includes as well.
-INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_window.hip": "sta_sampler.hip"}
+# once, in csrc/sta_step_dev.h, which sta_inpaint.hip includes as well. sta_rows640.hip (sta_rows_c640: the level-1 Linear + residual
+# (+ LayerNorm) pass) is the C = 640 sibling of sta_rowgemm.hip's kernel and shares its headers and -ffinite-math-only.
+INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_window.hip": "sta_sampler.hip",
+                    "sta_rows640.hip": "sta_rowgemm.hip"}
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -45,7 +47,8 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 # (sta_conv.hip: the sub-pixel instantiations conv3x3_nhwc_kernel<T, GEO, NTW, true> — "Lb1E" is the mangled `true`)
 # (sta_sampler.hip: the window kernels index offset tables that arrive by value in the kernel arguments; a toolchain that copies the
 # tables to scratch to index them is refused)
-NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",),
+# (sta_rows640.hip: an included source is named by its own file; its kernels are looked for in the assembly of the unit that includes it)
+NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",), "sta_rows640.hip": ("rows640_kernel",),
                     "sta_sampler.hip": ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel",
                                         "sampler_step_windows_masked_kernel", "window_blend_kernel")}
 
@@ -84,6 +87,9 @@ SYMBOLS = {
     "sta_to_out_ln_packed_wo_bytes": (_sz, [_i, _i]),
     "sta_to_out_ln_pack_wo": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "sta_to_out_ln_ofrag": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _f, _i, _i, _vp]),
+    "sta_rows_c640_packed_w_bytes": (_sz, [_i, _i]),
+    "sta_rows_c640_pack_w": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "sta_rows_c640": (_i, [_vp] * 8 + [_l, _i, _i, _f, _i, _i, _i, _vp]),
     "sta_selfattn_fwd_sfrag": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _l, _l, _f, _i, _vp]),
     "sta_xattn_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "sta_xattn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
@@ -251,6 +257,9 @@ def _compile_checked(hipcc, base, flags, src, obj, workdir, verbose):
     with open(stem + ".s") as fh:
         text = fh.read()
     check_no_spill(src, text)
+    for inc, host in INCLUDED_SOURCES.items():
+        if host == os.path.basename(src):
+            check_no_spill(inc, text)
     fixed, log = isa_lint.fix_text(text)
     left = isa_lint.lint_text(fixed)
     if left:

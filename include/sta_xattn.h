@@ -237,6 +237,24 @@ int sta_selfattn_fwd_sfrag(const void* q, const void* k, const void* vt, void* o
                            int ldq, int ldk, long vt_row_stride, long vt_batch_stride, float scale, int dtype, void* stream);
 
 /*
+ * SD-v1 level 1 (C = 640): an output Linear of the block with the residual add — and, behind the two attentions, the LayerNorm
+ * that follows — in one pass over ROW-MAJOR activations (csrc/sta_rows640.hip):
+ *     K = 640:   s = x + a . W^T + bias ;  y = LayerNorm(s) * gamma + beta     attn1.to_out + norm2, attn2.to_out + norm3
+ *     K = 2560:  s = x + a . W^T + bias                                        ff.net[2] + the block's last residual
+ * The Linear's [R][640] result never exists in HBM (row-major: a library GEMM that writes it + a pass that reads it back). W [640][K]
+ * is re-laid out once per model by the pack entry point (the bytes entry point: 640 * K * 2; 0 = unsupported: C = 640 with K = 640 or
+ * 2560 only) and streamed through LDS. The statistics are taken of s as stored (rounded to dtype), in the two-pass order of
+ * sta_add_layernorm.
+ *   a: [R][K];  bias: [640] or NULL;  x, s, y: [R][640];  R % 16 == 0, R * K * 2 bytes < 4 GiB
+ *   K = 640: gamma, beta, y required; y_qfrag = 1 writes y in QUERY-fragment order (sta_add_layernorm_qfrag's). K = 2560: all three NULL.
+ *   max_workgroups: 0 = one persistent workgroup per CU; n > 0 caps the grid (tests: several 128-row passes per workgroup)
+ */
+size_t sta_rows_c640_packed_w_bytes(int C, int K);
+int sta_rows_c640_pack_w(const void* w, void* packed, int C, int K, int dtype, void* stream);
+int sta_rows_c640(const void* a, const void* packed_w, const void* bias, const void* x, const void* gamma, const void* beta,
+                  void* s, void* y, long R, int C, int K, float eps, int y_qfrag, int max_workgroups, int dtype, void* stream);
+
+/*
  * Token maps: WHERE the pixels attend, reduced to what a diagnostic needs. `attn` (attention.py:194) is a local of the
  * reference's forward; the `maps` output of sta_xattn_fwd writes it out in full ([K+2][heads][N][M] fp32 per image). This
  * entry point keeps R weighted key sums per pixel instead — readout r names a context c_r = sel_ctx[r] and a weight row:
