@@ -18,6 +18,18 @@ struct StepCoef {
   float c_x, c_m, c_p, c_e, c_n;
 };
 
+// v held in a vector register from here on (an empty asm that only constrains where v lives), and a StepCoef held so: for a kernel
+// whose grid tables and streams fill the scalar file to the last register (the wrapped masked step of sta_window.hip)
+__device__ __forceinline__ float in_vgpr(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+__device__ __forceinline__ StepCoef coef_in_vgprs(const StepCoef& c) {
+  return StepCoef{in_vgpr(c.scale), in_vgpr(c.sigma_t), in_vgpr(c.alpha_t), in_vgpr(c.c_x), in_vgpr(c.c_m), in_vgpr(c.c_p), in_vgpr(c.c_e),
+                  in_vgpr(c.c_n)};
+}
+
 __device__ __forceinline__ void load8(const float* p, float* v) {
   const F4 a = *(const F4*)p, b = *(const F4*)(p + 4);
 #pragma unroll

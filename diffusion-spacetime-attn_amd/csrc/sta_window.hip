@@ -1,6 +1,7 @@
 // sta_window.hip — wide canvases sampled as overlapping square windows (gfx950). C-ABI in include/sta_unet.h (sta_window_split /
-// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend). #included at the end of sta_sampler.hip (its
-// flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division). The step on the overlap means
+// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend, and their `_ring` siblings for canvases
+// that close on themselves: WRAP, a compile-time mask of the cyclic axes, 0 in the five clamped entry points). #included at the end of
+// sta_sampler.hip (its flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division). The step on the overlap means
 // is step1 of sta_step_dev.h, the definition the square kernels use, with that header's V8T / F4 / load8 / store8 / round8 / StepCoef.
 // Conventions of sta_sampler.hip: 256-lane groups, grid-stride, a lane owns 8 consecutive elements of one CANVAS row, 16-byte loads and
 // stores, fp32 arithmetic. Window sides, offsets and canvas sides are multiples of 8, so a lane's vector lies inside or outside a window
@@ -42,17 +43,29 @@ __device__ __forceinline__ long window_at(long img, int C, int c, int s, int dy,
   return ((img * C + c) * s + dy) * (long)s + dx;
 }
 
-// sum over the covering windows of pair row r (ascending w, fp32, starting from the first one's value) -> count
-template <typename T>
-__device__ __forceinline__ int gather_sum(const T* __restrict__ eps, const WinGrid& g, long p, int r, int C, const CanvasPos& q, float* acc) {
+// position of canvas coordinate `at` inside the window at offset o of an axis of length L: on a cyclic axis (WRAPPED) the window covers
+// (o + d) mod L for d = 0 .. s - 1, so a negative distance is taken once round the ring (d < 0 ? d + L : d, on the sign bits: no lane
+// mask); the window covers `at` iff (unsigned)d < s
+template <bool WRAPPED>
+__device__ __forceinline__ int window_dist(int at, int o, int L) {
+  int d = at - o;
+  if constexpr (WRAPPED) d += (d >> 31) & L;
+  return d;
+}
+
+// sum over the covering windows of pair row r (ascending w, fp32, starting from the first one's value) -> count.
+// WRAP: the cyclic axes, bit 0 = x (length Wc), bit 1 = y (length Hc); 0 = the clamped grid
+template <typename T, int WRAP>
+__device__ __forceinline__ int gather_sum(const T* __restrict__ eps, const WinGrid& g, long p, int r, int C, int Hc, int Wc, const CanvasPos& q,
+                                          float* acc) {
   using V8 = typename V8T<T>::type;
   const long T_ = (long)g.ny * g.nx;
   int n = 0;
   for (int j = 0; j < g.ny; ++j) {
-    const int dy = q.y - g.oy[j];
+    const int dy = window_dist<(WRAP & 2) != 0>(q.y, g.oy[j], Hc);
     if ((unsigned)dy >= (unsigned)g.s) continue;
     for (int i = 0; i < g.nx; ++i) {
-      const int dx = q.x - g.ox[i];
+      const int dx = window_dist<(WRAP & 1) != 0>(q.x, g.ox[i], Wc);
       if ((unsigned)dx >= (unsigned)g.s) continue;
       const V8 e = *(const V8*)(eps + window_at(2 * (p * T_ + j * g.nx + i) + r, C, q.c, g.s, dy, dx));
 #pragma unroll
@@ -64,16 +77,16 @@ __device__ __forceinline__ int gather_sum(const T* __restrict__ eps, const WinGr
 }
 
 // o -> rows r0 .. r1 of the pair of every covering window
-template <typename T>
-__device__ __forceinline__ void scatter(T* __restrict__ xin, const WinGrid& g, long p, int r0, int r1, int C, const CanvasPos& q,
+template <typename T, int WRAP>
+__device__ __forceinline__ void scatter(T* __restrict__ xin, const WinGrid& g, long p, int r0, int r1, int C, int Hc, int Wc, const CanvasPos& q,
                                         const typename V8T<T>::type o) {
   using V8 = typename V8T<T>::type;
   const long T_ = (long)g.ny * g.nx;
   for (int j = 0; j < g.ny; ++j) {
-    const int dy = q.y - g.oy[j];
+    const int dy = window_dist<(WRAP & 2) != 0>(q.y, g.oy[j], Hc);
     if ((unsigned)dy >= (unsigned)g.s) continue;
     for (int i = 0; i < g.nx; ++i) {
-      const int dx = q.x - g.ox[i];
+      const int dx = window_dist<(WRAP & 1) != 0>(q.x, g.ox[i], Wc);
       if ((unsigned)dx >= (unsigned)g.s) continue;
       for (int r = r0; r <= r1; ++r) *(V8*)(xin + window_at(2 * (p * T_ + j * g.nx + i) + r, C, q.c, g.s, dy, dx)) = o;
     }
@@ -81,7 +94,7 @@ __device__ __forceinline__ void scatter(T* __restrict__ xin, const WinGrid& g, l
 }
 
 // src [P rows][C][Hc][Wc] (S = float or T) -> xin [2 P T][C][s][s]; rows == 1: the canvas state goes to both rows of every pair
-template <typename S, typename T>
+template <typename S, typename T, int WRAP>
 __global__ __launch_bounds__(256) void window_split_kernel(const S* __restrict__ src, T* __restrict__ xin, long nvec, int rows, int C, int Hc,
                                                            int Wc, WinGrid g) {
   using V8 = typename V8T<T>::type;
@@ -98,12 +111,12 @@ __global__ __launch_bounds__(256) void window_split_kernel(const S* __restrict__
       o = ((const V8*)src)[v];
     }
     const int r = rows == 2 ? (int)(q.row & 1) : 0;
-    scatter<T>(xin, g, rows == 2 ? q.row >> 1 : q.row, r, rows == 2 ? r : 1, C, q, o);
+    scatter<T, WRAP>(xin, g, rows == 2 ? q.row >> 1 : q.row, r, rows == 2 ? r : 1, C, Hc, Wc, q, o);
   }
 }
 
 // eps [2 P T][C][s][s] -> out [2 P][C][Hc][Wc]: the mean over the covering windows, fp32 sum / count, rounded once
-template <typename T>
+template <typename T, int WRAP>
 __global__ __launch_bounds__(256) void window_fuse_kernel(const T* __restrict__ eps, T* __restrict__ out, long nvec, int C, int Hc, int Wc,
                                                           WinGrid g) {
   using V8 = typename V8T<T>::type;
@@ -111,7 +124,7 @@ __global__ __launch_bounds__(256) void window_fuse_kernel(const T* __restrict__ 
   for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
     const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
     float acc[8] = {};
-    const float cnt = (float)gather_sum<T>(eps, g, q.row >> 1, (int)(q.row & 1), C, q, acc);
+    const float cnt = (float)gather_sum<T, WRAP>(eps, g, q.row >> 1, (int)(q.row & 1), C, Hc, Wc, q, acc);
     V8 o;
 #pragma unroll
     for (int k = 0; k < 8; ++k) o[k] = (T)(acc[k] / cnt);
@@ -121,7 +134,7 @@ __global__ __launch_bounds__(256) void window_fuse_kernel(const T* __restrict__ 
 
 // sampler_step_kernel on the overlap means of the windows' UNet output (fp32, not rounded): the same step1;
 // xin (null = not written): the rounded x_next to both rows of every covering window, the next call's input
-template <typename T>
+template <typename T, int WRAP>
 __global__ __launch_bounds__(256) void sampler_step_windows_kernel(const T* __restrict__ eps, const float* __restrict__ x,
                                                                    const float* __restrict__ m_prev, const float* __restrict__ noise,
                                                                    float* __restrict__ x_next, float* __restrict__ m, T* __restrict__ xin,
@@ -131,8 +144,8 @@ __global__ __launch_bounds__(256) void sampler_step_windows_kernel(const T* __re
   for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
     const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
     float eu[8] = {}, ec[8] = {};
-    const float cnt = (float)gather_sum<T>(eps, g, q.row, 0, C, q, eu);
-    gather_sum<T>(eps, g, q.row, 1, C, q, ec);
+    const float cnt = (float)gather_sum<T, WRAP>(eps, g, q.row, 0, C, Hc, Wc, q, eu);
+    gather_sum<T, WRAP>(eps, g, q.row, 1, C, Hc, Wc, q, ec);
     float xv[8], mp[8], nz[8], xn[8], mv[8];
     load8(x + 8 * v, xv);
     if (m_prev) load8(m_prev + 8 * v, mp);
@@ -141,7 +154,7 @@ __global__ __launch_bounds__(256) void sampler_step_windows_kernel(const T* __re
     for (int k = 0; k < 8; ++k) xn[k] = step1(eu[k] / cnt, ec[k] / cnt, xv[k], mp + k, nz + k, m_prev, noise, c, mv[k]);
     store8(x_next + 8 * v, xn);
     store8(m + 8 * v, mv);
-    if (xin) scatter<T>(xin, g, q.row, 0, 1, C, q, round8<T>(xn));
+    if (xin) scatter<T, WRAP>(xin, g, q.row, 0, 1, C, Hc, Wc, q, round8<T>(xn));
   }
 }
 
@@ -152,7 +165,7 @@ __device__ __forceinline__ long mask_at(const CanvasPos& q, int Hc, int Wc) { re
 // (blend1 of sta_blend_dev.h, as sampler_step_masked_kernel): x0 / qnoise canvas-shaped, keep [P][Hc][Wc]; m is the unblended data
 // prediction; xin (null = not written): the rounded BLENDED x_next to both rows of every covering window. MP / NZ: m_prev / noise are
 // given — compile-time here, since the three extra streams leave no scalar registers for the run-time tests' masks
-template <typename T, bool MP, bool NZ>
+template <typename T, bool MP, bool NZ, int WRAP>
 __global__ __launch_bounds__(256) void sampler_step_windows_masked_kernel(const T* __restrict__ eps, const float* __restrict__ x,
                                                                           const float* __restrict__ m_prev, const float* __restrict__ noise,
                                                                           const float* __restrict__ x0, const float* __restrict__ keep,
@@ -160,12 +173,16 @@ __global__ __launch_bounds__(256) void sampler_step_windows_masked_kernel(const 
                                                                           float* __restrict__ m, T* __restrict__ xin, long nvec, int C, int Hc,
                                                                           int Wc, WinGrid g, StepCoef c, float q_a, float q_b) {
   using V8 = typename V8T<T>::type;
+  if constexpr (WRAP != 0) {      // the ring arithmetic costs this kernel its last scalar registers: the ten coefficients move to vector ones
+    c = coef_in_vgprs(c);
+    q_a = in_vgpr(q_a), q_b = in_vgpr(q_b);
+  }
   const long stride = (long)gridDim.x * 256;
   for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
     const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
     float eu[8] = {}, ec[8] = {};
-    const float cnt = (float)gather_sum<T>(eps, g, q.row, 0, C, q, eu);
-    gather_sum<T>(eps, g, q.row, 1, C, q, ec);
+    const float cnt = (float)gather_sum<T, WRAP>(eps, g, q.row, 0, C, Hc, Wc, q, eu);
+    gather_sum<T, WRAP>(eps, g, q.row, 1, C, Hc, Wc, q, ec);
     float xv[8], mp[8], nz[8], xn[8], mv[8], z0[8], kp[8], qn[8];
     load8(x + 8 * v, xv);
     if constexpr (MP) load8(m_prev + 8 * v, mp);
@@ -180,12 +197,12 @@ __global__ __launch_bounds__(256) void sampler_step_windows_masked_kernel(const 
     }
     store8(x_next + 8 * v, xn);
     store8(m + 8 * v, mv);
-    if (xin) scatter<T>(xin, g, q.row, 0, 1, C, q, round8<T>(xn));
+    if (xin) scatter<T, WRAP>(xin, g, q.row, 0, 1, C, Hc, Wc, q, round8<T>(xn));
   }
 }
 
 // the blend of the first call on a canvas, then the split: latent_blend_kernel and window_split_kernel (rows = 1) in one pass
-template <typename T>
+template <typename T, int WRAP>
 __global__ __launch_bounds__(256) void window_blend_kernel(const float* __restrict__ x, const float* __restrict__ x0,
                                                            const float* __restrict__ keep, const float* __restrict__ noise,
                                                            float* __restrict__ x_out, T* __restrict__ xin, long nvec, int C, int Hc, int Wc,
@@ -202,7 +219,7 @@ __global__ __launch_bounds__(256) void window_blend_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < 8; ++k) xo[k] = blend1(kp[k], z0[k], qn[k], xv[k], q_a, q_b);
     store8(x_out + 8 * v, xo);
-    if (xin) scatter<T>(xin, g, q.row, 0, 1, C, q, round8<T>(xo));
+    if (xin) scatter<T, WRAP>(xin, g, q.row, 0, 1, C, Hc, Wc, q, round8<T>(xo));
   }
 }
 
@@ -220,18 +237,150 @@ int window_axis_ok(const char* what, const char* axis, int n, const int* o, int 
   return STA_OK;
 }
 
-int window_grid_ok(const char* what, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, WinGrid* g) {
+// offsets along one CYCLIC axis of length L (s <= L is the caller's rule: a window covers an element at most once): 0 first, multiples
+// of 8, ascending, every one on the axis (o < L; a window may run over the seam), no gap (step <= s), the ring closes (L - last <= s)
+int window_ring_axis_ok(const char* what, const char* axis, int n, const int* o, int s, int L) {
+  if (n < 1 || n > STA_MAX_WINDOW_OFFSETS) return sta_fail(STA_E_ARG, "%s: n%s=%d (need 1 .. %d offsets)", what, axis, n, STA_MAX_WINDOW_OFFSETS);
+  for (int k = 0; k < n; ++k) {
+    const int prev = k ? o[k - 1] : 0;
+    if (o[k] % 8) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d is not a multiple of 8", what, axis, k, o[k]);
+    if (o[k] < 0 || o[k] >= L) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d is not on the wrapped axis (length %d)", what, axis, k, o[k], L);
+    if (k ? o[k] <= prev : o[k] != 0) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d unsorted (after %d; the first offset is 0)", what, axis, k, o[k], prev);
+    if (o[k] - prev > s) return sta_fail(STA_E_ARG, "%s: gap between o%s[%d]=%d and o%s[%d]=%d (s=%d)", what, axis, k - 1, prev, axis, k, o[k], s);
+  }
+  if (L - o[n - 1] > s)
+    return sta_fail(STA_E_ARG, "%s: the ring does not close behind o%s[%d]=%d (s=%d, wrapped length %d)", what, axis, n - 1, o[n - 1], s, L);
+  return STA_OK;
+}
+
+// wrap: the cyclic axes (bit 0 = x, bit 1 = y); the other axes keep window_axis_ok
+int window_grid_ok(const char* what, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, WinGrid* g) {
   if (!oy || !ox) return sta_fail(STA_E_ARG, "null pointer");
+  if (wrap < 0 || wrap > 3) return sta_fail(STA_E_ARG, "%s: wrap=%d (need 0 .. 3: bit 0 = x, bit 1 = y)", what, wrap);
   if (P <= 0 || C <= 0) return sta_fail(STA_E_ARG, "%s: P=%ld C=%d", what, P, C);
   if (s < 8 || Hc < s || Wc < s || s % 8 || Hc % 8 || Wc % 8)
     return sta_fail(STA_E_ARG, "%s: s=%d Hc=%d Wc=%d (need multiples of 8 and 8 <= s <= Hc, Wc)", what, s, Hc, Wc);
-  if (const int rc = window_axis_ok(what, "y", ny, oy, s, Hc)) return rc;
-  if (const int rc = window_axis_ok(what, "x", nx, ox, s, Wc)) return rc;
+  if (const int rc = (wrap & 2 ? window_ring_axis_ok : window_axis_ok)(what, "y", ny, oy, s, Hc)) return rc;
+  if (const int rc = (wrap & 1 ? window_ring_axis_ok : window_axis_ok)(what, "x", nx, ox, s, Wc)) return rc;
   *g = WinGrid{};
   g->ny = ny, g->nx = nx, g->s = s;
   for (int k = 0; k < ny; ++k) g->oy[k] = oy[k];
   for (int k = 0; k < nx; ++k) g->ox[k] = ox[k];
   return STA_OK;
+}
+
+// f(std::integral_constant<int, wrap>) for a wrap window_grid_ok has accepted (0 .. 3): the kernels take the cyclic axes at compile time
+template <typename F>
+int by_wrap(int wrap, F&& f) {
+  switch (wrap) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 0>{});
+  }
+}
+
+// The five launches; `what` names the entry point in the texts (the clamped entry points are wrap = 0 of these).
+int window_split(const char* what, const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy,
+                 const int* ox, int s, int wrap, int src_dtype, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!src || !xin) return sta_fail(STA_E_ARG, "null pointer");
+  WinGrid g;
+  if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
+  if (rows != 1 && rows != 2) return sta_fail(STA_E_ARG, "%s: rows=%d (1: canvas states, 2: input pairs)", what, rows);
+  if (!sta_aligned16(src) || !sta_aligned16(xin)) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  if (src_dtype != STA_SRC_F32 && src_dtype != dtype)
+    return sta_fail(STA_E_UNSUP, "%s: src_dtype %d (float32 = %d, or the output's dtype %d)", what, src_dtype, STA_SRC_F32, dtype);
+  const long nvec = P * rows * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return by_wrap(wrap, [&](auto w) {
+      constexpr int W = decltype(w)::value;
+      if (src_dtype == STA_SRC_F32)
+        return sta_launch<window_split_kernel<float, T, W>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
+                                                            (T*)xin, nvec, rows, C, Hc, Wc, g);
+      return sta_launch<window_split_kernel<T, T, W>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)src, (T*)xin,
+                                                      nvec, rows, C, Hc, Wc, g);
+    });
+  });
+}
+
+int window_fuse(const char* what, const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                int wrap, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!eps || !out) return sta_fail(STA_E_ARG, "null pointer");
+  WinGrid g;
+  if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
+  if (!sta_aligned16(eps) || !sta_aligned16(out)) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  const long nvec = 2 * P * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return by_wrap(wrap, [&](auto w) {
+      return sta_launch<window_fuse_kernel<T, decltype(w)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
+                                                                   (const T*)eps, (T*)out, nvec, C, Hc, Wc, g);
+    });
+  });
+}
+
+int step_windows(const char* what, const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin,
+                 long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, const StepCoef& c, int dtype,
+                 void* stream) {
+  g_sta_err[0] = 0;
+  WinGrid g;
+  if (const int rc = sta_step_args_ok(what, eps, x, m_prev, noise, x_next, m, xin, false, nullptr, nullptr, nullptr, c.alpha_t,
+                                      [&] { return window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g); }))
+    return rc;
+  const long nvec = P * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return by_wrap(wrap, [&](auto w) {
+      return sta_launch<sampler_step_windows_kernel<T, decltype(w)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
+                                                                            (const T*)eps, x, m_prev, noise, x_next, m, (T*)xin, nvec, C, Hc,
+                                                                            Wc, g, c);
+    });
+  });
+}
+
+int step_windows_masked(const char* what, const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
+                        const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc, int ny, int nx,
+                        const int* oy, const int* ox, int s, int wrap, const StepCoef& c, float q_a, float q_b, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  WinGrid g;
+  if (const int rc = sta_step_args_ok(what, eps, x, m_prev, noise, x_next, m, xin, true, x0, keep, qnoise, c.alpha_t,
+                                      [&] { return window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g); }))
+    return rc;
+  const long nvec = P * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return by_wrap(wrap, [&](auto w) {
+      auto launch = [&](auto mp, auto nz) {
+        return sta_launch<sampler_step_windows_masked_kernel<T, decltype(mp)::value, decltype(nz)::value, decltype(w)::value>>(
+            what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)eps, x, m_prev, noise, x0, keep, qnoise, x_next, m,
+            (T*)xin, nvec, C, Hc, Wc, g, c, q_a, q_b);
+      };
+      using Yes = std::true_type;
+      using No = std::false_type;
+      return m_prev ? (noise ? launch(Yes{}, Yes{}) : launch(Yes{}, No{})) : (noise ? launch(No{}, Yes{}) : launch(No{}, No{}));
+    });
+  });
+}
+
+int window_blend(const char* what, const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C,
+                 int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!x || !x0 || !keep || !noise || !x_out) return sta_fail(STA_E_ARG, "%s: null pointer", what);
+  WinGrid g;
+  if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
+  if (!sta_aligned16(x) || !sta_aligned16(x0) || !sta_aligned16(keep) || !sta_aligned16(noise) || !sta_aligned16(x_out) || !sta_aligned16(xin))
+    return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  const long nvec = P * C * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return by_wrap(wrap, [&](auto w) {
+      return sta_launch<window_blend_kernel<T, decltype(w)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, x, x0,
+                                                                    keep, noise, x_out, (T*)xin, nvec, C, Hc, Wc, g, q_a, q_b);
+    });
+  });
 }
 
 }  // namespace
@@ -240,95 +389,63 @@ extern "C" {
 
 int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
                      int src_dtype, int dtype, void* stream) {
-  g_sta_err[0] = 0;
-  if (!src || !xin) return sta_fail(STA_E_ARG, "null pointer");
-  WinGrid g;
-  if (const int rc = window_grid_ok("window_split", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
-  if (rows != 1 && rows != 2) return sta_fail(STA_E_ARG, "window_split: rows=%d (1: canvas states, 2: input pairs)", rows);
-  if (!sta_aligned16(src) || !sta_aligned16(xin)) return sta_fail(STA_E_ARG, "window_split: every tensor must be 16-byte aligned");
-  if (src_dtype != STA_SRC_F32 && src_dtype != dtype)
-    return sta_fail(STA_E_UNSUP, "window_split: src_dtype %d (float32 = %d, or the output's dtype %d)", src_dtype, STA_SRC_F32, dtype);
-  const long nvec = P * rows * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    if (src_dtype == STA_SRC_F32)
-      return sta_launch<window_split_kernel<float, T>>("window_split", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
-                                                       (const float*)src, (T*)xin, nvec, rows, C, Hc, Wc, g);
-    return sta_launch<window_split_kernel<T, T>>("window_split", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)src,
-                                                 (T*)xin, nvec, rows, C, Hc, Wc, g);
-  });
+  return window_split("window_split", src, xin, P, rows, C, Hc, Wc, ny, nx, oy, ox, s, 0, src_dtype, dtype, stream);
+}
+
+int sta_window_split_ring(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox,
+                          int s, int wrap, int src_dtype, int dtype, void* stream) {
+  return window_split("window_split_ring", src, xin, P, rows, C, Hc, Wc, ny, nx, oy, ox, s, wrap, src_dtype, dtype, stream);
 }
 
 int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int dtype,
                     void* stream) {
-  g_sta_err[0] = 0;
-  if (!eps || !out) return sta_fail(STA_E_ARG, "null pointer");
-  WinGrid g;
-  if (const int rc = window_grid_ok("window_fuse", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
-  if (!sta_aligned16(eps) || !sta_aligned16(out)) return sta_fail(STA_E_ARG, "window_fuse: every tensor must be 16-byte aligned");
-  const long nvec = 2 * P * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    return sta_launch<window_fuse_kernel<T>>("window_fuse", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)eps, (T*)out,
-                                             nvec, C, Hc, Wc, g);
-  });
+  return window_fuse("window_fuse", eps, out, P, C, Hc, Wc, ny, nx, oy, ox, s, 0, dtype, stream);
+}
+
+int sta_window_fuse_ring(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                         int dtype, void* stream) {
+  return window_fuse("window_fuse_ring", eps, out, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, dtype, stream);
 }
 
 int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin, long P,
                              int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t,
                              float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream) {
-  g_sta_err[0] = 0;
-  WinGrid g;
-  if (const int rc = sta_step_args_ok("sampler_step_windows", eps, x, m_prev, noise, x_next, m, xin, false, nullptr, nullptr, nullptr, alpha_t,
-                                      [&] { return window_grid_ok("sampler_step_windows", P, C, Hc, Wc, ny, nx, oy, ox, s, &g); }))
-    return rc;
-  const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
-  const long nvec = P * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    return sta_launch<sampler_step_windows_kernel<T>>("sampler_step_windows", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
-                                                      (const T*)eps, x, m_prev, noise, x_next, m, (T*)xin, nvec, C, Hc, Wc, g, c);
-  });
+  return step_windows("sampler_step_windows", eps, x, m_prev, noise, x_next, m, xin, P, C, Hc, Wc, ny, nx, oy, ox, s, 0,
+                      StepCoef{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n}, dtype, stream);
+}
+
+int sta_sampler_step_windows_ring(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin,
+                                  long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale,
+                                  float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream) {
+  return step_windows("sampler_step_windows_ring", eps, x, m_prev, noise, x_next, m, xin, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap,
+                      StepCoef{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n}, dtype, stream);
 }
 
 int sta_sampler_step_windows_masked(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
                                     const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc,
                                     int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t, float alpha_t, float c_x,
                                     float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream) {
-  g_sta_err[0] = 0;
-  WinGrid g;
-  if (const int rc = sta_step_args_ok("sampler_step_windows_masked", eps, x, m_prev, noise, x_next, m, xin, true, x0, keep, qnoise, alpha_t,
-                                      [&] { return window_grid_ok("sampler_step_windows_masked", P, C, Hc, Wc, ny, nx, oy, ox, s, &g); }))
-    return rc;
-  const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
-  const long nvec = P * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    auto launch = [&](auto mp, auto nz) {
-      return sta_launch<sampler_step_windows_masked_kernel<T, decltype(mp)::value, decltype(nz)::value>>(
-          "sampler_step_windows_masked", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)eps, x, m_prev, noise, x0, keep,
-          qnoise, x_next, m, (T*)xin, nvec, C, Hc, Wc, g, c, q_a, q_b);
-    };
-    using Yes = std::true_type;
-    using No = std::false_type;
-    return m_prev ? (noise ? launch(Yes{}, Yes{}) : launch(Yes{}, No{})) : (noise ? launch(No{}, Yes{}) : launch(No{}, No{}));
-  });
+  return step_windows_masked("sampler_step_windows_masked", eps, x, m_prev, noise, x0, keep, qnoise, x_next, m, xin, P, C, Hc, Wc, ny, nx, oy, ox,
+                             s, 0, StepCoef{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n}, q_a, q_b, dtype, stream);
+}
+
+int sta_sampler_step_windows_masked_ring(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
+                                         const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc,
+                                         int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t,
+                                         float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype,
+                                         void* stream) {
+  return step_windows_masked("sampler_step_windows_masked_ring", eps, x, m_prev, noise, x0, keep, qnoise, x_next, m, xin, P, C, Hc, Wc, ny, nx,
+                             oy, ox, s, wrap, StepCoef{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n}, q_a, q_b, dtype, stream);
 }
 
 int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
                      int Wc, int ny, int nx, const int* oy, const int* ox, int s, float q_a, float q_b, int dtype, void* stream) {
-  g_sta_err[0] = 0;
-  if (!x || !x0 || !keep || !noise || !x_out) return sta_fail(STA_E_ARG, "window_blend: null pointer");
-  WinGrid g;
-  if (const int rc = window_grid_ok("window_blend", P, C, Hc, Wc, ny, nx, oy, ox, s, &g)) return rc;
-  if (!sta_aligned16(x) || !sta_aligned16(x0) || !sta_aligned16(keep) || !sta_aligned16(noise) || !sta_aligned16(x_out) || !sta_aligned16(xin))
-    return sta_fail(STA_E_ARG, "window_blend: every tensor must be 16-byte aligned");
-  const long nvec = P * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    return sta_launch<window_blend_kernel<T>>("window_blend", dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, x, x0, keep, noise,
-                                              x_out, (T*)xin, nvec, C, Hc, Wc, g, q_a, q_b);
-  });
+  return window_blend("window_blend", x, x0, keep, noise, x_out, xin, P, C, Hc, Wc, ny, nx, oy, ox, s, 0, q_a, q_b, dtype, stream);
+}
+
+int sta_window_blend_ring(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
+                          int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream) {
+  return window_blend("window_blend_ring", x, x0, keep, noise, x_out, xin, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, q_a, q_b, dtype, stream);
 }
 
 }  // extern "C"

@@ -319,10 +319,11 @@ class PLMSSampler(object):
 
     _canvas = None               # the sta.canvas.Grid while sample_canvas / inpaint_canvas runs (set like _start / _inpaint, cleared in `finally`)
     canvas_fused_step = True     # step-kernel samplers on a canvas: one sta_sampler_step_windows launch per call (False: fuse + step + split)
+    canvas_wrap_margin = 8       # wrapped canvases: latent cells of circular padding per side around the ONE decode (0: none; <= the axis)
 
     def sample_canvas(self, S, canvas, window, stride=None, conditionings=None, unconditional_conditionings=None, bboxs=None,
                       object_names=None, local_conditionings=None, x_T=None, unconditional_guidance_scale=7.5, eta=0.0, seed=1,
-                      prompt_indices=None, curr_texts=None, mask=None, x0=None, channels=4, verbose=False):
+                      prompt_indices=None, curr_texts=None, mask=None, x0=None, channels=4, verbose=False, wrap=""):
         """P wide or tall canvases (same number of objects), each sampled as T overlapping square windows (sta.canvas): every UNet call
         sees the 2 P T window rows as one CFG batch — an ordinary batch of P T images for the blocks, graph replay included —, the T
         predictions are averaged where windows overlap and the sampler step runs on the canvas.
@@ -331,6 +332,9 @@ class PLMSSampler(object):
         re-expressed in its own coordinates: a disc has radius 0.2 s latent pixels everywhere); the prompt, the unconditional context,
         the local contexts and the blend weights W[p] belong to the canvas and are repeated per window. x_T: [P, channels, Hc, Wc].
         `last_result`: x0 [P, channels, Hc, Wc], image [P, 3, 8 Hc, 8 Wc] from ONE decode of the whole canvas, W [P, K, S].
+        wrap = "x" | "y" | "xy": the canvas closes on itself along those axes (360 degree panorama: "x"; tileable image: "xy"): the
+        windows run over the seam (sta.canvas.window_grid's ring rules) and the decode sees `canvas_wrap_margin` latent cells of the
+        other side on each wrapped border (`_decode_canvas`).
         Fixed weights only. ValueError before any UNet call for opt_epochs > 1 (the loss front end takes square images:
         sta.clip.check_view_shapes), an attached attn_capture, attn_loss or latent_guidance, mask= / x0= (inpainting) and a non-zero
         `_start` (img2img decodes): none of them is defined on a canvas by this method (inpainting: `inpaint_canvas` of the step-kernel
@@ -339,7 +343,7 @@ class PLMSSampler(object):
             raise ValueError("sample_canvas: mask= / x0= (inpainting) is not defined on a canvas (see inpaint_canvas)")
         return self._sample_canvas("sample_canvas", S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
                                    local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices, curr_texts, channels,
-                                   verbose)
+                                   verbose, wrap=wrap)
 
     def inpaint_canvas(self, S, canvas, window, stride=None, *, mask=None, x0=None, image=None, mask_px=None, **kwargs):
         """Inpainting / outpainting on a canvas: the step-kernel samplers only (SolverSamplerBase.inpaint_canvas), as `sample(mask=)`."""
@@ -348,7 +352,7 @@ class PLMSSampler(object):
 
     def _sample_canvas(self, what, S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
                        local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices, curr_texts, channels, verbose,
-                       prepare=None):
+                       prepare=None, wrap=""):
         """The body of sample_canvas and inpaint_canvas: every refusal, then the epoch loop on the canvas with `_canvas` set.
         prepare(P, channels, grid): the caller's own checks and state once the canvas is known (inpaint_canvas: the inpaint state)."""
         from sta import canvas as _cv
@@ -361,7 +365,12 @@ class PLMSSampler(object):
         if getattr(self, "_start", 0):
             raise ValueError("%s: a trajectory that starts at call %d (img2img) is not defined on a canvas" % (what, self._start))
         Hc, Wc = canvas
-        grid = _cv.window_grid(Hc, Wc, window, window // 2 if stride is None else stride)
+        grid = _cv.window_grid(Hc, Wc, window, window // 2 if stride is None else stride, wrap)
+        margin = int(self.canvas_wrap_margin)
+        for axis, L in (("x", grid.Wc), ("y", grid.Hc)):
+            if axis in grid.wrap and not 0 <= margin <= L:
+                raise ValueError("%s: canvas_wrap_margin = %d latent cells does not fit the wrapped %s axis of %d (need 0 .. %d)"
+                                 % (what, margin, axis, L, L))
         P = len(conditionings)
         if not (len(bboxs) == len(object_names) == len(local_conditionings) == P):
             raise ValueError("%s takes per-canvas lists of equal length (%d conditionings, %d bboxs, %d object_names, %d "
@@ -386,6 +395,17 @@ class PLMSSampler(object):
         finally:
             self._canvas = None
         return None
+
+    def _decode_canvas(self, img):
+        """The one decode of the final latent. On a wrapped canvas the decoder must see across the seam: the latent is padded circularly
+        by `canvas_wrap_margin` cells on both sides of every wrapped axis, decoded once and cropped by 8 margin pixels per side. (That
+        bounds the convolutional seam only: the VAE's mid-block attention is global.)"""
+        grid, m = self._canvas, int(self.canvas_wrap_margin)
+        if grid is None or not grid.wrap or m == 0:
+            return self.model.decode_first_stage(img)
+        mx, my = m if "x" in grid.wrap else 0, m if "y" in grid.wrap else 0
+        out = self.model.decode_first_stage(torch.nn.functional.pad(img, (mx, mx, my, my), mode="circular"))
+        return out[..., 8 * my:out.shape[-2] - 8 * my, 8 * mx:out.shape[-1] - 8 * mx].contiguous()
 
     def _window_unet(self, cond, uncond, scale, bboxs_curr, text_index, graph, img):
         """The canvas trajectory's UNet call -> (grid, unet(xin, t, coef)): xin the [2 P T] window input pairs, t [P] and coef [P, K] of
@@ -484,9 +504,9 @@ class PLMSSampler(object):
                     elif self.model.first_stage_model is not None and self._paste() is not None:
                         # inpainting with a pixel-space pair: the result (and what the loss sees) is the original outside the mask
                         from sta import solver as _solver
-                        x_img = _solver.image_composite(self.model.decode_first_stage(img), *self._paste())
+                        x_img = _solver.image_composite(self._decode_canvas(img), *self._paste())
                     elif self.model.first_stage_model is not None:
-                        x_img = torch.clamp((self.model.decode_first_stage(img) + 1.0) / 2.0, min=0.0, max=1.0)   # :249-250
+                        x_img = torch.clamp((self._decode_canvas(img) + 1.0) / 2.0, min=0.0, max=1.0)   # :249-250
                     if track:
                         lm = self.clip_loss_model
                         if not decode:
@@ -848,14 +868,15 @@ class SolverSamplerBase(PLMSSampler):
 
     def inpaint_canvas(self, S, canvas, window, stride=None, *, mask=None, x0=None, image=None, mask_px=None, conditionings=None,
                        unconditional_conditionings=None, bboxs=None, object_names=None, local_conditionings=None, x_T=None,
-                       unconditional_guidance_scale=7.5, eta=0.0, seed=1, prompt_indices=None, curr_texts=None, channels=4, verbose=False):
+                       unconditional_guidance_scale=7.5, eta=0.0, seed=1, prompt_indices=None, curr_texts=None, channels=4, verbose=False,
+                       wrap=""):
         """`sample_canvas` with the kept region (mask == 1) of every canvas re-noised from x0 before every UNet call: outpainting (x0 holds
         an existing picture's latent on its footprint, mask is 1 there) and the repaint of a region of a canvas sampled earlier.
         mask [P, 1, Hc, Wc] in [0, 1], 1 = keep; x0 [P, channels, Hc, Wc]; image [P, 3, 8 Hc, 8 Wc] in [0, 1] / mask_px [P, 1, 8 Hc, 8 Wc]:
         the original and its keep mask for the pixel-space paste over the ONE decode of the whole canvas (sta_image_composite); the other
-        keywords are sample_canvas's. On the GPU one sta_window_blend launch runs before call 0, one sta_sampler_step_windows_masked
-        launch after calls 0 .. S - 2 and the plain sta_sampler_step_windows after the last call. The blend draws are canvas-shaped, in
-        the order of `sample(mask=)`: blend draw of call i, eta draw of call i, blend draw of call i + 1, ...
+        keywords are sample_canvas's (wrap= included: the `_ring` launches, and the pixel-space paste on the cropped decode). On the GPU
+        one sta_window_blend launch runs before call 0, one sta_sampler_step_windows_masked launch after calls 0 .. S - 2 and the plain
+        sta_sampler_step_windows after the last call. The blend draws are canvas-shaped, in the order of `sample(mask=)`: blend draw of call i, eta draw of call i, blend draw of call i + 1, ...
         ValueError before any UNet call: what sample_canvas refuses, a missing mask or x0, shapes that are not the canvas's, mask values
         outside [0, 1], image without mask_px or the reverse."""
         if mask is None or x0 is None:
@@ -875,7 +896,7 @@ class SolverSamplerBase(PLMSSampler):
         try:
             return self._sample_canvas("inpaint_canvas", S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs,
                                        object_names, local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices,
-                                       curr_texts, channels, verbose, prepare=prepare)
+                                       curr_texts, channels, verbose, prepare=prepare, wrap=wrap)
         finally:
             self._inpaint = None
 

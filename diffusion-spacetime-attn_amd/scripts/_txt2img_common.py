@@ -9,7 +9,8 @@ ignores, accepted for compatibility). Added: --layout (JSON replacing the layout
 --attn_guidance ETA / --attn_guidance_steps / --attn_guidance_iters (attention-guided latent updates, sta.guidance; shared with
 img2img.py and inpaint.py through add_guidance_arguments / check_guidance_option / make_guidance / report_guidance),
 --canvas HxW / --canvas_stride PX (a wide or tall canvas sampled as overlapping --H x --W windows, sta.canvas; the layout's centres are
-then normalised to the canvas; fixed blend weights only).
+then normalised to the canvas; fixed blend weights only), --canvas_wrap x|y|xy (the canvas closes on itself along those axes: a 360 degree
+panorama or a tileable image).
 With torch.distributed.run the prompts are sharded round-robin over the ranks (one GPU each).
 """
 import argparse
@@ -97,6 +98,10 @@ def build_parser(default_dataset):
     p.add_argument("--canvas_stride", type=int, default=None, metavar="PX",
                    help="distance between neighbouring windows of --canvas in pixels: a multiple of 8 x --f, at most the window "
                         "(default: half the window)")
+    p.add_argument("--canvas_wrap", type=str, default=None, choices=("x", "y", "xy"),
+                   help="the --canvas closes on itself along these axes (x: a 360 degree panorama whose right edge continues into the left "
+                        "one; xy: a tileable image): the windows run over the seam. A wrapped axis must be a multiple of the stride and at "
+                        "least 1.5 windows long")
     add_guidance_arguments(p)
     return p
 
@@ -196,9 +201,12 @@ def report_guidance(sampler, indices, tag=""):
 
 def canvas_grid(opt):
     """The sta.canvas.Grid of --canvas / --canvas_stride in latent pixels, or None without --canvas; every refusal that needs no GPU."""
+    wrap = getattr(opt, "canvas_wrap", None) or ""
     if opt.canvas is None:
         if opt.canvas_stride is not None:
             raise SystemExit("--canvas_stride %d needs --canvas HxW" % opt.canvas_stride)
+        if wrap:
+            raise SystemExit("--canvas_wrap %s needs --canvas HxW" % wrap)
         return None
     parts = opt.canvas.lower().split("x")
     if len(parts) != 2 or not all(v.isdigit() for v in parts):
@@ -219,7 +227,7 @@ def canvas_grid(opt):
             raise SystemExit("%s reads one square image's attention maps and is not defined on a --canvas" % flag)
     from sta import canvas
     try:
-        return canvas.window_grid(Hpx // opt.f, Wpx // opt.f, opt.H // opt.f, stride // opt.f)
+        return canvas.window_grid(Hpx // opt.f, Wpx // opt.f, opt.H // opt.f, stride // opt.f, wrap)
     except ValueError as e:
         raise SystemExit("--canvas %s (latent pixels): %s" % (opt.canvas, e))
 
@@ -433,7 +441,7 @@ def run(kind, default_dataset):
                               bboxs=[[l[n] for n in l] for _, _, l in group], object_names=[list(l.keys()) for _, _, l in group],
                               local_conditionings=[c[2] for c in conds], curr_texts=[p for _, p, _ in group],
                               x_T=x1.expand(len(group), -1, -1, -1).contiguous(), unconditional_guidance_scale=opt.scale, eta=eta, seed=seed,
-                              prompt_indices=[i for i, _, _ in group], channels=opt.C)
+                              prompt_indices=[i for i, _, _ in group], channels=opt.C, wrap=grid.wrap)
 
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}) for i, p in mine]
     if grid is not None:

@@ -6,6 +6,8 @@ The flags of scripts/img2img.py (same parser, same seed discipline), plus
   --canvas HxW             the canvas in pixels, sampled as overlapping --H x --W windows (square; default 512), as in the txt2img scripts;
   --canvas_stride PX       distance between neighbouring windows (default: half a window);
   --place X,Y              where the picture's top-left corner lies on the canvas, in pixels (default 0,0);
+  --canvas_wrap x|y|xy     the canvas closes on itself along these axes (sta.canvas: a 360 degree panorama, a tileable image); a side
+                           of the picture on a wrapped border is then no border (--seam erodes it), and the picture may not cross the seam;
   --seam PX                the picture's footprint is eroded by this many pixels on every side that does not lie on the canvas border:
                            the strip is repainted, so the new area grows out of the picture instead of meeting it at a hard edge
                            (default 0).
@@ -44,6 +46,8 @@ def build_parser():
     p.add_argument("--W", type=int, default=512, help="window width in pixels")
     p.add_argument("--canvas", type=str, default=None, metavar="HxW", help="the canvas in pixels, sampled as overlapping --H x --W windows")
     p.add_argument("--canvas_stride", type=int, default=None, metavar="PX", help="distance between neighbouring windows (default: half a window)")
+    p.add_argument("--canvas_wrap", type=str, default=None, choices=("x", "y", "xy"),
+                   help="the canvas closes on itself along these axes (x: 360 degree panorama, xy: tileable image)")
     p.add_argument("--place", type=str, default="0,0", metavar="X,Y", help="top-left corner of --init-img on the canvas, pixels")
     p.add_argument("--seam", type=int, default=0, metavar="PX",
                    help="erode the picture's footprint by PX on every side that does not lie on the canvas border (that strip is repainted)")
@@ -78,13 +82,16 @@ def check_options(opt):
 
 def keep_masks(size, place, seam, grid, f=8):
     """(keep [1, 1, Hc, Wc], keep_px [1, 1, f Hc, f Wc], (y0, x0) the picture's latent offset): 1 on the footprint of a size x size
-    picture at pixel (X, Y) = place, eroded by `seam` pixels on every side that does not lie on the canvas border."""
+    picture at pixel (X, Y) = place, eroded by `seam` pixels on every side that does not lie on the canvas border. The borders of a
+    wrapped axis (grid.wrap) are no borders: the canvas goes on behind them, so the seam is eroded there too. A footprint that would
+    itself cross the seam is refused like one outside the canvas."""
     X, Y = place
     Hpx, Wpx = grid.Hc * f, grid.Wc * f
     if X + size > Wpx or Y + size > Hpx:
         raise SystemExit("--place %d,%d: the %d x %d picture does not lie inside the %d x %d canvas" % (X, Y, size, size, Hpx, Wpx))
-    top, bottom = Y + (seam if Y > 0 else 0), Y + size - (seam if Y + size < Hpx else 0)
-    left, right = X + (seam if X > 0 else 0), X + size - (seam if X + size < Wpx else 0)
+    wx, wy = "x" in grid.wrap, "y" in grid.wrap
+    top, bottom = Y + (seam if Y > 0 or wy else 0), Y + size - (seam if Y + size < Hpx or wy else 0)
+    left, right = X + (seam if X > 0 or wx else 0), X + size - (seam if X + size < Wpx or wx else 0)
     if top >= bottom or left >= right:
         raise SystemExit("--seam %d leaves nothing of the %d x %d picture kept" % (seam, size, size))
     keep_px = torch.zeros(1, 1, Hpx, Wpx)
@@ -170,7 +177,7 @@ def main(argv=None):
                                unconditional_conditionings=[c[0] for c in conds], bboxs=[[l[n] for n in l] for _, _, l, _ in group],
                                object_names=[list(l.keys()) for _, _, l, _ in group], local_conditionings=[c[2] for c in conds],
                                curr_texts=[p for _, p, _, _ in group], x_T=x_T, unconditional_guidance_scale=opt.scale, eta=opt.ddim_eta,
-                               seed=opt.seed, prompt_indices=[i for i, _, _, _ in group], channels=opt.C)
+                               seed=opt.seed, prompt_indices=[i for i, _, _, _ in group], channels=opt.C, wrap=grid.wrap)
 
     by_k = {}
     for it in items:

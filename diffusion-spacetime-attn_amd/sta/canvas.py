@@ -23,6 +23,12 @@ in ascending order): the restatements are what the kernels are tested against an
 Inpainting and outpainting (a solver.Blend with canvas-shaped x0 / noise and keep [P, 1, Hc, Wc]): `window_blend` is the first call's
 blend and the split in one launch (sta_window_blend), `sampler_step_windows_masked` the step of call i with the blend of call i + 1 on
 x_next (sta_sampler_step_windows_masked); restatements `window_blend_reference` and `step_windows_masked_reference`.
+
+Wrap-around canvases (`window_grid(..., wrap="x" | "y" | "xy")`: a 360 degree panorama closes along x, a tileable image along both axes):
+the offsets of a wrapped axis of length L are 0, stride, ..., L - stride (L % stride == 0, L >= 1.5 s), and the window at offset o covers
+the canvas positions (o + d) mod L, d = 0 .. s - 1: the last windows run over the seam, so the first and the last column share a UNet
+window. Every window sees a centre at the representative nearest to it (`window_centres`), the restatements index modulo L, and the CUDA
+dispatchers call the `_ring` siblings of the five entry points; a grid without wrap is the clamped grid above, code and bits unchanged.
 """
 import ctypes
 from collections import namedtuple
@@ -32,7 +38,8 @@ import torch
 from sta import lib, solver
 
 MAX_WINDOW_OFFSETS = lib.MAX_WINDOW_OFFSETS
-Grid = namedtuple("Grid", "Hc Wc s stride oy ox ny nx T")
+Grid = namedtuple("Grid", "Hc Wc s stride oy ox ny nx T wrap", defaults=("",))
+WRAPS = {"": 0, "x": 1, "y": 2, "xy": 3}         # Grid.wrap -> the C-ABI's wrap mask (bit 0 = x, bit 1 = y)
 _DT = solver._DT
 
 
@@ -44,9 +51,23 @@ def _offsets(L, s, stride):
     return tuple(o)
 
 
-def window_grid(Hc, Wc, s, stride):
-    """The window grid of an Hc x Wc canvas latent (sides in latent pixels) -> Grid(Hc, Wc, s, stride, oy, ox, ny, nx, T)."""
+def _ring_offsets(L, s, stride, axis):
+    """The offsets 0, stride, ..., L - stride of a wrapped axis of length L (the windows behind L - s run over the seam)."""
+    if L % stride:
+        raise ValueError("wrapped %s axis: length %d is not a multiple of the stride %d (the ring of windows would not close evenly)"
+                         % (axis, L, stride))
+    if 2 * L < 3 * s:
+        raise ValueError("wrapped %s axis: length %d is shorter than 1.5 windows of %d (a disc of diameter 0.4 s could enter one window "
+                         "from both sides)" % (axis, L, s))
+    return tuple(range(0, L, stride))
+
+
+def window_grid(Hc, Wc, s, stride, wrap=""):
+    """The window grid of an Hc x Wc canvas latent (sides in latent pixels) -> Grid(Hc, Wc, s, stride, oy, ox, ny, nx, T, wrap).
+    wrap: "" (the clamped grid), "x", "y" or "xy": the axes that close on themselves."""
     Hc, Wc, s, stride = int(Hc), int(Wc), int(s), int(stride)
+    if wrap not in WRAPS:
+        raise ValueError("wrap = %r is none of '', 'x', 'y', 'xy' (canvas %d x %d, window %d, stride %d)" % (wrap, Hc, Wc, s, stride))
     for name, v in (("window side s", s), ("stride", stride), ("canvas height Hc", Hc), ("canvas width Wc", Wc)):
         if v <= 0 or v % 8:
             raise ValueError("%s = %d is not a positive multiple of 8 (canvas %d x %d, window %d, stride %d)" % (name, v, Hc, Wc, s, stride))
@@ -54,11 +75,12 @@ def window_grid(Hc, Wc, s, stride):
         raise ValueError("the canvas %d x %d is smaller than the window %d" % (Hc, Wc, s))
     if stride > s:
         raise ValueError("stride %d > window %d would leave gaps between windows" % (stride, s))
-    oy, ox = _offsets(Hc, s, stride), _offsets(Wc, s, stride)
+    oy = _ring_offsets(Hc, s, stride, "y") if "y" in wrap else _offsets(Hc, s, stride)
+    ox = _ring_offsets(Wc, s, stride, "x") if "x" in wrap else _offsets(Wc, s, stride)
     if len(oy) > MAX_WINDOW_OFFSETS or len(ox) > MAX_WINDOW_OFFSETS:
         raise ValueError("canvas %d x %d with window %d and stride %d needs %d x %d window offsets; at most %d per axis"
                          % (Hc, Wc, s, stride, len(oy), len(ox), MAX_WINDOW_OFFSETS))
-    return Grid(Hc, Wc, s, stride, oy, ox, len(oy), len(ox), len(oy) * len(ox))
+    return Grid(Hc, Wc, s, stride, oy, ox, len(oy), len(ox), len(oy) * len(ox), wrap)
 
 
 def windows(grid):
@@ -66,16 +88,36 @@ def windows(grid):
     return [(y0, x0) for y0 in grid.oy for x0 in grid.ox]
 
 
+def _centre(u, L, o, s, wrapped):
+    """Canvas-normalised coordinate u on an axis of length L -> the window's own coordinate (offset o, side s). Wrapped axis: of the
+    images u L + k L the one nearest the window's middle, so an object near the seam is seen by the windows on both sides of it."""
+    c = float(u) * L - o
+    if wrapped:
+        c = ((c - s / 2 + L / 2) % L) + s / 2 - L / 2
+    return c / s
+
+
 def window_centres(centres, grid):
     """Canvas-normalised centres [(x, y)] -> per window (in window order) the list of that window's centres."""
-    return [[[(float(x) * grid.Wc - x0) / grid.s, (float(y) * grid.Hc - y0) / grid.s] for x, y in centres] for y0, x0 in windows(grid)]
+    wx, wy = "x" in grid.wrap, "y" in grid.wrap
+    return [[[_centre(x, grid.Wc, x0, grid.s, wx), _centre(y, grid.Hc, y0, grid.s, wy)] for x, y in centres] for y0, x0 in windows(grid)]
+
+
+def _region(grid, y0, x0, device=None):
+    """The index of window (y0, x0) into the last two axes of a canvas tensor: slices on the clamped grid, index tensors modulo the
+    axis length on a wrapped one (s <= L: no position twice)."""
+    if not grid.wrap:
+        return slice(y0, y0 + grid.s), slice(x0, x0 + grid.s)
+    ys = (y0 + torch.arange(grid.s, device=device)) % grid.Hc
+    xs = (x0 + torch.arange(grid.s, device=device)) % grid.Wc
+    return ys[:, None], xs[None, :]
 
 
 def cover_count(grid):
     """[Hc, Wc] int32: how many windows cover each canvas element (>= 1 everywhere)."""
     n = torch.zeros((grid.Hc, grid.Wc), dtype=torch.int32)
     for y0, x0 in windows(grid):
-        n[y0:y0 + grid.s, x0:x0 + grid.s] += 1
+        n[_region(grid, y0, x0)] += 1
     return n
 
 
@@ -96,7 +138,7 @@ def window_split_reference(src, grid, dtype=None, rows=1):
     out = torch.empty((P, grid.T, 2, C, s, s), dtype=v.dtype, device=src.device)
     for w, (y0, x0) in enumerate(windows(grid)):
         for r in range(2):
-            out[:, w, r] = v[:, r if rows == 2 else 0, :, y0:y0 + s, x0:x0 + s]
+            out[:, w, r] = v[:, r if rows == 2 else 0][(Ellipsis,) + _region(grid, y0, x0, src.device)]
     return out.reshape(2 * P * grid.T, C, s, s)
 
 
@@ -111,9 +153,10 @@ def _fuse32(eps, grid):
     seen = torch.zeros((grid.Hc, grid.Wc), dtype=torch.bool, device=eps.device)
     for w, (y0, x0) in enumerate(windows(grid)):
         v = e[:, w].to(torch.float32)
-        region = acc[..., y0:y0 + s, x0:x0 + s]
-        region.copy_(torch.where(seen[y0:y0 + s, x0:x0 + s], region + v, v))      # the first covering window's value starts the sum
-        seen[y0:y0 + s, x0:x0 + s] = True
+        at = _region(grid, y0, x0, eps.device)
+        region = acc[(Ellipsis,) + at]
+        acc[(Ellipsis,) + at] = torch.where(seen[at], region + v, v)      # the first covering window's value starts the sum
+        seen[at] = True
     return (acc / cover_count(grid).to(eps.device, torch.float32)).reshape(2 * P, C, grid.Hc, grid.Wc)
 
 
@@ -150,12 +193,19 @@ _TABLES = {}
 
 
 def _grid_args(grid):
-    """(ny, nx, oy, ox, s) as the C-ABI takes them; the host offset arrays are kept per grid."""
+    """(ny, nx, oy, ox, s) as the C-ABI takes them, on a wrapped grid (ny, nx, oy, ox, s, wrap) as the `_ring` siblings take them; the
+    host offset arrays are kept per grid."""
     key = (grid.oy, grid.ox)
     if key not in _TABLES:
         _TABLES[key] = ((ctypes.c_int * grid.ny)(*grid.oy), (ctypes.c_int * grid.nx)(*grid.ox))
     oy, ox = _TABLES[key]
-    return grid.ny, grid.nx, ctypes.addressof(oy), ctypes.addressof(ox), grid.s
+    return (grid.ny, grid.nx, ctypes.addressof(oy), ctypes.addressof(ox), grid.s) + ((WRAPS[grid.wrap],) if grid.wrap else ())
+
+
+def _entry(name, grid):
+    """(the C function, its name) of launch `name` on this grid: the `_ring` sibling when an axis wraps."""
+    name = name + "_ring" if grid.wrap else name
+    return getattr(lib.load(), name), name
 
 
 def _stream(t):
@@ -174,9 +224,9 @@ def window_split(src, grid, dtype=None, rows=1):
     P, C = _canvases(src.shape[0], rows, "src"), src.shape[1]
     src = src.detach().contiguous()
     xin = torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=src.device)
-    lib.check(lib.load().sta_window_split(src.data_ptr(), xin.data_ptr(), P, rows, C, grid.Hc, grid.Wc, *_grid_args(grid),
-                                          lib.STA_SRC_F32 if src.dtype == torch.float32 else _DT[dtype], _DT[dtype], _stream(src)),
-              "sta_window_split")
+    fn, name = _entry("sta_window_split", grid)
+    lib.check(fn(src.data_ptr(), xin.data_ptr(), P, rows, C, grid.Hc, grid.Wc, *_grid_args(grid),
+                 lib.STA_SRC_F32 if src.dtype == torch.float32 else _DT[dtype], _DT[dtype], _stream(src)), name)
     return xin
 
 
@@ -191,8 +241,8 @@ def window_fuse(eps, grid):
     P, C = _canvases(eps.shape[0], 2 * grid.T, "eps"), eps.shape[1]
     eps = eps.detach().contiguous()
     out = torch.empty((2 * P, C, grid.Hc, grid.Wc), dtype=eps.dtype, device=eps.device)
-    lib.check(lib.load().sta_window_fuse(eps.data_ptr(), out.data_ptr(), P, C, grid.Hc, grid.Wc, *_grid_args(grid), _DT[eps.dtype],
-                                         _stream(eps)), "sta_window_fuse")
+    fn, name = _entry("sta_window_fuse", grid)
+    lib.check(fn(eps.data_ptr(), out.data_ptr(), P, C, grid.Hc, grid.Wc, *_grid_args(grid), _DT[eps.dtype], _stream(eps)), name)
     return out
 
 
@@ -237,7 +287,8 @@ def _step_windows(eps, x, m_prev, noise, c, bl, grid, want_xin):
         blend, q = (x0.data_ptr(), keep.data_ptr(), qn.data_ptr()), (bl.q_a, bl.q_b)
     args = (eps.data_ptr(), x.data_ptr(), _ptr(m_prev), _ptr(noise)) + blend + (x_next.data_ptr(), m.data_ptr(), _ptr(xin))
     args += (x.shape[0], x.shape[1], grid.Hc, grid.Wc) + _grid_args(grid) + tuple(c) + q + (_DT[eps.dtype], _stream(x))
-    lib.check(getattr(lib.load(), "sta_" + what)(*args), "sta_" + what)
+    fn, name = _entry("sta_" + what, grid)
+    lib.check(fn(*args), name)
     return x_next, m, xin
 
 
@@ -267,6 +318,7 @@ def window_blend(x, bl, grid, dtype=None, want_xin=False):
     P, C = x.shape[0], x.shape[1]
     out = torch.empty_like(x)
     xin = torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=x.device) if want_xin else None
-    lib.check(lib.load().sta_window_blend(x.data_ptr(), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(), out.data_ptr(), _ptr(xin), P, C,
-                                          grid.Hc, grid.Wc, *_grid_args(grid), bl.q_a, bl.q_b, _DT[dtype], _stream(x)), "sta_window_blend")
+    fn, name = _entry("sta_window_blend", grid)
+    lib.check(fn(x.data_ptr(), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(), out.data_ptr(), _ptr(xin), P, C, grid.Hc, grid.Wc,
+                 *_grid_args(grid), bl.q_a, bl.q_b, _DT[dtype], _stream(x)), name)
     return out, xin

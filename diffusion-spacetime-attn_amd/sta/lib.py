@@ -46,7 +46,8 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 # that spills one (a spilled B fragment is a scratch round trip per MFMA: the pass would be slower than the pair it replaces).
 # (sta_conv.hip: the sub-pixel instantiations conv3x3_nhwc_kernel<T, GEO, NTW, true> — "Lb1E" is the mangled `true`)
 # (sta_sampler.hip: the window kernels index offset tables that arrive by value in the kernel arguments; a toolchain that copies the
-# tables to scratch to index them is refused)
+# tables to scratch to index them is refused; the names are substrings, so every instantiation — the four wrap masks of the `_ring`
+# entry points included — falls under the rule)
 # (sta_rows640.hip: an included source is named by its own file; its kernels are looked for in the assembly of the unit that includes it)
 NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",), "sta_rows640.hip": ("rows640_kernel",),
                     "sta_sampler.hip": ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel",
@@ -163,6 +164,12 @@ SYMBOLS = {
     "sta_sampler_step_windows": (_i, [_vp] * 7 + [_l] + [_i] * 5 + [_vp, _vp, _i] + [_f] * 8 + [_i, _vp]),
     "sta_sampler_step_windows_masked": (_i, [_vp] * 10 + [_l] + [_i] * 5 + [_vp, _vp, _i] + [_f] * 10 + [_i, _vp]),
     "sta_window_blend": (_i, [_vp] * 6 + [_l] + [_i] * 5 + [_vp, _vp, _i, _f, _f, _i, _vp]),
+    # wrap-around canvases: the siblings of the five above with `int wrap` directly after s
+    "sta_window_split_ring": (_i, [_vp, _vp, _l] + [_i] * 6 + [_vp, _vp] + [_i] * 4 + [_vp]),
+    "sta_window_fuse_ring": (_i, [_vp, _vp, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _i, _vp]),
+    "sta_sampler_step_windows_ring": (_i, [_vp] * 7 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i] + [_f] * 8 + [_i, _vp]),
+    "sta_sampler_step_windows_masked_ring": (_i, [_vp] * 10 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i] + [_f] * 10 + [_i, _vp]),
+    "sta_window_blend_ring": (_i, [_vp] * 6 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i, _f, _f, _i, _vp]),
 }
 
 

@@ -391,6 +391,16 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  *   bit-equal to sta_sampler_step_masked. The last call of a trajectory takes sta_sampler_step_windows (no blend after the last step).
  * sta_window_blend: the blend of the first call, x_out = keep (q_a x0 + q_b noise) + (1 - keep) x on [P][C][Hc][Wc] fp32, and xin (NULL =
  *   not written) = the windows of the rounded result: sta_latent_blend and sta_window_split (rows = 1) in one launch.
+ *
+ * Wrap-around canvases (360 degree panoramas: x closes on itself; tileable images: both axes): the five siblings sta_window_split_ring,
+ * sta_window_fuse_ring, sta_sampler_step_windows_ring, sta_sampler_step_windows_masked_ring and sta_window_blend_ring take `int wrap`
+ * directly after s and are otherwise their sibling, argument for argument. wrap: bit 0 = the x axis (columns, length Wc) is cyclic, bit 1 =
+ * the y axis (rows, length Hc); wrap = 0 is the sibling itself, bit for bit. On a cyclic axis of length L the window at offset o covers the
+ * canvas positions (o + d) mod L, d = 0 .. s - 1: a window may run over the seam, and the first and the last column share windows. The visiting
+ * order (ascending w), the sum from the first covering window's value and the division by the count are unchanged.
+ * Rules of a cyclic axis (STA_E_ARG with text, nothing launched; a non-cyclic axis keeps the rules above): wrap in 0 .. 3; 1 ..
+ * STA_MAX_WINDOW_OFFSETS offsets, the first 0, ascending multiples of 8, every offset < L (o + s <= L is NOT required), consecutive ones at
+ * most s apart, and the ring closes without a gap: L - o[n - 1] <= s; s <= L (a window covers an element at most once).
  */
 #define STA_MAX_WINDOW_OFFSETS 16
 #define STA_SRC_F32 2
@@ -407,6 +417,20 @@ int sta_sampler_step_windows_masked(const void* eps, const float* x, const float
                                     float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream);
 int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
                      int Wc, int ny, int nx, const int* oy, const int* ox, int s, float q_a, float q_b, int dtype, void* stream);
+int sta_window_split_ring(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox,
+                          int s, int wrap, int src_dtype, int dtype, void* stream);
+int sta_window_fuse_ring(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                         int dtype, void* stream);
+int sta_sampler_step_windows_ring(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin,
+                                  long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale,
+                                  float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream);
+int sta_sampler_step_windows_masked_ring(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
+                                         const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc,
+                                         int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t,
+                                         float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype,
+                                         void* stream);
+int sta_window_blend_ring(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
+                          int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream);
 
 /*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
