@@ -34,6 +34,7 @@
 #include "sta_unet.h"
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
+#include "sta_encode_dev.h"     // the per-pixel arithmetic of part 2: shared with the canvas form in sta_window.hip
 
 namespace {
 
@@ -216,33 +217,18 @@ __global__ __launch_bounds__(256) void vae_encode_step_kernel(const T* __restric
                                                               float* __restrict__ x, float* __restrict__ z0, T* __restrict__ xin, long npx,
                                                               long hw, float scale_factor, float sqrt_a, float sqrt_1ma) {
   using V8 = typename V8T<T>::type;
-  float w[8][8], bias[8];
-#pragma unroll
-  for (int o = 0; o < 8; ++o) {
-    bias[o] = qb[o];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[o][i] = qw[8 * o + i];
-  }
+  QuantConv q;
+  quant_conv_load(q, qw, qb);
   const long stride = (long)gridDim.x * 256;
   for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < npx; v += stride) {
     const long img = v / hw, pix = v - img * hw;
-    const V8 hv = ((const V8*)h)[v];                       // the 8 channels of one NHWC pixel: one 16-byte load
-    float hf[8], mo[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hf[i] = (float)hv[i];
-#pragma unroll
-    for (int o = 0; o < 8; ++o) {
-      float s = bias[o];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += w[o][i] * hf[i];
-      mo[o] = s;
-    }
+    float mo[8];
+    quant_moments<T>(q, ((const V8*)h)[v], mo);            // the 8 channels of one NHWC pixel: one 16-byte load
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float logvar = fminf(fmaxf(mo[4 + c], -30.f), 20.f);
       const long idx = (img * 4 + c) * hw + pix;
-      const float zz = scale_factor * (mo[c] + expf(0.5f * logvar) * n_post[idx]);
-      const float xx = sqrt_a * zz + sqrt_1ma * n_enc[idx];
+      float zz;
+      const float xx = encode1(mo[c], mo[4 + c], n_post[idx], n_enc[idx], scale_factor, sqrt_a, sqrt_1ma, zz);
       x[idx] = xx;
       if (z0) z0[idx] = zz;
       if (xin) {

@@ -1,6 +1,6 @@
 // sta_window.hip — wide canvases sampled as overlapping square windows (gfx950). C-ABI in include/sta_unet.h (sta_window_split /
-// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend, and their `_ring` siblings for canvases
-// that close on themselves: WRAP, a compile-time mask of the cyclic axes, 0 in the five clamped entry points). #included at the end of
+// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend / sta_vae_encode_step_windows, and their
+// `_ring` siblings for canvases that close on themselves: WRAP, a compile-time mask of the cyclic axes, 0 in the clamped entry points). #included at the end of
 // sta_sampler.hip (its flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division). The step on the overlap means
 // is step1 of sta_step_dev.h, the definition the square kernels use, with that header's V8T / F4 / load8 / store8 / round8 / StepCoef.
 // Conventions of sta_sampler.hip: 256-lane groups, grid-stride, a lane owns 8 consecutive elements of one CANVAS row, 16-byte loads and
@@ -10,8 +10,12 @@
 // one writer per output element, the same bits from launch to launch.
 // Inpainting on a canvas (sta_sampler_step_windows_masked / sta_window_blend): the blend is blend1 of sta_blend_dev.h, the definition
 // sta_inpaint.hip uses for square images.
+// img2img on a canvas (sta_vae_encode_step_windows and its `_ring` sibling): from the encoder's output on the whole canvas to the canvas
+// state and the first call's window inputs in one launch; the per-pixel arithmetic is sta_encode_dev.h's, the definition
+// sta_vae_encode_step (sta_encode.hip) uses for square images.
 
 #include "sta_blend_dev.h"
+#include "sta_encode_dev.h"
 #include "sta_step_dev.h"
 
 namespace {
@@ -223,6 +227,54 @@ __global__ __launch_bounds__(256) void window_blend_kernel(const float* __restri
   }
 }
 
+// img2img on a canvas: vae_encode_step_kernel (sta_encode.hip) on the whole canvas's encoder output, then the split — the same
+// quant_moments / encode1 of sta_encode_dev.h per latent pixel, and window_split_kernel's (rows = 1) scatter of the rounded x.
+// h [P][Hc][Wc][8] T (NHWC); n_post, n_enc, x, z0 [P][4][Hc][Wc] fp32 (z0 null = not written); xin (null = not written) [2 P T][4][s][s].
+// A lane owns 8 consecutive canvas pixels of one row (vector v of [P][Hc][Wc / 8]): their 8 x 8 channels are 128 contiguous bytes of h,
+// eight 16-byte loads; per latent channel it then reads the two noises' and writes x's (z0's) 8-vector and hands the rounded one to scatter.
+template <typename T, int WRAP>
+__global__ __launch_bounds__(256) void vae_encode_step_windows_kernel(const T* __restrict__ h, const float* __restrict__ qw,
+                                                                      const float* __restrict__ qb, const float* __restrict__ n_post,
+                                                                      const float* __restrict__ n_enc, float* __restrict__ x,
+                                                                      float* __restrict__ z0, T* __restrict__ xin, long nvec, int Hc, int Wc,
+                                                                      WinGrid g, float scale_factor, float sqrt_a, float sqrt_1ma) {
+  using V8 = typename V8T<T>::type;
+  QuantConv qc;
+  quant_conv_load(qc, qw, qb);
+#pragma unroll
+  for (int o = 0; o < 8; ++o) {   // the offset tables fill the scalar file: the 72 quant_conv constants live in vector registers
+    qc.bias[o] = in_vgpr(qc.bias[o]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) qc.w[o][i] = in_vgpr(qc.w[o][i]);
+  }
+  const int wvec = Wc / 8;
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const long line = v / wvec;                            // p Hc + y
+    CanvasPos q;
+    q.x = (int)(v - line * wvec) * 8;
+    q.row = line / Hc;
+    q.y = (int)(line - q.row * Hc);
+    const V8* hp = (const V8*)h + 8 * v;                   // pixel (p, y, x) of h is its vector line Wc + x = 8 v
+    float mo[8][8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) quant_moments<T>(qc, hp[k], mo[k]);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      q.c = c;
+      const long at = ((q.row * 4 + c) * Hc + q.y) * (long)Wc + q.x;
+      float np[8], ne[8], xx[8], zz[8];
+      load8(n_post + at, np);
+      load8(n_enc + at, ne);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) xx[k] = encode1(mo[k][c], mo[k][4 + c], np[k], ne[k], scale_factor, sqrt_a, sqrt_1ma, zz[k]);
+      store8(x + at, xx);
+      if (z0) store8(z0 + at, zz);
+      if (xin) scatter<T, WRAP>(xin, g, q.row, 0, 1, 4, Hc, Wc, q, round8<T>(xx));
+    }
+  }
+}
+
 // offsets along one axis of length L: 0 first, multiples of 8, ascending, no gap (step <= s), the last window ends at L
 int window_axis_ok(const char* what, const char* axis, int n, const int* o, int s, int L) {
   if (n < 1 || n > STA_MAX_WINDOW_OFFSETS) return sta_fail(STA_E_ARG, "%s: n%s=%d (need 1 .. %d offsets)", what, axis, n, STA_MAX_WINDOW_OFFSETS);
@@ -383,9 +435,44 @@ int window_blend(const char* what, const float* x, const float* x0, const float*
   });
 }
 
+int encode_step_windows(const char* what, const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc,
+                        float* x, float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                        float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!h || !quant_w || !quant_b || !n_post || !n_enc || !x) return sta_fail(STA_E_ARG, "%s: null pointer", what);
+  WinGrid g;
+  if (const int rc = window_grid_ok(what, P, 4, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
+  if (!sta_aligned16(h) || !sta_aligned16(n_post) || !sta_aligned16(n_enc) || !sta_aligned16(x) || !sta_aligned16(z0) || !sta_aligned16(xin))
+    return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_ARG, "%s: dtype %d (STA_BF16 or STA_F16)", what, dtype);
+  const long nvec = P * Hc * (Wc / 8);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return by_wrap(wrap, [&](auto w) {
+      return sta_launch<vae_encode_step_windows_kernel<T, decltype(w)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
+                                                                               (const T*)h, quant_w, quant_b, n_post, n_enc, x, z0, (T*)xin, nvec,
+                                                                               Hc, Wc, g, scale_factor, sqrt_a, sqrt_1ma);
+    });
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int sta_vae_encode_step_windows(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
+                                float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                                float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream) {
+  return encode_step_windows("vae_encode_step_windows", h, quant_w, quant_b, n_post, n_enc, x, z0, xin, P, Hc, Wc, ny, nx, oy, ox, s, 0,
+                             scale_factor, sqrt_a, sqrt_1ma, dtype, stream);
+}
+
+int sta_vae_encode_step_windows_ring(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
+                                     float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                                     float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream) {
+  return encode_step_windows("vae_encode_step_windows_ring", h, quant_w, quant_b, n_post, n_enc, x, z0, xin, P, Hc, Wc, ny, nx, oy, ox, s, wrap,
+                             scale_factor, sqrt_a, sqrt_1ma, dtype, stream);
+}
 
 int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
                      int src_dtype, int dtype, void* stream) {

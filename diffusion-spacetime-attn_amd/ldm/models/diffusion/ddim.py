@@ -94,6 +94,71 @@ class DDIMSampler(SolverSamplerBase):
         qc = first_stage_model.quant_conv
         return fused.vae_encode_step(h, qc.weight, qc.bias, n_post, n_enc, sf, float(sa[t_enc]), float(s1m[t_enc]), want_z0=want_z0)
 
+    def encode_step_canvas(self, h, first_stage_model, t_enc, n_post, n_enc, grid, scale_factor=None, want_z0=False):
+        """`encode_step` on a canvas: from the encoder's conv_out result h [P, 8, Hc, Wc] on the WHOLE canvas (PLMSSampler._encode_canvas)
+        to (x [P, 4, Hc, Wc] fp32, z0 or None, xin): the canvas state noised to table index t_enc and the first call's window input pairs
+        [2 P T, 4, s, s], what `decode_canvas(..., xin=xin)` feeds the first UNet call. The coefficient tables are encode_step's. GPU: one
+        sta_vae_encode_step_windows launch (sta.canvas.encode_step_windows); `canvas_fused_step = False`: sta_vae_encode_step +
+        window_split, the pair it replaces (tests, A/B runs); CPU tensors: the restatement."""
+        from sta import canvas as _cv
+        from sta import fused
+        sa, s1m = self._encode_coefs()
+        sf = self.model.scale_factor if scale_factor is None else scale_factor
+        qc = first_stage_model.quant_conv
+        if h.is_cuda and not self.canvas_fused_step:
+            x, z0, _ = fused.vae_encode_step(h, qc.weight, qc.bias, n_post, n_enc, sf, float(sa[t_enc]), float(s1m[t_enc]), want_z0=want_z0,
+                                             want_xin=False)
+            return x, z0, _cv.window_split(x, grid, h.dtype)
+        return _cv.encode_step_windows(h, qc.weight, qc.bias, n_post, n_enc, sf, float(sa[t_enc]), float(s1m[t_enc]), grid, want_z0=want_z0)
+
+    def decode_canvas(self, x_latents, canvas, window, stride=None, *, t_start, conditionings, unconditional_conditionings, bboxs,
+                      object_names, local_conditionings, unconditional_guidance_scale=7.5, seed=1, prompt_indices=None, curr_texts=None,
+                      xin=None, mask=None, x0=None, image=None, mask_px=None, wrap=""):
+        """img2img on a canvas: the last t_start DDIM calls of the schedule `make_schedule()` made (not made again, as `decode`), from the
+        canvas latents x_latents [P, 4, Hc, Wc] — an encoded picture noised by `encode_step_canvas` / `stochastic_encode`, or a canvas
+        sampled earlier. Every call is one CFG batch of 2 P T window rows and the step runs on the canvas (`sample_canvas`, whose other
+        keywords these are); call j runs at the timestep and with the weight column of call S - t_start + j. `last_result` as for
+        sample_canvas. xin: the first call's window input pairs [2 P T, 4, s, s] (encode_step_canvas); without it they come from
+        window_split. mask= / x0= (image= / mask_px=): the kept region is re-noised from x0 before every call as in `decode(mask=)` and
+        `inpaint_canvas`; the first call is blended too (sta_window_blend then replaces a given xin). Fixed weights only.
+        ValueError before any UNet call: everything sample_canvas / inpaint_canvas refuses apart from the start, t_start outside 1 .. S,
+        x_latents or xin of another shape than the canvas's, no schedule made."""
+        if self.tables is None:
+            raise ValueError("decode_canvas: make_schedule() first (the decode runs the last t_start calls of the schedule it made)")
+        S = len(self.tables["t_in"])
+        if not 1 <= int(t_start) <= S:
+            raise ValueError("decode_canvas: t_start must be in 1 .. %d, got %s" % (S, t_start))
+        if x_latents is None or x_latents.dim() != 4:
+            raise ValueError("decode_canvas: x_latents must be the canvas latents [P, C, Hc, Wc]")
+        masked = not (mask is None and x0 is None and image is None and mask_px is None)
+        if masked and (mask is None or x0 is None):
+            raise ValueError("decode_canvas: inpainting needs both mask= and x0=")
+        if (image is None) != (mask_px is None):
+            raise ValueError("decode_canvas: the pixel-space paste needs both image= and mask_px=")
+        channels = x_latents.shape[1]
+
+        def prepare(P, channels, grid):
+            want = (2 * P * grid.T, channels, grid.s, grid.s)
+            if xin is not None and tuple(xin.shape) != want:
+                raise ValueError("decode_canvas: xin %s must be the window pair batch %s of this canvas" % (tuple(xin.shape), list(want)))
+            if masked:
+                self._set_inpaint(mask, x0, image, mask_px, batch=P)
+                inp = self._inpaint
+                shapes = dict(x0=(P, channels, grid.Hc, grid.Wc), keep=(P, 1, grid.Hc, grid.Wc), image=(P, 3, 8 * grid.Hc, 8 * grid.Wc),
+                              keep_px=(P, 1, 8 * grid.Hc, 8 * grid.Wc))
+                for name, shape in shapes.items():
+                    if inp[name] is not None and tuple(inp[name].shape) != shape:
+                        raise ValueError("decode_canvas: %s %s must be [%d, %d, %d, %d] on this canvas"
+                                         % (dict(keep="mask", keep_px="mask_px").get(name, name), tuple(inp[name].shape), *shape))
+        self._xin0 = xin
+        try:
+            self._sample_canvas("decode_canvas", S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
+                                local_conditionings, x_latents.float(), unconditional_guidance_scale, None, seed, prompt_indices, curr_texts,
+                                channels, False, prepare=prepare, wrap=wrap, decode_from=S - int(t_start))
+        finally:
+            self._xin0, self._inpaint = None, None
+        return self.last_result["x0"]
+
     def _decode_start(self, t_start, use_original_steps):
         if use_original_steps:
             raise NotImplementedError("decode(use_original_steps=True) is not on the spatial-temporal path: the weight columns follow the "

@@ -352,9 +352,11 @@ class PLMSSampler(object):
 
     def _sample_canvas(self, what, S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
                        local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices, curr_texts, channels, verbose,
-                       prepare=None, wrap=""):
-        """The body of sample_canvas and inpaint_canvas: every refusal, then the epoch loop on the canvas with `_canvas` set.
-        prepare(P, channels, grid): the caller's own checks and state once the canvas is known (inpaint_canvas: the inpaint state)."""
+                       prepare=None, wrap="", decode_from=None):
+        """The body of sample_canvas, inpaint_canvas and DDIMSampler.decode_canvas: every refusal, then the epoch loop on the canvas with
+        `_canvas` set. prepare(P, channels, grid): the caller's own checks and state once the canvas is known (inpaint_canvas: the inpaint
+        state). decode_from: None, or the call decode_canvas starts at — its explicit permission for a non-zero `_start`, which it sets
+        itself once every refusal has passed (S is then the schedule's own length, and the schedule is not made again)."""
         from sta import canvas as _cv
         if self.opt_epochs > 1:
             raise ValueError("%s samples with fixed blend weights: opt_epochs = %d tracks epochs, and the loss front end "
@@ -362,7 +364,7 @@ class PLMSSampler(object):
         for name in ("attn_capture", "attn_loss", "latent_guidance"):
             if getattr(self, name) is not None:
                 raise ValueError("%s: an attached %s reads one square image's attention maps; detach it for canvases" % (what, name))
-        if getattr(self, "_start", 0):
+        if getattr(self, "_start", 0):      # set from outside: decode_canvas passes decode_from and leaves `_start` at 0 until here
             raise ValueError("%s: a trajectory that starts at call %d (img2img) is not defined on a canvas" % (what, self._start))
         Hc, Wc = canvas
         grid = _cv.window_grid(Hc, Wc, window, window // 2 if stride is None else stride, wrap)
@@ -384,7 +386,10 @@ class PLMSSampler(object):
             prepare(P, channels, grid)
         self._canvas = grid
         try:
-            self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+            if decode_from is None:
+                self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+            else:
+                self._start = int(decode_from)
             # the blocks see P T images: the canvas's local contexts once per window
             self.plms_sampling(cond, (P, channels, grid.Hc, grid.Wc), x_T=x_T, unconditional_guidance_scale=unconditional_guidance_scale,
                                unconditional_conditioning=uncond, text_index=0,
@@ -394,7 +399,25 @@ class PLMSSampler(object):
                                local_conditionings=[loc for loc in local_conditionings for _ in range(grid.T)], batched=True)
         finally:
             self._canvas = None
+            if decode_from is not None:
+                self._start = 0
         return None
+
+    def _encode_canvas(self, image, grid, first_stage_model=None):
+        """The one encode of a canvas picture: image [P, 3, 8 Hc, 8 Wc] in [-1, 1] -> h [P, 8, Hc, Wc], the encoder's conv_out result the
+        fused entry launch reads (DDIMSampler.encode_step_canvas). On a wrapped canvas the encoder must see across the seam, as the
+        decoder does (`_decode_canvas`): the image is padded circularly by 8 `canvas_wrap_margin` pixels on both sides of every wrapped
+        axis, encoded once and cropped by the margin in latent cells (a view: the launch takes its contiguous NHWC copy). (That bounds the
+        convolutional seam only: the VAE's mid-block attention is global.)"""
+        vae = self.model.first_stage_model if first_stage_model is None else first_stage_model
+        m = int(self.canvas_wrap_margin)
+        if tuple(image.shape[-2:]) != (8 * grid.Hc, 8 * grid.Wc):
+            raise ValueError("image %s is not the canvas's %d x %d pixels" % (tuple(image.shape), 8 * grid.Hc, 8 * grid.Wc))
+        if not grid.wrap or m == 0:
+            return vae.encode_moments_input(image)
+        mx, my = m if "x" in grid.wrap else 0, m if "y" in grid.wrap else 0
+        h = vae.encode_moments_input(torch.nn.functional.pad(image, (8 * mx, 8 * mx, 8 * my, 8 * my), mode="circular"))
+        return h[..., my:h.shape[-2] - my, mx:h.shape[-1] - mx]
 
     def _decode_canvas(self, img):
         """The one decode of the final latent. On a wrapped canvas the decoder must see across the seam: the latent is padded circularly
@@ -950,7 +973,9 @@ class SolverSamplerBase(PLMSSampler):
         return x
 
     def _canvas_trajectory(self, img, cond, uncond, scale, time_range, W, bboxs_curr, text_index, graph):
-        """The S calls of a canvas (sample_canvas: fixed weights, no autograd, from call 0). The first call's window inputs come from
+        """The calls `_start` .. S - 1 of a canvas (fixed weights, no autograd; sample_canvas / inpaint_canvas: from call 0; DDIMSampler.
+        decode_canvas: img2img, from call S - t_start with weight column i, eta draw i - _start and blend draw i - _start, the draw order
+        of `_trajectory`; m_prev starts as None). The first call's window inputs are `_xin0` (the fused encode step's) or come from
         window_split; after every UNet call ONE sta_sampler_step_windows launch reads the windows' output, forms the overlap means,
         steps the canvas state and writes the next call's window inputs: x and m_prev stay canvas-shaped, and nothing but the
         (graph-replayed) UNet call and that launch runs per step. `canvas_fused_step = False` takes window_fuse + solver_step +
@@ -964,18 +989,20 @@ class SolverSamplerBase(PLMSSampler):
         wdtype = next(self.model.model.parameters()).dtype
         S, P, device = len(time_range), img.shape[0], img.device
         fused, masked = self.canvas_fused_step, self._inpaint is not None
+        start = self._start        # > 0: DDIMSampler.decode_canvas (img2img): calls start .. S - 1 with weight column i, draws i - start
         x, m_prev = img, None
-        if masked and fused:
-            x, xin = _cv.window_blend(x, self._blend(0, x), grid, dtype=wdtype, want_xin=True)
-        else:
-            if masked:
-                x, _ = solver.latent_blend(x, self._blend(0, x), dtype=wdtype)
+        if masked and fused:       # the blend of the first call replaces a given `_xin0`, as in `_trajectory`
+            x, xin = _cv.window_blend(x, self._blend(start, x), grid, dtype=wdtype, want_xin=True)
+        elif masked:
+            x, _ = solver.latent_blend(x, self._blend(start, x), dtype=wdtype)
             xin = _cv.window_split(x, grid, wdtype)
-        for i in range(S):
+        else:
+            xin = self._xin0 if self._xin0 is not None else _cv.window_split(x, grid, wdtype)
+        for i in range(start, S):
             t_val = float(time_range[i]) if self.t_dtype.is_floating_point else int(time_range[i])
             out = unet(xin, torch.full((P,), t_val, device=device, dtype=self.t_dtype), W[..., i])
             c = self._coef(i, scale)
-            noise = self._noise(i, x) if c.c_n else None           # the eta draw of call i, then the blend draw of call i + 1
+            noise = self._noise(i - start, x) if c.c_n else None   # the eta draw of call i, then the blend draw of call i + 1
             bl = self._blend(i + 1, x) if masked and i + 1 < S else None       # no blend after the last step
             if fused and bl is not None:
                 x, m_prev, xin = _cv.sampler_step_windows_masked(out, x, m_prev, noise, c, bl, grid, dtype=wdtype, want_xin=True)

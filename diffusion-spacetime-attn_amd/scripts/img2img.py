@@ -10,6 +10,18 @@ or prompt index; prompts without an entry run with K = 0, plain SD img2img on th
 (or .jpg); the images of one CFG batch are encoded in one encoder call. Images load as the reference's load_img: sides rounded down
 to a multiple of 32, LANCZOS, scaled to [-1, 1]. Output files are named as txt2img names them (final{E-1}_s{seed}_index_{i}.png).
 
+--canvas HxW / --canvas_stride PX / --canvas_wrap x|y|xy / --window PX (default 512): img2img on a wide, tall or wrap-around canvas decoded
+as overlapping --window x --window windows (sta.canvas; the flags mean what they mean in the txt2img scripts, with --window as their --H =
+--W). The init image may then be of any size: it is resized to the canvas with LANCZOS at load time (printed), so a 512^2 picture with
+--canvas 1024x1024 --strength 0.4 is a tiled upscale-and-refine pass. The whole canvas is encoded once (on a wrapped canvas with circular
+padding, so the encoder sees across the seam), one sta_vae_encode_step_windows launch writes the canvas state and the first call's window
+inputs, and DDIMSampler.decode_canvas runs the last t_enc calls. The layout's centres are normalised to the canvas; prompts with the same
+object count run as P canvases of one batch (--batch_prompts); the draws below are canvas-shaped. Refused with --canvas before a model is
+built: --opt_epochs > 1, --attn_guidance, a --window that is no multiple of 8 x --f, and every refusal of the txt2img scripts' canvas
+grid. Not claimed: image quality or seam visibility with real weights; the VAE's mid-block attention is global over the canvas, O((Hc
+Wc)^2) memory in its chunked form, for the encoder as for the one decode; a disc keeps its radius of 0.2 window sides, so objects shrink
+relative to an upscaled canvas.
+
 Refused before anything is built: --plms (the reference raises NotImplementedError too), --dpm_solver, t_enc = int(strength S) outside
 1 .. S - 1 (at t_enc = S the reference indexes past its tables), --n_samples != 1, a non-square image or a side that is not a multiple
 of 64 (the blocks need square latents and the UNet downsamples three times), mixed image sizes.
@@ -34,7 +46,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def build_parser():
+def build_parser(canvas=False):
+    """canvas=True: img2img.py's own parser, with --canvas / --canvas_stride / --canvas_wrap / --window. inpaint.py and outpaint.py build
+    on this parser and take it without them (outpaint.py defines its own --canvas flags, inpaint.py has no canvas form)."""
     p = argparse.ArgumentParser()
     p.add_argument("--prompt", type=str, nargs="?", default="a painting of a virus monster playing guitar")
     p.add_argument("--init-img", type=str, nargs="?", help="path to the input image, or a directory with <prompt index>.png|jpg")
@@ -65,8 +79,33 @@ def build_parser():
     p.add_argument("--clip_tokenizer", type=str, default=None)
     p.add_argument("--synthetic", action="store_true", help="synthetic weights/text embeddings when no checkpoint is available")
     p.add_argument("--batch_prompts", type=int, default=1)
+    if canvas:
+        add_canvas_arguments(p)
     _txt2img_common.add_guidance_arguments(p, attn_res=True)
     return p
+
+
+def add_canvas_arguments(p):
+    p.add_argument("--canvas", type=str, default=None, metavar="HxW",
+                   help="img2img on a canvas of H x W pixels, decoded as overlapping --window x --window windows in one CFG batch per UNet "
+                        "call (sta.canvas); the init image, of any size, is resized to the canvas (LANCZOS): a smaller picture is upscaled "
+                        "and refined window by window; fixed blend weights only (--opt_epochs 0 or 1), no --attn_guidance")
+    p.add_argument("--canvas_stride", type=int, default=None, metavar="PX",
+                   help="distance between neighbouring windows of --canvas in pixels (default: half the window)")
+    p.add_argument("--canvas_wrap", type=str, default=None, choices=("x", "y", "xy"),
+                   help="the --canvas closes on itself along these axes (x: a 360 degree panorama)")
+    p.add_argument("--window", type=int, default=512, metavar="PX", help="side of the square windows of --canvas in pixels")
+
+
+def canvas_grid(opt):
+    """The sta.canvas.Grid of --canvas / --canvas_stride / --canvas_wrap / --window (the rules of the txt2img scripts,
+    _txt2img_common.canvas_grid, with --window as their --H = --W), or None without --canvas; every refusal that needs no GPU."""
+    view = argparse.Namespace(canvas=opt.canvas, canvas_stride=opt.canvas_stride, canvas_wrap=opt.canvas_wrap, H=opt.window, W=opt.window,
+                              f=opt.f, opt_epochs=opt.opt_epochs, attn_maps=False, attn_loss=None, attn_guidance=opt.attn_guidance)
+    try:
+        return _txt2img_common.canvas_grid(view)
+    except SystemExit as e:
+        raise SystemExit(str(e).replace("--H / --W", "--window").replace("--H x --W", "--window x --window"))
 
 
 def check_options(opt):
@@ -97,12 +136,17 @@ def read_prompts(opt):
     return [opt.prompt]
 
 
-def load_img(path):
-    """The reference's load_img (img2img.py:47-57): [1, 3, h, w] in [-1, 1], sides rounded down to a multiple of 32, LANCZOS."""
+def load_img(path, size=None):
+    """The reference's load_img (img2img.py:47-57): [1, 3, h, w] in [-1, 1], sides rounded down to a multiple of 32, LANCZOS.
+    size = (h, w): --canvas, the picture is resized to the canvas instead (any size in, LANCZOS; the resize is printed)."""
     from PIL import Image
     image = Image.open(path).convert("RGB")
     w, h = image.size
-    w, h = map(lambda x: x - x % 32, (w, h))
+    if size is None:
+        w, h = map(lambda x: x - x % 32, (w, h))
+    else:
+        print("%s: %d x %d resized to the %d x %d canvas (LANCZOS)" % (path, w, h, size[1], size[0]))
+        h, w = size
     image = image.resize((w, h), resample=Image.LANCZOS)
     image = np.array(image).astype(np.float32) / 255.0
     image = torch.from_numpy(image[None].transpose(0, 3, 1, 2))
@@ -155,14 +199,18 @@ def encode_noise(seed, shape, device):
 
 
 def main(argv=None):
-    opt = build_parser().parse_args(argv)
+    opt = build_parser(canvas=True).parse_args(argv)
     t_enc = check_options(opt)
+    grid = canvas_grid(opt)
     prompts = read_prompts(opt)
     paths = image_paths(opt.init_img, len(prompts))
-    images = {p: load_img(p) for p in dict.fromkeys(paths)}
-    size = check_images(images)
-    _txt2img_common.check_clip_option(opt, (size, size))
-    _txt2img_common.check_guidance_option(opt, size)
+    if grid is None:
+        images = {p: load_img(p) for p in dict.fromkeys(paths)}
+        size = check_images(images)
+        _txt2img_common.check_clip_option(opt, (size, size))
+        _txt2img_common.check_guidance_option(opt, size)
+    else:           # any picture, resized to the canvas: --opt_epochs > 1 and --attn_guidance are refused above, nothing else reads the size
+        images = {p: load_img(p, (grid.Hc * opt.f, grid.Wc * opt.f)) for p in dict.fromkeys(paths)}
     from sta import datasets
     layouts = datasets.load_layouts(opt.layout) if opt.layout else None
     loss_tokenize = None
@@ -201,8 +249,7 @@ def main(argv=None):
                           latent_guidance=_txt2img_common.make_guidance(opt, model))
     sampler.make_schedule(opt.ddim_steps, ddim_eta=opt.ddim_eta, verbose=False)
     os.makedirs(opt.outdir, exist_ok=True)
-    lat = size // opt.f
-    shape = (1, opt.C, lat, lat)
+    shape = (1, opt.C, size // opt.f, size // opt.f) if grid is None else (1, opt.C, grid.Hc, grid.Wc)
     print("target t_enc is %d steps" % t_enc)
 
     # posterior moments input h per distinct image, the images of one batch through one encoder call
@@ -212,7 +259,9 @@ def main(argv=None):
         todo = [p for p in dict.fromkeys(batch_paths) if p not in h_cache]
         if todo:
             with torch.no_grad():
-                h = vae.encode_moments_input(torch.cat([images[p] for p in todo]).to(dev))
+                batch = torch.cat([images[p] for p in todo]).to(dev)
+                # a canvas: one encode of the whole picture, which on a wrapped canvas sees across the seam (circular padding)
+                h = vae.encode_moments_input(batch) if grid is None else sampler._encode_canvas(batch, grid, vae)
             for p, hp in zip(todo, h.split(1)):
                 h_cache[p] = hp
         return torch.cat([h_cache[p] for p in batch_paths])
@@ -225,10 +274,20 @@ def main(argv=None):
         n_post = torch.cat([post_noise[g[3]] for g in group])
         n_enc = torch.cat([encode_noise(opt.seed, shape, dev) for _ in group])  # draw 2, one per prompt
         with torch.no_grad():
-            x, _, xin = sampler.encode_step(h, vae, t_enc, n_post, n_enc)
+            if grid is None:
+                x, _, xin = sampler.encode_step(h, vae, t_enc, n_post, n_enc)
+            else:       # the canvas state and the first call's window inputs in one launch
+                x, _, xin = sampler.encode_step_canvas(h, vae, t_enc, n_post, n_enc, grid)
         conds = [conditionings(model, p, list(l.keys()), dtype) for _, p, l, _ in group]
-        print("Start img2img for prompts %s" % [i for i, _, _, _ in group])
-        if len(group) == 1:
+        print("Start img2img for prompts %s" % [i for i, _, _, _ in group] + ("" if grid is None else " on a %s canvas (%d windows each)"
+                                                                              % (opt.canvas, grid.T)))
+        if grid is not None:        # the prompts of the group as P canvases of one CFG batch of 2 P T window rows per UNet call
+            sampler.decode_canvas(x, (grid.Hc, grid.Wc), grid.s, grid.stride, t_start=t_enc, conditionings=[c[1] for c in conds],
+                                  unconditional_conditionings=[c[0] for c in conds], bboxs=[[l[n] for n in l] for _, _, l, _ in group],
+                                  object_names=[list(l.keys()) for _, _, l, _ in group], local_conditionings=[c[2] for c in conds],
+                                  unconditional_guidance_scale=opt.scale, seed=opt.seed, prompt_indices=[i for i, _, _, _ in group],
+                                  curr_texts=[p for _, p, _, _ in group], xin=xin, wrap=grid.wrap)
+        elif len(group) == 1:
             (i, p, l, _), (uc, c, local) = group[0], conds[0]
             names = list(l.keys())
             sampler.decode(x, c, t_enc, unconditional_guidance_scale=opt.scale, unconditional_conditioning=uc, text_index=0, curr_text=p,

@@ -29,6 +29,10 @@ the offsets of a wrapped axis of length L are 0, stride, ..., L - stride (L % st
 the canvas positions (o + d) mod L, d = 0 .. s - 1: the last windows run over the seam, so the first and the last column share a UNet
 window. Every window sees a centre at the representative nearest to it (`window_centres`), the restatements index modulo L, and the CUDA
 dispatchers call the `_ring` siblings of the five entry points; a grid without wrap is the clamped grid above, code and bits unchanged.
+
+img2img on a canvas (`encode_step_windows`, restatement `encode_step_windows_reference`): from the VAE encoder's output on the whole canvas
+to the canvas state noised to the decode's start and the first call's window input pairs, one sta_vae_encode_step_windows launch
+(sta_vae_encode_step and sta_window_split in one); DDIMSampler.encode_step_canvas / decode_canvas are its users.
 """
 import ctypes
 from collections import namedtuple
@@ -188,6 +192,34 @@ def window_blend_reference(x, bl, grid, dtype=None, want_xin=False):
     return xb, (window_split_reference(xb, grid, dtype or x.dtype) if want_xin else None)
 
 
+def _check_encode(h, n_post, n_enc, grid):
+    if h.dim() != 4 or h.shape[1] != 8 or tuple(h.shape[-2:]) != (grid.Hc, grid.Wc):
+        raise ValueError("encode_step_windows: h %s must be [P, 8, %d, %d], the encoder's output on the whole canvas" % (tuple(h.shape), grid.Hc, grid.Wc))
+    want = (h.shape[0], 4, grid.Hc, grid.Wc)
+    if tuple(n_post.shape) != want or tuple(n_enc.shape) != want:
+        raise ValueError("encode_step_windows: noises %s / %s must be [P, 4, Hc, Wc] = %s" % (tuple(n_post.shape), tuple(n_enc.shape), want))
+
+
+def encode_step_windows_reference(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, dtype=None, want_z0=False, want_xin=True):
+    """img2img's entry into a canvas trajectory, restated: the encoder's conv_out result h [P, 8, Hc, Wc] on the whole canvas -> (x, z0,
+    xin). float32 arithmetic in the kernel's order per latent pixel (sta_vae_encode_step's): moments = qb + sum_i qw[:, i] h[i] with i
+    ascending, logvar clamped to [-30, 20], z0 = sf (mean + exp(logvar / 2) n_post), x = sa z0 + s1m n_enc; x, z0 [P, 4, Hc, Wc] float32
+    (z0 None unless want_z0); xin (want_xin) = window_split_reference(x) in `dtype` (default: h's). qw [8, 8] (or the 1x1 conv's
+    [8, 8, 1, 1]), qb [8]; sf, sa, s1m Python floats, rounded to float32 as the C-ABI takes them."""
+    _check_encode(h, n_post, n_enc, grid)
+    f32 = torch.float32
+    hf = h.detach().to(f32)
+    qw, qb = qw.detach().reshape(8, 8).to(hf.device, f32), qb.detach().reshape(8).to(hf.device, f32)
+    n_post, n_enc = n_post.detach().to(hf.device, f32), n_enc.detach().to(hf.device, f32)
+    sf, sa, s1m = (torch.tensor(float(v), dtype=f32, device=hf.device) for v in (sf, sa, s1m))
+    mo = qb.reshape(1, 8, 1, 1).expand(hf.shape[0], 8, grid.Hc, grid.Wc).clone()
+    for i in range(8):
+        mo = mo + qw[:, i].reshape(1, 8, 1, 1) * hf[:, i:i + 1]
+    z0 = sf * (mo[:, :4] + torch.exp(0.5 * mo[:, 4:].clamp(-30.0, 20.0)) * n_post)
+    x = sa * z0 + s1m * n_enc
+    return x, (z0 if want_z0 else None), (window_split_reference(x, grid, dtype or h.dtype) if want_xin else None)
+
+
 # ---------------------------------------------------------------------------------------------------- HIP entry points
 _TABLES = {}
 
@@ -322,3 +354,26 @@ def window_blend(x, bl, grid, dtype=None, want_xin=False):
     lib.check(fn(x.data_ptr(), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(), out.data_ptr(), _ptr(xin), P, C, grid.Hc, grid.Wc,
                  *_grid_args(grid), bl.q_a, bl.q_b, _DT[dtype], _stream(x)), name)
     return out, xin
+
+
+def encode_step_windows(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, dtype=None, want_z0=False, want_xin=True):
+    """The encoder's conv_out result h [P, 8, Hc, Wc] on the whole canvas (16-bit CUDA; taken as NHWC) -> (x, z0, xin): the canvas state
+    x [P, 4, Hc, Wc] float32 noised to the decode's start, the posterior's sample z0 (want_z0) and the first UNet call's window input
+    pairs xin [2 P T, 4, s, s] (want_xin). CUDA: ONE sta_vae_encode_step_windows launch (sta_vae_encode_step and sta_window_split in
+    one; the `_ring` sibling on a wrapped grid); CPU: encode_step_windows_reference."""
+    if not h.is_cuda:
+        return encode_step_windows_reference(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, dtype, want_z0, want_xin)
+    _check_encode(h, n_post, n_enc, grid)
+    if h.dtype not in _DT or (dtype or h.dtype) != h.dtype:
+        raise TypeError("sta_vae_encode_step_windows reads 16-bit h and writes window inputs of the same type (h %s, dtype %s)" % (h.dtype, dtype))
+    P = h.shape[0]
+    h = h.detach().contiguous(memory_format=torch.channels_last)
+    f = lambda t: t.detach().to(device=h.device, dtype=torch.float32).contiguous()
+    qw, qb, n_post, n_enc = f(qw.reshape(8, 8)), f(qb), f(n_post), f(n_enc)
+    x = torch.empty((P, 4, grid.Hc, grid.Wc), dtype=torch.float32, device=h.device)
+    z0 = torch.empty_like(x) if want_z0 else None
+    xin = torch.empty((2 * P * grid.T, 4, grid.s, grid.s), dtype=h.dtype, device=h.device) if want_xin else None
+    fn, name = _entry("sta_vae_encode_step_windows", grid)
+    lib.check(fn(h.data_ptr(), qw.data_ptr(), qb.data_ptr(), n_post.data_ptr(), n_enc.data_ptr(), x.data_ptr(), _ptr(z0), _ptr(xin), P,
+                 grid.Hc, grid.Wc, *_grid_args(grid), float(sf), float(sa), float(s1m), _DT[h.dtype], _stream(h)), name)
+    return x, z0, xin

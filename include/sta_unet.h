@@ -401,6 +401,16 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  * Rules of a cyclic axis (STA_E_ARG with text, nothing launched; a non-cyclic axis keeps the rules above): wrap in 0 .. 3; 1 ..
  * STA_MAX_WINDOW_OFFSETS offsets, the first 0, ascending multiples of 8, every offset < L (o + s <= L is NOT required), consecutive ones at
  * most s apart, and the ring closes without a gap: L - o[n - 1] <= s; s <= L (a window covers an element at most once).
+ *
+ * img2img on a canvas: sta_vae_encode_step_windows goes from the encoder's conv_out result on the WHOLE canvas to the canvas state and the
+ * first UNet call's window inputs in one launch: per latent pixel exactly sta_vae_encode_step's arithmetic (one device definition, csrc/
+ * sta_encode_dev.h: quant_conv, logvar clamped to [-30, 20], z0 = scale_factor (mean + exp(logvar / 2) n_post), x = sqrt_a z0 + sqrt_1ma
+ * n_enc), then sta_window_split (rows = 1, STA_SRC_F32) of x. Bit-equal to those two launches one after the other.
+ *   h: [P][Hc][Wc][8] dtype (NHWC, 16-byte aligned);  quant_w [8][8], quant_b [8] fp32;  n_post, n_enc, x, z0: [P][4][Hc][Wc] fp32 (z0 may be
+ *   NULL);  xin: NULL, or [2 P T][4][s][s] dtype = the rounded x in both rows of every covering window's pair, in sta_window_split's order.
+ * sta_vae_encode_step_windows_ring takes `int wrap` directly after s, as the other `_ring` siblings do (wrap = 0: the sibling, bit for bit).
+ * Rules (STA_E_ARG with text, nothing launched): the grid rules above (C = 4); every tensor but z0 / xin non-NULL; h, n_post, n_enc, x, z0,
+ * xin 16-byte aligned; wrap in 0 .. 3; dtype STA_BF16 / STA_F16.
  */
 #define STA_MAX_WINDOW_OFFSETS 16
 #define STA_SRC_F32 2
@@ -431,6 +441,12 @@ int sta_sampler_step_windows_masked_ring(const void* eps, const float* x, const 
                                          void* stream);
 int sta_window_blend_ring(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
                           int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream);
+int sta_vae_encode_step_windows(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
+                                float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                                float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream);
+int sta_vae_encode_step_windows_ring(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
+                                     float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                                     float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream);
 
 /*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
