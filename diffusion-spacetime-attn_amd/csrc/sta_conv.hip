@@ -109,15 +109,6 @@ __global__ __launch_bounds__(64) void pack_conv_up2_w_kernel(const T* __restrict
   *(typename Tr<T>::V8*)(packed + (size_t)fr * (FRAG / 2) + lane * 8) = x;
 }
 
-// sum over the 16 lanes of a DPP row (lanes 16 g .. 16 g + 15), result in every lane: xor 1, xor 2, half-row mirror, row mirror
-__device__ __forceinline__ float row16_sum(float x) {
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xf, 0xf, true));   // row_half_mirror
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xf, 0xf, true));   // row_mirror
-  return x;
-}
-
 struct CV {
   const char* x;        // [B][Hs][Ws][Cin] (Hs = H >> up2)
   const char* w;        // packed weights

@@ -34,6 +34,7 @@
 #include "sta_unet.h"
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
+#include "sta_wring_dev.h"      // row16_sum
 #include "sta_encode_dev.h"     // the per-pixel arithmetic of part 2: shared with the canvas form in sta_window.hip
 
 namespace {
@@ -65,15 +66,6 @@ struct S2 {
 // LDS byte offset of channel chunk g of the pixel at column col of an even input row (odd rows: bit 5 flipped; the chunk swizzle of
 // sta_conv.hip: chunk g of LDS pixel P sits at slot g ^ 2 ((P >> 2) & 1))
 __device__ __forceinline__ unsigned col_off(int col, int g) { return (unsigned)(col * 64 + ((g ^ (((col >> 2) & 1) << 1)) << 4)); }
-
-// sum over the 16 lanes of a DPP row (lanes 16 g .. 16 g + 15), result in every lane
-__device__ __forceinline__ float row16_sum(float x) {
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xf, 0xf, true));   // row_half_mirror
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xf, 0xf, true));   // row_mirror
-  return x;
-}
 
 template <typename T>
 __global__ __launch_bounds__(64 * S2_NW, 2) void conv3x3_s2_nhwc_kernel(const S2 p) {

@@ -451,3 +451,6 @@ int sta_ff_geglu_c640_qfrag(const void* y_qfrag, const void* packed_w, const voi
 }
 
 }  // extern "C"
+
+// The tail of a SpatialTransformer (the output Linear above + proj_out as one GEMM), built with this translation unit
+#include "sta_rowstail.hip"

@@ -47,14 +47,6 @@ __global__ __launch_bounds__(64) void pack_gemm_w_kernel(const T* __restrict__ w
   *(typename Tr<T>::V8*)(packed + (size_t)fr * (FRAG / 2) + lane * 8) = x;
 }
 
-__device__ __forceinline__ float gm_row16_sum(float x) {     // sum over the 16 lanes of a DPP row, result in every lane
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xf, 0xf, true));
-  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xf, 0xf, true));
-  return x;
-}
-
 struct GM {
   const char* x;        // [R][K], or [R][Ka] when xb is set
   const char* xb;       // null, or [R][K - Ka]: the input is the column concatenation [x | xb], read in place (Ka % 64 == 0)
@@ -268,8 +260,8 @@ __global__ __launch_bounds__(64 * GM_NW, 1) void gemm_rows_kernel(const GM p) {
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
           f32x4 lo, hi;
-          lo[0] = gm_row16_sum(ssum[t][0]); lo[1] = gm_row16_sum(ssq[t][0]); lo[2] = gm_row16_sum(ssum[t][1]); lo[3] = gm_row16_sum(ssq[t][1]);
-          hi[0] = gm_row16_sum(ssum[t][2]); hi[1] = gm_row16_sum(ssq[t][2]); hi[2] = gm_row16_sum(ssum[t][3]); hi[3] = gm_row16_sum(ssq[t][3]);
+          lo[0] = row16_sum(ssum[t][0]); lo[1] = row16_sum(ssq[t][0]); lo[2] = row16_sum(ssum[t][1]); lo[3] = row16_sum(ssq[t][1]);
+          hi[0] = row16_sum(ssum[t][2]); hi[1] = row16_sum(ssq[t][2]); hi[2] = row16_sum(ssum[t][3]); hi[3] = row16_sum(ssq[t][3]);
           if (c16 == 0) {
             *(f32x4*)(dst + 32 * t) = lo;
             *(f32x4*)(dst + 32 * t + 4) = hi;

@@ -1,6 +1,6 @@
 // sta_wring_dev.h — the device-side pieces the streamed-weight passes share (sta_rowgemm.hip, sta_ffgemm.hip, sta_lnqkv.hip,
 // sta_gemm.hip, sta_conv.hip): the 2-slot LDS weight ring, the row permutation of their packed weights, the wave reduction of
-// the LayerNorm kernels, the dropped buffer offset and a compile-time loop. gfx950 only. Needs nothing but the HIP runtime, so
+// the LayerNorm kernels, the DPP row sum of the statistics epilogues, the dropped buffer offset and a compile-time loop. gfx950 only. Needs nothing but the HIP runtime, so
 // the glue kernels (sta_unet.hip, sta_unet_bwd.hip) take wave_sum from here too.
 #ifndef STA_WRING_DEV_H
 #define STA_WRING_DEV_H
@@ -30,6 +30,17 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+
+// Sum over the 16 lanes of a DPP row (lanes 16 g .. 16 g + 15), result in every lane: xor 1, xor 2, half-row mirror, row mirror. The
+// epilogues that accumulate a consumer GroupNorm's statistics (sta_conv.hip, sta_gemm.hip, sta_encode.hip, sta_rowstail.hip) fold the
+// 16 rows / pixels of an MFMA column group with it.
+__device__ __forceinline__ float row16_sum(float x) {
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xf, 0xf, true));   // row_half_mirror
+  x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xf, 0xf, true));   // row_mirror
+  return x;
 }
 
 // f(integral_constant<int, 0>{}), ..., f(integral_constant<int, N - 1>{}) in this order: a loop whose index is a constant expression

@@ -289,9 +289,12 @@ class BasicTransformerBlock(nn.Module):
         cache.version, cache.centres = _ps.version(), centres
         return cache
 
-    def forward(self, x, context=None, time=None, text_index=None, coef=None, bboxs_curr=None, in_bias=None):
+    def forward(self, x, context=None, time=None, text_index=None, coef=None, bboxs_curr=None, in_bias=None, tail=None):
         """`in_bias` (not in the reference): a per-channel bias the caller still owes to `x` (SpatialTransformer's
-        proj_in bias when the projection ran as a bias-free GEMM); it is added inside the first fused pass."""
+        proj_in bias when the projection ran as a bias-free GEMM); it is added inside the first fused pass.
+        `tail` (not in the reference): a sta.fused.FfTail from the SpatialTransformer whose LAST block this is — where the fused
+        feed-forward path is taken and the shapes allow it, the block's output pass applies proj_out and the transformer's residual
+        as well and sets `tail.done`; otherwise the block returns what it returns without `tail`."""
         bboxs_curr = [] if bboxs_curr is None else bboxs_curr
         if context is None:
             raise ValueError("BasicTransformerBlock needs the text context")
@@ -307,10 +310,10 @@ class BasicTransformerBlock(nn.Module):
         al = self._attn_loss
         if al is not None and al.wants(x.shape[1]):
             # the loss's side value cannot leave a checkpointed forward: a recording block keeps its activations (sta.attnloss)
-            return self._forward(x, coef, cache, in_bias)
-        return checkpoint(lambda xx, cc: self._forward(xx, cc, cache, in_bias), (x, coef), self.parameters(), self.checkpoint)
+            return self._forward(x, coef, cache, in_bias, tail)
+        return checkpoint(lambda xx, cc: self._forward(xx, cc, cache, in_bias, tail), (x, coef), self.parameters(), self.checkpoint)
 
-    def _forward(self, x, coef, cache, in_bias=None):
+    def _forward(self, x, coef, cache, in_bias=None, tail=None):
         c = coef if coef.numel() else None
         cap = self._attn_capture                     # None unless an AttnCapture is attached (the one test an ordinary call pays)
         if cap is not None and not cap.wants(x.shape[1]):
@@ -362,7 +365,7 @@ class BasicTransformerBlock(nn.Module):
                     lin = self.attn2.to_out[0]
                     x, y = _fused.to_out_add_layernorm_ofrag(x, blended, self._wo_fragments(), lin.bias, n3.weight, n3.bias, n3.eps, self.attn2.heads,
                                                              y_qfrag=ffq)
-                    return self._ff_tail(x, y, ffq)
+                    return self._ff_tail(x, y, ffq, tail)
             else:
                 q = self.attn2.to_q(y)
                 self._keep_maps(q, c, cache)
@@ -374,7 +377,7 @@ class BasicTransformerBlock(nn.Module):
                 x, y = _fused.linear_res_c640(x, blended, self.attn2.to_out[0], n3, y_qfrag=ffq)
             else:
                 x, y = _fused.add_layernorm(x, self.attn2.to_out(blended), None, n3.weight, n3.bias, n3.eps, qfrag=ffq)
-            return self._ff_tail(x, y, ffq)
+            return self._ff_tail(x, y, ffq, tail)
         al = self._attn_loss                         # an AttnLayoutLoss records only while autograd is enabled: the two branches below
         if al is not None and not al.wants(x.shape[1]):
             al = None
@@ -421,8 +424,9 @@ class BasicTransformerBlock(nn.Module):
         return isinstance(net[0], GEGLU) and isinstance(net[0].proj, nn.Linear) and (x.numel() // x.shape[-1]) % 16 == 0 \
             and (_fused.ff_geglu_supported(x.shape[-1], net[0].proj.out_features // 2) or self._ff_c640(x))
 
-    def _ff_tail(self, x, y, ffq):
-        """x + ff(y) (attention.py:299). `ffq`: y is in query-fragment order and the GEGLU projection runs as the fused pass."""
+    def _ff_tail(self, x, y, ffq, tail=None):
+        """x + ff(y) (attention.py:299). `ffq`: y is in query-fragment order and the GEGLU projection runs as the fused pass.
+        `tail`: see forward — with it the output pass is sta.fused.ff_tail and the result is the SpatialTransformer's."""
         if not ffq:
             return self.ff(y) + x
         proj = self.ff.net[0].proj
@@ -430,6 +434,8 @@ class BasicTransformerBlock(nn.Module):
             w1 = _fused.cached_image(self, "w1", (proj.weight,), lambda: _fused.pack_geglu_c640_weight(proj.weight))
             h = _fused.ff_geglu_c640_qfrag(y, w1, proj.bias, proj.out_features // 2)
             if _fused.FF_OUT_RES_C640 and _fused.rows_c640_supported(x, self.ff.net[2]):
+                if tail is not None and _fused.ff_tail_supported(x, self.ff.net[2], tail.proj_out):
+                    return tail.run(x, h, self.ff.net[2])      # ... + proj_out + the transformer's residual (csrc/sta_rowstail.hip)
                 # ... and the output Linear + the block's last residual as one pass over row-major h (net[1] is Dropout(0))
                 return _fused.linear_res_c640(x, h, self.ff.net[2])[0]
             return self.ff.net[2](self.ff.net[1](h)) + x
@@ -437,8 +443,10 @@ class BasicTransformerBlock(nn.Module):
         out = self.ff.net[2]
         if isinstance(out, nn.Linear):
             # ... and the output Linear + the block's last residual as one pass over h in fragment order (net[1] is Dropout(0))
-            w2 = _fused.cached_image(self, "w2", (out.weight,), lambda: _fused.pack_ff_out_weight(out.weight))
             h = _fused.ff_geglu_qfrag(y, w1, proj.bias, proj.out_features // 2, h_frag=True)
+            if tail is not None and _fused.ff_tail_supported(x, out, tail.proj_out):
+                return tail.run(x, h, out)                      # ... + proj_out + the transformer's residual (csrc/sta_rowstail.hip)
+            w2 = _fused.cached_image(self, "w2", (out.weight,), lambda: _fused.pack_ff_out_weight(out.weight))
             return _fused.ff_out_res_hfrag(x, h, w2, out.bias)
         h = _fused.ff_geglu_qfrag(y, w1, proj.bias, proj.out_features // 2)
         return out(self.ff.net[1](h)) + x
@@ -508,12 +516,22 @@ class SpatialTransformer(nn.Module):
                 t = _fused.linear_rows(rows, _fused.packed_linear_weight(self, self.proj_in, w_in), inner, bias=self.proj_in.bias)
             else:
                 t = F.linear(rows, w_in, self.proj_in.bias)
-            for blk in self.transformer_blocks:
-                t = blk(t, context=context, time=time, text_index=text_index, coef=coef, bboxs_curr=bboxs_curr)
+            # the LAST block's feed-forward output pass can apply proj_out, its bias and the residual `+ x_in` as well (one GEMM over
+            # [h | x2]: csrc/sta_rowstail.hip); the block says through `tail.done` whether it did
+            x_rows = x.permute(0, 2, 3, 1).reshape(b, h * w, c)
+            tail = _fused.FfTail(self, self.proj_out, x_rows, h * w if _fused.GN_STATS_FROM_PRODUCER else None) if inner == c else None
+            last = len(self.transformer_blocks) - 1
+            for i, blk in enumerate(self.transformer_blocks):
+                t = blk(t, context=context, time=time, text_index=text_index, coef=coef, bboxs_curr=bboxs_curr, tail=tail if i == last else None)
+            if tail is not None and tail.done:
+                out = t.view(b, h, w, c).permute(0, 3, 1, 2)                                       # NHWC view of [b, hw, c]
+                if hasattr(t, "_sta_stats"):
+                    out._sta_stats = t._sta_stats          # the next GroupNorm's statistics, accumulated by the pass's epilogue
+                return out
             if _fused.linear_rows_supported(t, w_out):
                 # proj_out, its bias and the residual `+ x_in` (attention.py:346) in the GEMM's epilogue: no separate residual pass
                 y = _fused.linear_rows(t, _fused.packed_linear_weight(self, self.proj_out, w_out), c, bias=self.proj_out.bias,
-                                       res=x.permute(0, 2, 3, 1).reshape(b, h * w, c), stats_rows=h * w if _fused.GN_STATS_FROM_PRODUCER else None)
+                                       res=x_rows, stats_rows=h * w if _fused.GN_STATS_FROM_PRODUCER else None)
                 out = y.view(b, h, w, c).permute(0, 3, 1, 2)                                       # NHWC view of [b, hw, c]
                 if hasattr(y, "_sta_stats"):
                     out._sta_stats = y._sta_stats          # the next GroupNorm's statistics, accumulated by the GEMM's epilogue

@@ -344,6 +344,113 @@ def linear_res_c640(x, a, lin, norm=None, y_qfrag=False):
     return rows_c640(x, a, wp, lin.bias, norm.weight, norm.bias, norm.eps, y_qfrag=y_qfrag)
 
 
+# The tail of a SpatialTransformer as one pass (csrc/sta_rowstail.hip): ff.net[2] + the last block's residual, then proj_out + the
+# transformer's residual, are one GEMM over [h | x2] against [Wp W2 | Wp]. False: the feed-forward output pass, then proj_out as a row GEMM.
+FF_TAIL_PROJ_OUT_C320 = True    # level 0 (C = 320, h in fragment order)
+FF_TAIL_PROJ_OUT_C640 = True    # level 1 (C = 640, h row-major)
+FF_TAIL_PASS_ROWS = {320: 256, 640: 128}    # rows of one workgroup pass: what rows-per-image must be a multiple of for the statistics
+
+
+def ff_tail_weights(net2, proj_out):
+    """(W', b') of out = x_in + [h | x2] [W' | Wp]^T + b' for x3 = x2 + net2(h), out = x_in + proj_out(x3): W' = Wp W2 ([C, inner]) and
+    b' = Wp b2 + bp ([C], None when neither module has a bias). `proj_out`: an nn.Linear or a 1x1 nn.Conv2d. 16-bit weights are
+    multiplied in fp32 and W' is rounded ONCE to their dtype; wider types keep their own precision. b' stays in the precision of the
+    products (fp32 for 16-bit weights: the kernel reads it as such). Runs on any device."""
+    w2, wp = net2.weight.detach(), proj_out.weight.detach()
+    wp = wp.reshape(wp.shape[0], wp.shape[1])
+    acc = torch.float32 if w2.dtype in (torch.float16, torch.bfloat16) else w2.dtype
+    wpa = wp.to(acc)
+    w = (wpa @ w2.to(acc)).to(w2.dtype)
+    b = None
+    if net2.bias is not None:
+        b = wpa @ net2.bias.detach().to(acc)
+    if proj_out.bias is not None:
+        b = proj_out.bias.detach().to(acc) if b is None else b + proj_out.bias.detach().to(acc)
+    return w, b
+
+
+def _is_pointwise(m, C):
+    """`m` is a plain nn.Linear [C <- C] or a plain 1x1 nn.Conv2d of C channels (stride 1, no padding, no groups)."""
+    if type(m) is torch.nn.Linear:
+        return m.in_features == C and m.out_features == C
+    return (type(m) is torch.nn.Conv2d and m.in_channels == C and m.out_channels == C and m.kernel_size == (1, 1) and m.stride == (1, 1)
+            and m.padding == (0, 0) and m.groups == 1)
+
+
+def ff_tail_supported(x, net2, proj_out):
+    """The switch of x's width is on, `net2` is a plain nn.Linear [C <- 4 C] and `proj_out` a plain nn.Linear / 1x1 nn.Conv2d of C channels, both
+    of x's dtype on its device; x [.., C] has a multiple of 16 rows, enough of them for a persistent pass (rowgemm_worthwhile), and the
+    [rows, 4 C] input stays below what a launch addresses."""
+    C = x.shape[-1]
+    if not {320: FF_TAIL_PROJ_OUT_C320, 640: FF_TAIL_PROJ_OUT_C640}.get(C, False):
+        return False
+    return (type(net2) is torch.nn.Linear and net2.out_features == C and _is_pointwise(proj_out, C)
+            and net2.weight.dtype == x.dtype and proj_out.weight.dtype == x.dtype and net2.weight.is_cuda and proj_out.weight.is_cuda
+            and (x.numel() // C) % 16 == 0 and rowgemm_worthwhile(x, net2.in_features)
+            and bool(lib.load().sta_ff_tail_packed_w_bytes(C, net2.in_features)))
+
+
+def pack_ff_tail_weight(wcat):
+    """[W' | Wp] [C, inner + C] -> the fragment image sta_ff_tail streams through LDS (uint8 tensor); once per model."""
+    C, K = wcat.shape
+    return _pack_ff_weight(wcat, C, K - C, "sta_ff_tail_packed_w_bytes", "sta_ff_tail_pack_w",
+                           "feed-forward output + proj_out: a CUDA weight [320, 1600] or [640, 3200]")
+
+
+def ff_tail_image(owner, net2, proj_out):
+    """(packed [W' | Wp], b' in fp32 or None) of ff_tail_weights(net2, proj_out), cached on `owner` and rebuilt when any of the (up to)
+    four tensors changes."""
+    tensors = tuple(t for t in (net2.weight, net2.bias, proj_out.weight, proj_out.bias) if t is not None)
+
+    def build():
+        w, b = ff_tail_weights(net2, proj_out)
+        wp = proj_out.weight.detach()
+        return pack_ff_tail_weight(torch.cat([w, wp.reshape(wp.shape[0], wp.shape[1])], dim=1)), (None if b is None else b.float().contiguous())
+    return cached_image(owner, ("ff_tail", id(net2), id(proj_out)), tensors, build)
+
+
+def ff_tail(h, x2, x_in, w_packed, bias=None, stats_rows=None, max_workgroups=0):
+    """x_in + [h | x2] [W' | Wp]^T + b' over x2, x_in [.., C] and h [.., 4 C] (row-major at C = 640; at C = 320 in the fragment order of
+    ff_geglu_qfrag(h_frag=True)); `w_packed`, `bias` (fp32): ff_tail_image's. One pass (csrc/sta_rowstail.hip). stats_rows = rows per
+    image (a multiple of FF_TAIL_PASS_ROWS[C] that divides the rows, refused otherwise): per-image, per-channel sum / sum of squares ride
+    on the result as `_sta_stats`, as from linear_rows. `max_workgroups` > 0 caps the grid (tests)."""
+    C, inner = x2.shape[-1], h.shape[-1]
+    R = x2.numel() // C
+    if h.numel() // inner != R or x_in.numel() != x2.numel() or h.dtype != x2.dtype or x_in.dtype != x2.dtype:
+        raise ValueError("ff_tail: h %s, x2 %s and x_in %s must have the same rows and dtype" % (tuple(h.shape), tuple(x2.shape), tuple(x_in.shape)))
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != C):
+        raise ValueError("ff_tail: b' must be %d fp32 values" % C)
+    h, x2, x_in = h.contiguous(), x2.contiguous(), x_in.contiguous()
+    out = torch.empty_like(x2)
+    part, n_img, slots = None, 0, 0
+    if stats_rows:
+        n_img, slots = R // stats_rows, max(1, stats_rows // 32)
+        part = torch.empty((n_img + 1, slots, C, 2), dtype=torch.float32, device=x2.device)
+    lib.check(lib.load().sta_ff_tail(h.data_ptr(), x2.data_ptr(), w_packed.data_ptr(), _ptr(bias), x_in.data_ptr(), out.data_ptr(), _ptr(part),
+                                     int(stats_rows or 0), R, C, inner, int(max_workgroups), _DT[x2.dtype], _stream()), "sta_ff_tail")
+    if part is not None and _version(out) is not None:
+        out._sta_stats = (out._version, _finalize_stats(part, n_img, slots, C))
+    return out
+
+
+class FfTail:
+    """What SpatialTransformer hands its LAST block so that the block's feed-forward output pass also applies proj_out and the
+    transformer's residual: the module that owns the packed-weight cache, proj_out, the row view of the transformer's input and the
+    rows per image (None: no statistics wanted). The block sets `done` when its result IS the transformer's output."""
+
+    def __init__(self, owner, proj_out, x_in, stats_rows):
+        self.owner, self.proj_out, self.x_in, self.stats_rows, self.done = owner, proj_out, x_in, stats_rows, False
+
+    def run(self, x2, h, net2):
+        """The fused tail over the block's residual stream x2 and GEGLU output h (ff_tail_supported accepted them)."""
+        wp, b = ff_tail_image(self.owner, net2, self.proj_out)
+        C = x2.shape[-1]
+        sr = self.stats_rows if self.stats_rows and self.stats_rows % FF_TAIL_PASS_ROWS[C] == 0 and (x2.numel() // C) % self.stats_rows == 0 else None
+        out = ff_tail(h, x2, self.x_in, wp, b, stats_rows=sr)
+        self.done = True
+        return out
+
+
 LN_QKV = True           # level 0: norm1 + the q|k and V^T projections of attn1 as one pass (csrc/sta_lnqkv.hip); False: sta_add_layernorm + two library GEMMs
 
 

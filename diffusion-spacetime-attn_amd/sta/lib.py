@@ -27,9 +27,11 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # sta_encode.hip: canvases sampled as overlapping windows) runs the sampler step on overlap means and is built with it for the same
 # reason: no fast-math flag (its mean is a correctly rounded fp32 division). The step itself and the helpers of all three are defined
 # once, in csrc/sta_step_dev.h, which sta_inpaint.hip includes as well. sta_rows640.hip (sta_rows_c640: the level-1 Linear + residual
-# (+ LayerNorm) pass) is the C = 640 sibling of sta_rowgemm.hip's kernel and shares its headers and -ffinite-math-only.
+# (+ LayerNorm) pass) is the C = 640 sibling of sta_rowgemm.hip's kernel and shares its headers and -ffinite-math-only. sta_rowstail.hip
+# (sta_ff_tail: the feed-forward output Linear + proj_out of a SpatialTransformer as one pass) continues the feed-forward passes of
+# sta_ffgemm.hip and is built with them: the set of translation units is pinned (tests/test_abi_dtype_cpu.py).
 INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_window.hip": "sta_sampler.hip",
-                    "sta_rows640.hip": "sta_rowgemm.hip"}
+                    "sta_rows640.hip": "sta_rowgemm.hip", "sta_rowstail.hip": "sta_ffgemm.hip"}
 
 # Self-attention keeps its MFMA accumulators in VGPRs: hipcc otherwise parks them in AGPRs and brackets the
 # online-softmax rescale with v_accvgpr_read/write pairs (120 extra VALU instructions per key block in a kernel
@@ -50,7 +52,7 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 # tables to scratch to index them is refused; the names are substrings, so every instantiation — the four wrap masks of the `_ring`
 # entry points included — falls under the rule)
 # (sta_rows640.hip: an included source is named by its own file; its kernels are looked for in the assembly of the unit that includes it)
-NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",), "sta_rows640.hip": ("rows640_kernel",),
+NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",), "sta_rows640.hip": ("rows640_kernel",), "sta_rowstail.hip": ("rows_tail_kernel",),
                     "sta_sampler.hip": ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel",
                                         "sampler_step_windows_masked_kernel", "window_blend_kernel", "vae_encode_step_windows_kernel")}
 
@@ -92,6 +94,9 @@ SYMBOLS = {
     "sta_rows_c640_packed_w_bytes": (_sz, [_i, _i]),
     "sta_rows_c640_pack_w": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sta_rows_c640": (_i, [_vp] * 8 + [_l, _i, _i, _f, _i, _i, _i, _vp]),
+    "sta_ff_tail_packed_w_bytes": (_sz, [_i, _i]),
+    "sta_ff_tail_pack_w": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "sta_ff_tail": (_i, [_vp] * 7 + [_l, _l, _i, _i, _i, _i, _vp]),
     "sta_selfattn_fwd_sfrag": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _l, _l, _f, _i, _vp]),
     "sta_xattn_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "sta_xattn_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),

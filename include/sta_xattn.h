@@ -255,6 +255,26 @@ int sta_rows_c640(const void* a, const void* packed_w, const void* bias, const v
                   void* s, void* y, long R, int C, int K, float eps, int y_qfrag, int max_workgroups, int dtype, void* stream);
 
 /*
+ * The tail of a SpatialTransformer at SD-v1 level 0 / level 1 as one pass (csrc/sta_rowstail.hip): ff.net[2] + the block's last
+ * residual, then proj_out + the transformer's residual. Only additions lie between the two Linear maps, so
+ *     out = x_in + (x2 + h . W2^T + b2) . Wp^T + bp  =  x_in + [h | x2] . [W' | Wp]^T + b',    W' = Wp . W2,  b' = Wp . b2 + bp
+ * is ONE GEMM over K = inner + C: the block's result is neither written nor read back. W' and b' are the caller's (frozen weights:
+ * once per model, products in fp32 or better, W' rounded once to dtype); the pack entry point re-lays [W' | Wp] ([C][inner + C],
+ * row-major, dtype) out as the fragment image the pass streams through LDS (the bytes entry point: C * (inner + C) * 2; 0 =
+ * unsupported: C = 320 with inner = 1280, or C = 640 with inner = 2560).
+ *   h: C = 640: [R][inner] row-major; C = 320: the fragment order sta_ff_geglu_qfrag(h_frag = 1) writes.  x2, x_in, out: [R][C].
+ *   bias: b' [C] in FP32, or NULL.  R % 16 == 0, R * inner * 2 bytes < 4 GiB.
+ *   stats: NULL, or [R / rows_per_image + 1][rows_per_image / 32][C][2] fp32 — per (image, 32-row slot) the sum and the sum of squares
+ *   of the values as stored, per output channel (plain stores, fixed slots, no atomics; fold with sta_stats_finalize(slots =
+ *   rows_per_image / 32)). rows_per_image must be a multiple of the pass height (C = 320: 256 rows, C = 640: 128) that divides R.
+ *   max_workgroups: 0 = one persistent workgroup per CU; n > 0 caps the grid (tests: several passes per workgroup)
+ */
+size_t sta_ff_tail_packed_w_bytes(int C, int inner);
+int sta_ff_tail_pack_w(const void* wcat, void* packed, int C, int inner, int dtype, void* stream);
+int sta_ff_tail(const void* h, const void* x2, const void* packed_w, const float* bias, const void* x_in, void* out, float* stats,
+                long rows_per_image, long R, int C, int inner, int max_workgroups, int dtype, void* stream);
+
+/*
  * Token maps: WHERE the pixels attend, reduced to what a diagnostic needs. `attn` (attention.py:194) is a local of the
  * reference's forward; the `maps` output of sta_xattn_fwd writes it out in full ([K+2][heads][N][M] fp32 per image). This
  * entry point keeps R weighted key sums per pixel instead — readout r names a context c_r = sel_ctx[r] and a weight row:

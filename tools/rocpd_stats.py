@@ -60,8 +60,8 @@ def category(n):
         return "sta row GEMM: proj_in / proj_out + residual, skip 1x1 over the concatenation (ours)"
     if "conv3x3_nhwc_kernel" in n or "pack_conv_w" in n:
         return "sta 3x3 convolution (ours)"
-    if "to_out_ln_ofrag" in n or "ff_geglu_qfrag" in n or "ff_out_res_hfrag" in n or "add_layernorm_qfrag" in n or "ln_qkv_kernel" in n or "pack_w" in n or "rows640_kernel" in n:
-        return "sta level-0 chain: norm1+q/k/v, to_out+LN, GEGLU projection (+ level 1's), ff output, fragment LayerNorm, level 1's Linear+residual(+LN) (ours)"
+    if "to_out_ln_ofrag" in n or "ff_geglu_qfrag" in n or "ff_out_res_hfrag" in n or "add_layernorm_qfrag" in n or "ln_qkv_kernel" in n or "pack_w" in n or "rows640_kernel" in n or "rows_tail_kernel" in n:
+        return "sta level-0 chain: norm1+q/k/v, to_out+LN, GEGLU projection (+ level 1's), ff output, fragment LayerNorm, level 1's Linear+residual(+LN), ff output+proj_out (ours)"
     if "stats_finalize_kernel" in n or "gn_silu_kernel" in n or "geglu_kernel" in n or "add_layernorm_kernel" in n or "add_bias_nchw_kernel" in n or "gn_nhwc_" in n or "add_bias_rows_kernel" in n:
         return "sta trunk glue: GroupNorm/GEGLU/LayerNorm/residual (ours)"
     if "attn_fwd" in n or "attention" in n.lower():
