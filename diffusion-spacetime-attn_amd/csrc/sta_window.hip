@@ -1,5 +1,6 @@
 // sta_window.hip — wide canvases sampled as overlapping square windows (gfx950). C-ABI in include/sta_unet.h (sta_window_split /
-// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend / sta_vae_encode_step_windows, and their
+// sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend / sta_vae_encode_step_windows /
+// sta_latent_guide_windows, and their
 // `_ring` siblings for canvases that close on themselves: WRAP, a compile-time mask of the cyclic axes, 0 in the clamped entry points). #included at the end of
 // sta_sampler.hip (its flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division). The step on the overlap means
 // is step1 of sta_step_dev.h, the definition the square kernels use, with that header's V8T / F4 / load8 / store8 / round8 / StepCoef.
@@ -13,6 +14,8 @@
 // img2img on a canvas (sta_vae_encode_step_windows and its `_ring` sibling): from the encoder's output on the whole canvas to the canvas
 // state and the first call's window inputs in one launch; the per-pixel arithmetic is sta_encode_dev.h's, the definition
 // sta_vae_encode_step (sta_encode.hip) uses for square images.
+// Attention guidance on a canvas (sta_latent_guide_windows and its `_ring` sibling): the adjoint of the split applied to the window pairs'
+// gradient, then sta_latent_guide's update (sta_guide.hip, included before this file: its guide_overlap and GUIDE_MAX_PARTS) and the split.
 
 #include "sta_blend_dev.h"
 #include "sta_encode_dev.h"
@@ -275,6 +278,95 @@ __global__ __launch_bounds__(256) void vae_encode_step_windows_kernel(const T* _
   }
 }
 
+// Attention guidance on a canvas (sta_latent_guide_windows and its `_ring` sibling): latent_guide_kernel of sta_guide.hip carried to a
+// canvas. g [2 P T][C][s][s] is the gradient w.r.t. the window input pairs; the windows are window_split(x), so the gradient w.r.t. the
+// canvas state is the split's adjoint, a SUM over the covering windows and both pair rows (not the overlap mean).
+// d of one lane's 8 canvas elements: the covering windows' (g_u + g_c) in ascending w, fp32, starting from the first one's value, times
+// (1 - keep); kp == nullptr: factor 1. With one window this is guide_d.
+template <typename T, int WRAP>
+__device__ __forceinline__ void guide_windows_d(const T* __restrict__ g, const WinGrid& gr, int C, int Hc, int Wc, const CanvasPos& q,
+                                                const float* __restrict__ kp, float* d) {
+  using V8 = typename V8T<T>::type;
+  const long T_ = (long)gr.ny * gr.nx;
+  int n = 0;
+  for (int j = 0; j < gr.ny; ++j) {
+    const int dy = window_dist<(WRAP & 2) != 0>(q.y, gr.oy[j], Hc);
+    if ((unsigned)dy >= (unsigned)gr.s) continue;
+    for (int i = 0; i < gr.nx; ++i) {
+      const int dx = window_dist<(WRAP & 1) != 0>(q.x, gr.ox[i], Wc);
+      if ((unsigned)dx >= (unsigned)gr.s) continue;
+      const long at = window_at(2 * (q.row * T_ + j * gr.nx + i), C, q.c, gr.s, dy, dx);
+      const V8 gu = *(const V8*)(g + at), gc = *(const V8*)(g + at + (long)C * gr.s * gr.s);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float sum = (float)gu[k] + (float)gc[k];
+        d[k] = n ? d[k] + sum : sum;
+      }
+      ++n;
+    }
+  }
+  if (kp) {
+    float k8[8];
+    load8(kp, k8);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = d[k] * (1.0f - k8[k]);
+  }
+}
+
+// One launch, no atomics, no hand-off between workgroups: a canvas is shared by `parts` workgroups and EVERY one of them reduces the whole
+// canvas's sum of d^2 itself in the same fixed order (lane t takes canvas vectors t, t + 256, ..., the 8 squares of each in element order,
+// then latent_guide_kernel's LDS tree), so all of them hold the same bits of rms_p; each then forms d again for its own slice (the
+// gradient is served by L2 the second time), writes x_out and scatters the rounded vector to the covering windows' pairs. One writer per
+// output element; a canvas's outputs depend on that canvas's inputs alone.
+// canvec = C Hc Wc / 8 vectors per canvas; count [P]: the elements that receive gradient (the host's), rms_p = sqrt(sum d^2 / count[p]).
+template <typename T, int WRAP>
+__global__ __launch_bounds__(256) void latent_guide_windows_kernel(const T* __restrict__ g, const float* __restrict__ x,
+                                                                   const float* __restrict__ keep, const float* __restrict__ step,
+                                                                   const float* __restrict__ count, float* __restrict__ x_out,
+                                                                   T* __restrict__ xin, float* __restrict__ stats, long canvec, int C, int Hc,
+                                                                   int Wc, WinGrid gr, int parts, long chunk, int normalize, float inv_scale) {
+  __shared__ float red[256];
+  const long p = blockIdx.x / parts;
+  const int part = (int)(blockIdx.x - p * parts);
+  const int tid = threadIdx.x;
+  const int wvec = Wc / 8;
+
+  float acc = 0.f;
+  for (long v = tid; v < canvec; v += 256) {
+    const CanvasPos q = canvas_pos(p * canvec + v, C, Hc, wvec);
+    float d[8] = {};
+    guide_windows_d<T, WRAP>(g, gr, C, Hc, Wc, q, keep ? keep + mask_at(q, Hc, Wc) : nullptr, d);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc += d[k] * d[k];
+  }
+  red[tid] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  const float rms = sqrtf(red[0] / count[p]);
+  const bool live = (__float_as_uint(rms) & 0x7f800000u) != 0x7f800000u && rms > 0.f;      // finite (neither Inf nor NaN) and positive
+  const float s = !live ? 0.f : normalize ? step[p] / rms : step[p] * inv_scale;
+
+  const long end = (part + 1) * chunk < canvec ? (part + 1) * chunk : canvec;
+  for (long v = part * chunk + tid; v < end; v += 256) {
+    const CanvasPos q = canvas_pos(p * canvec + v, C, Hc, wvec);
+    float xv[8];
+    load8(x + 8 * (p * canvec + v), xv);
+    if (live) {
+      float d[8] = {};
+      guide_windows_d<T, WRAP>(g, gr, C, Hc, Wc, q, keep ? keep + mask_at(q, Hc, Wc) : nullptr, d);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) xv[k] = xv[k] - s * d[k];
+    }
+    store8(x_out + 8 * (p * canvec + v), xv);
+    if (xin) scatter<T, WRAP>(xin, gr, p, 0, 1, C, Hc, Wc, q, round8<T>(xv));
+  }
+  if (stats && part == 0 && tid == 0) stats[p] = rms;
+}
+
 // offsets along one axis of length L: 0 first, multiples of 8, ascending, no gap (step <= s), the last window ends at L
 int window_axis_ok(const char* what, const char* axis, int n, const int* o, int s, int L) {
   if (n < 1 || n > STA_MAX_WINDOW_OFFSETS) return sta_fail(STA_E_ARG, "%s: n%s=%d (need 1 .. %d offsets)", what, axis, n, STA_MAX_WINDOW_OFFSETS);
@@ -456,9 +548,60 @@ int encode_step_windows(const char* what, const void* h, const float* quant_w, c
   });
 }
 
+int latent_guide_windows(const char* what, const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out,
+                         void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                         int normalize, float inv_scale, int dtype, void* stream) {
+  g_sta_err[0] = 0;
+  if (!g || !x || !step || !count || !x_out) return sta_fail(STA_E_ARG, "%s: null pointer", what);
+  WinGrid gr;
+  if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &gr)) return rc;
+  if (!sta_aligned16(g) || !sta_aligned16(x) || !sta_aligned16(keep) || !sta_aligned16(x_out) || !sta_aligned16(xin) || ((uintptr_t)step & 3) ||
+      ((uintptr_t)count & 3) || ((uintptr_t)stats & 3))
+    return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned (step, count and stats: 4-byte)", what);
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_ARG, "%s: dtype %d (STA_BF16 or STA_F16)", what, dtype);
+  const size_t plane = (size_t)Hc * Wc, f32 = (size_t)P * C * plane * 4, pairs = (size_t)2 * P * ny * nx * C * s * s * 2;
+  const void* ins[] = {g, x, keep, step, count};
+  const size_t in_bytes[] = {pairs, f32, (size_t)P * plane * 4, (size_t)P * 4, (size_t)P * 4};
+  const void* outs[] = {x_out, xin, stats};
+  const size_t out_bytes[] = {f32, pairs, (size_t)P * 4};
+  for (int o = 0; o < 3; ++o) {
+    for (int i = 0; i < 5; ++i)
+      if (guide_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) return sta_fail(STA_E_ARG, "%s: an output aliases an input", what);
+    for (int q = o + 1; q < 3; ++q)
+      if (guide_overlap(outs[o], out_bytes[o], outs[q], out_bytes[q])) return sta_fail(STA_E_ARG, "%s: two outputs alias each other", what);
+  }
+  const long canvec = (long)C * Hc * (Wc / 8);
+  long parts = (canvec + 255) / 256;                       // sta_latent_guide's rule
+  if (parts > GUIDE_MAX_PARTS) parts = GUIDE_MAX_PARTS;
+  const long chunk = (canvec + parts - 1) / parts;
+  if (P * parts > 0x7fffffffL) return sta_fail(STA_E_UNSUP, "%s: P=%ld canvases need more than 2^31 - 1 workgroups", what, P);
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return by_wrap(wrap, [&](auto w) {
+      return sta_launch<latent_guide_windows_kernel<T, decltype(w)::value>>(what, dim3((unsigned)(P * parts)), dim3(256), 0, (hipStream_t)stream,
+                                                                            (const T*)g, x, keep, step, count, x_out, (T*)xin, stats, canvec, C,
+                                                                            Hc, Wc, gr, (int)parts, chunk, normalize, inv_scale);
+    });
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int sta_latent_guide_windows(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out, void* xin,
+                             float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int normalize,
+                             float inv_scale, int dtype, void* stream) {
+  return latent_guide_windows("latent_guide_windows", g, x, keep, step, count, x_out, xin, stats, P, C, Hc, Wc, ny, nx, oy, ox, s, 0, normalize,
+                              inv_scale, dtype, stream);
+}
+
+int sta_latent_guide_windows_ring(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out,
+                                  void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                                  int wrap, int normalize, float inv_scale, int dtype, void* stream) {
+  return latent_guide_windows("latent_guide_windows_ring", g, x, keep, step, count, x_out, xin, stats, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap,
+                              normalize, inv_scale, dtype, stream);
+}
 
 int sta_vae_encode_step_windows(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
                                 float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,

@@ -215,8 +215,12 @@ class _AttnInject:
 class PLMSSampler(object):
     def __init__(self, model, schedule="linear", loss_model=None, opt_epochs=3, lr=0.005, weight_init=5.0,
                  local_loss_weight=5.0, use_graph=True, save_images=True, outdir="result_outputs/", loss_scale=None, keep_calls=None,
-                 batched_loss=True, attn_capture=None, attn_loss=None, attn_loss_weight=1.0, latent_guidance=None, **kwargs):
-        """`latent_guidance`: a sta.guidance.AttnGuidance. In every trajectory that runs WITHOUT autograd (the fixed-weight one, the kept
+                 batched_loss=True, attn_capture=None, attn_loss=None, attn_loss_weight=1.0, latent_guidance=None, canvas_guidance=None, **kwargs):
+        """`canvas_guidance`: a sta.guidance.CanvasGuidance, the latent guidance of CANVAS trajectories (sample_canvas, inpaint_canvas,
+        DDIMSampler.decode_canvas): the first `steps` UNet calls of a canvas are each preceded by its updates on the canvas state (eager
+        evaluations of the 2 P T window rows; the ordinary calls run as before); `last_guidance` as below. `sample` / `sample_batch` never
+        look at it, and a canvas never looks at `latent_guidance` (which stays refused there). None: nothing changes.
+        `latent_guidance`: a sta.guidance.AttnGuidance. In every trajectory that runs WITHOUT autograd (the fixed-weight one, the kept
         last epoch) its first `steps` UNet calls are each preceded by its latent updates (eager evaluations; the ordinary calls run as
         before, graph replay included); what they saw is left in `last_guidance`. Tracked epochs are never guided. None: nothing changes.
         `attn_loss`: a sta.attnloss.AttnLayoutLoss. Tracked epochs then minimise [the fidelity loss if `loss_model` is given] +
@@ -249,6 +253,7 @@ class PLMSSampler(object):
         self.attn_loss, self.attn_loss_weight = attn_loss, float(attn_loss_weight)
         self._attn_inject = None          # _AttnInject while a tracked epoch with an attention loss runs
         self.latent_guidance, self.last_guidance = latent_guidance, None
+        self.canvas_guidance = canvas_guidance
         self._graphs = None
         self._call_key = None             # (latent shape, object count) of the trajectory being sampled: keys the measured activation size
 
@@ -336,7 +341,8 @@ class PLMSSampler(object):
         windows run over the seam (sta.canvas.window_grid's ring rules) and the decode sees `canvas_wrap_margin` latent cells of the
         other side on each wrapped border (`_decode_canvas`).
         Fixed weights only. ValueError before any UNet call for opt_epochs > 1 (the loss front end takes square images:
-        sta.clip.check_view_shapes), an attached attn_capture, attn_loss or latent_guidance, mask= / x0= (inpainting) and a non-zero
+        sta.clip.check_view_shapes), an attached attn_capture, attn_loss or latent_guidance (layout guidance on a canvas is the sampler's
+        `canvas_guidance`, a sta.guidance.CanvasGuidance), mask= / x0= (inpainting) and a non-zero
         `_start` (img2img decodes): none of them is defined on a canvas by this method (inpainting: `inpaint_canvas` of the step-kernel
         samplers)."""
         if mask is not None or x0 is not None:
@@ -441,7 +447,10 @@ class PLMSSampler(object):
         boxes = [wc for bx in bboxs_curr for wc in _cv.window_centres(bx, grid)]
         inner = self._make_eps_fn(rep(cond), rep(uncond.expand(P, -1, -1)), scale, boxes, text_index, graph, img.new_empty((P * T, 0)),
                                   raw=True)
-        return grid, lambda xin, t, coef: inner(xin, rep(t), rep(coef))
+        def unet(xin, t, coef):
+            return inner(xin, rep(t), rep(coef))
+        unet.eager_call = lambda xin, t, coef: inner.eager_call(xin, rep(t), rep(coef))      # sta.guidance.CanvasGuidance: never the graph
+        return grid, unet
 
     def _canvas_eps_fn(self, cond, uncond, scale, bboxs_curr, text_index, graph, img):
         """eps(x, t, coef) of a canvas state x [P, C, Hc, Wc] with classifier-free guidance: split into windows, one UNet call, overlap
@@ -457,6 +466,7 @@ class PLMSSampler(object):
             out = out.reshape(P, 2, *out.shape[1:])
             e_u, e_c = out[:, 0], out[:, 1]
             return e_u + scale * (e_c - e_u)
+        eps.eager_call = unet.eager_call
         return eps
 
     # --------------------------------------------------------------------------------------------------
@@ -507,6 +517,8 @@ class PLMSSampler(object):
             lg = self.latent_guidance if not track else None
             if lg is not None:
                 lg.begin(boxes, texts=texts, names=names)
+            elif self._canvas is not None and self.canvas_guidance is not None:      # a canvas (never tracked; latent_guidance is refused there)
+                lg = self.canvas_guidance.begin(boxes, texts=texts, names=names, grid=self._canvas)
             al = self.attn_loss if track else None
             decode = not track or self.clip_loss_model is not None or al is None      # tracked with the attention loss alone: no decode
             while True:
@@ -658,7 +670,7 @@ class PLMSSampler(object):
             eps_fn = self._canvas_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img)
         else:
             eps_fn = self._make_eps_fn(cond, uncond, scale, bboxs_curr, text_index, graph, img, call_recompute, keep_last=keep, n_calls=S + 1)
-        guide = self._guide(eps_fn)
+        guide = self._guide(eps_fn) if self._canvas is None else self._canvas_guide(eps_fn)
         old_eps = []
         for i, step in enumerate(time_range):
             index = S - i - 1
@@ -748,6 +760,14 @@ class PLMSSampler(object):
         if lg is None or torch.is_grad_enabled() or not lg.ready:
             return None
         return lg.bind(eps_fn.eager_call)
+
+    def _canvas_guide(self, unet):
+        """`_guide` for a canvas trajectory: its CanvasGuidance bound to the eager call on the window rows (`unet.eager_call`, read only
+        when there is something to guide), or None."""
+        cg = self.canvas_guidance
+        if cg is None or torch.is_grad_enabled() or not cg.ready:
+            return None
+        return cg.bind(unet.eager_call)
 
     def _x_prev(self, x, e_t, index):
         """DDIM step with sigma = 0 (:321-338); the tables live on the host as Python floats."""
@@ -982,7 +1002,9 @@ class SolverSamplerBase(PLMSSampler):
         window_split instead (three launches; the means are then rounded to the UNet's type before the step).
         Inpainting (inpaint_canvas: `_inpaint` set): sta_window_blend re-noises the kept region and writes the first window inputs, and
         the launch after calls 0 .. S - 2 is sta_sampler_step_windows_masked, which blends for the NEXT call; the last call takes the
-        plain step. Unfused: latent_blend + window_split, then window_fuse + solver_step_masked + window_split."""
+        plain step. Unfused: latent_blend + window_split, then window_fuse + solver_step_masked + window_split.
+        `canvas_guidance`: the first `steps` calls (counted from `_start`) are each preceded by its updates of x and xin, one
+        sta_latent_guide_windows launch per update (sta.guidance.CanvasGuidance)."""
         from sta import canvas as _cv
         from sta import solver
         grid, unet = self._window_unet(cond, uncond, scale, bboxs_curr, text_index, graph, img)
@@ -998,9 +1020,15 @@ class SolverSamplerBase(PLMSSampler):
             xin = _cv.window_split(x, grid, wdtype)
         else:
             xin = self._xin0 if self._xin0 is not None else _cv.window_split(x, grid, wdtype)
+        guide = self._canvas_guide(unet)
         for i in range(start, S):
             t_val = float(time_range[i]) if self.t_dtype.is_floating_point else int(time_range[i])
-            out = unet(xin, torch.full((P,), t_val, device=device, dtype=self.t_dtype), W[..., i])
+            t = torch.full((P,), t_val, device=device, dtype=self.t_dtype)
+            if guide is not None and i - start < guide.steps:
+                # after the blend of a masked trajectory (the kept region is not guided), counted from `_start`; m_prev stays as it is
+                x, xin = guide.update(x, xin, t, W[..., i], i - start, float(self.tables["alpha_t"][i]) ** 2,
+                                      self._inpaint["keep"] if masked else None)
+            out = unet(xin, t, W[..., i])
             c = self._coef(i, scale)
             noise = self._noise(i - start, x) if c.c_n else None   # the eta draw of call i, then the blend draw of call i + 1
             bl = self._blend(i + 1, x) if masked and i + 1 < S else None       # no blend after the last step

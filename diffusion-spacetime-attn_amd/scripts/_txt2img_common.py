@@ -9,7 +9,8 @@ ignores, accepted for compatibility). Added: --layout (JSON replacing the layout
 --attn_guidance ETA / --attn_guidance_steps / --attn_guidance_iters (attention-guided latent updates, sta.guidance; shared with
 img2img.py and inpaint.py through add_guidance_arguments / check_guidance_option / make_guidance / report_guidance),
 --canvas HxW / --canvas_stride PX (a wide or tall canvas sampled as overlapping --H x --W windows, sta.canvas; the layout's centres are
-then normalised to the canvas; fixed blend weights only), --canvas_wrap x|y|xy (the canvas closes on itself along those axes: a 360 degree
+then normalised to the canvas; fixed blend weights only; --canvas_guidance ETA: attention guidance on the canvas, sta.guidance.
+CanvasGuidance), --canvas_wrap x|y|xy (the canvas closes on itself along those axes: a 360 degree
 panorama or a tileable image).
 With torch.distributed.run the prompts are sharded round-robin over the ranks (one GPU each).
 """
@@ -94,7 +95,7 @@ def build_parser(default_dataset):
                    help="sample a canvas of H x W pixels as overlapping --H x --W windows (which must be square) in one CFG batch per UNet "
                         "call, averaged where they overlap (sta.canvas); a multiple of 8 x --f and at least the window; the centres of "
                         "--layout are then normalised to the canvas; fixed blend weights only (--opt_epochs 0 or 1), no --attn_maps / "
-                        "--attn_loss / --attn_guidance")
+                        "--attn_loss / --attn_guidance (layout guidance on a canvas: --canvas_guidance)")
     p.add_argument("--canvas_stride", type=int, default=None, metavar="PX",
                    help="distance between neighbouring windows of --canvas in pixels: a multiple of 8 x --f, at most the window "
                         "(default: half the window)")
@@ -112,6 +113,11 @@ def add_guidance_arguments(p, attn_res=False):
                    help="step the latent down the gradient of the attention-layout energy (sta.guidance) before each of the first "
                         "--attn_guidance_steps UNet calls of the kept trajectory: x <- x - ETA (1 - alphas_cumprod_t) g / rms(g), read at "
                         "--attn_res on the encoder side of the UNet; needs no epochs and no CLIP; prompts without objects are not guided")
+    p.add_argument("--canvas_guidance", type=_positive_float, default=None, metavar="ETA",
+                   help="--attn_guidance on a --canvas (sta.guidance.CanvasGuidance): the energy is read per window, its gradient goes back "
+                        "to the canvas latent through the windows' split (one sta_latent_guide_windows launch per update) and the part of "
+                        "the canvas that receives gradient moves by ETA (1 - alphas_cumprod_t) in rms; reuses --attn_guidance_steps / "
+                        "--attn_guidance_iters / --attn_res (a level of the WINDOW); needs --canvas")
     p.add_argument("--attn_guidance_steps", type=_non_negative_int, default=10, metavar="N", help="guided UNet calls per trajectory")
     p.add_argument("--attn_guidance_iters", type=_positive_int, default=1, metavar="N", help="updates before each guided call")
     if attn_res:
@@ -185,11 +191,22 @@ def make_guidance(opt, model):
                                  iters=opt.attn_guidance_iters, tokenize=None if tok is None else attnmaps.content_tokenizer(tok))
 
 
+def make_canvas_guidance(opt, model):
+    """The sta.guidance.CanvasGuidance of --canvas_guidance, or None."""
+    if getattr(opt, "canvas_guidance", None) is None:
+        return None
+    from sta import attnmaps, guidance
+    tok = getattr(model.cond_stage_model, "tokenizer", None)
+    return guidance.CanvasGuidance(model.model.diffusion_model, resolution=opt.attn_res, scale=opt.canvas_guidance,
+                                   steps=opt.attn_guidance_steps, iters=opt.attn_guidance_iters,
+                                   tokenize=None if tok is None else attnmaps.content_tokenizer(tok))
+
+
 def report_guidance(sampler, indices, tag=""):
     """After sampling: per prompt the energy before the first and before the last update (with one update per call the last figure is
     the energy the last guided call started from), and the skipped updates."""
     res = getattr(sampler, "last_guidance", None)
-    if getattr(sampler, "latent_guidance", None) is None:
+    if getattr(sampler, "latent_guidance", None) is None and getattr(sampler, "canvas_guidance", None) is None:
         return
     if res is None:
         print("%sprompts %s: no objects (or no guided call), not guided" % (tag, list(indices)))
@@ -207,6 +224,8 @@ def canvas_grid(opt):
             raise SystemExit("--canvas_stride %d needs --canvas HxW" % opt.canvas_stride)
         if wrap:
             raise SystemExit("--canvas_wrap %s needs --canvas HxW" % wrap)
+        if getattr(opt, "canvas_guidance", None) is not None:
+            raise SystemExit("--canvas_guidance %s needs --canvas HxW (a square image is guided with --attn_guidance)" % opt.canvas_guidance)
         return None
     parts = opt.canvas.lower().split("x")
     if len(parts) != 2 or not all(v.isdigit() for v in parts):
@@ -225,6 +244,11 @@ def canvas_grid(opt):
     for flag, on in (("--attn_maps", opt.attn_maps), ("--attn_loss", opt.attn_loss is not None), ("--attn_guidance", opt.attn_guidance is not None)):
         if on:
             raise SystemExit("%s reads one square image's attention maps and is not defined on a --canvas" % flag)
+    if getattr(opt, "canvas_guidance", None) is not None:
+        levels = [opt.H // opt.f // d for d in (1, 2, 4, 8)]
+        if opt.attn_res not in levels:
+            raise SystemExit("--attn_res %d: no transformer level of a %d x %d window has that side (levels: %s)"
+                             % (opt.attn_res, opt.H, opt.H, ", ".join(str(v) for v in levels)))
     from sta import canvas
     try:
         return canvas.window_grid(Hpx // opt.f, Wpx // opt.f, opt.H // opt.f, stride // opt.f, wrap)
@@ -380,7 +404,7 @@ def run(kind, default_dataset):
         attn_loss = attnloss.AttnLayoutLoss(model.model.diffusion_model, resolution=opt.attn_res, tokenize=tokenize)
     sampler = sampler_class(sampler_name)(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, attn_capture=capture,
                                           attn_loss=attn_loss, attn_loss_weight=opt.attn_loss if attn_loss is not None else 1.0,
-                                          latent_guidance=make_guidance(opt, model))
+                                          latent_guidance=make_guidance(opt, model), canvas_guidance=make_canvas_guidance(opt, model))
     os.makedirs(opt.outdir, exist_ok=True)
 
     seed = 1                                                            # txt2img-gpt.py:304
@@ -442,6 +466,7 @@ def run(kind, default_dataset):
                               local_conditionings=[c[2] for c in conds], curr_texts=[p for _, p, _ in group],
                               x_T=x1.expand(len(group), -1, -1, -1).contiguous(), unconditional_guidance_scale=opt.scale, eta=eta, seed=seed,
                               prompt_indices=[i for i, _, _ in group], channels=opt.C, wrap=grid.wrap)
+        report_guidance(sampler, [i for i, _, _ in group], "[rank %d] " % rank)
 
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}) for i, p in mine]
     if grid is not None:

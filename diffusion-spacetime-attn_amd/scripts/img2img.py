@@ -16,7 +16,8 @@ as overlapping --window x --window windows (sta.canvas; the flags mean what they
 --canvas 1024x1024 --strength 0.4 is a tiled upscale-and-refine pass. The whole canvas is encoded once (on a wrapped canvas with circular
 padding, so the encoder sees across the seam), one sta_vae_encode_step_windows launch writes the canvas state and the first call's window
 inputs, and DDIMSampler.decode_canvas runs the last t_enc calls. The layout's centres are normalised to the canvas; prompts with the same
-object count run as P canvases of one batch (--batch_prompts); the draws below are canvas-shaped. Refused with --canvas before a model is
+object count run as P canvases of one batch (--batch_prompts); the draws below are canvas-shaped. --canvas_guidance ETA guides the decode
+from its first call (sta.guidance.CanvasGuidance; needs --canvas). Refused with --canvas before a model is
 built: --opt_epochs > 1, --attn_guidance, a --window that is no multiple of 8 x --f, and every refusal of the txt2img scripts' canvas
 grid. Not claimed: image quality or seam visibility with real weights; the VAE's mid-block attention is global over the canvas, O((Hc
 Wc)^2) memory in its chunked form, for the encoder as for the one decode; a disc keeps its radius of 0.2 window sides, so objects shrink
@@ -89,7 +90,8 @@ def add_canvas_arguments(p):
     p.add_argument("--canvas", type=str, default=None, metavar="HxW",
                    help="img2img on a canvas of H x W pixels, decoded as overlapping --window x --window windows in one CFG batch per UNet "
                         "call (sta.canvas); the init image, of any size, is resized to the canvas (LANCZOS): a smaller picture is upscaled "
-                        "and refined window by window; fixed blend weights only (--opt_epochs 0 or 1), no --attn_guidance")
+                        "and refined window by window; fixed blend weights only (--opt_epochs 0 or 1), no --attn_guidance (on a canvas: "
+                        "--canvas_guidance)")
     p.add_argument("--canvas_stride", type=int, default=None, metavar="PX",
                    help="distance between neighbouring windows of --canvas in pixels (default: half the window)")
     p.add_argument("--canvas_wrap", type=str, default=None, choices=("x", "y", "xy"),
@@ -101,7 +103,8 @@ def canvas_grid(opt):
     """The sta.canvas.Grid of --canvas / --canvas_stride / --canvas_wrap / --window (the rules of the txt2img scripts,
     _txt2img_common.canvas_grid, with --window as their --H = --W), or None without --canvas; every refusal that needs no GPU."""
     view = argparse.Namespace(canvas=opt.canvas, canvas_stride=opt.canvas_stride, canvas_wrap=opt.canvas_wrap, H=opt.window, W=opt.window,
-                              f=opt.f, opt_epochs=opt.opt_epochs, attn_maps=False, attn_loss=None, attn_guidance=opt.attn_guidance)
+                              f=opt.f, opt_epochs=opt.opt_epochs, attn_maps=False, attn_loss=None, attn_guidance=opt.attn_guidance,
+                              canvas_guidance=opt.canvas_guidance, attn_res=opt.attn_res)
     try:
         return _txt2img_common.canvas_grid(view)
     except SystemExit as e:
@@ -246,7 +249,8 @@ def main(argv=None):
     vae = model.first_stage_model
     vae.encoder.to(memory_format=torch.channels_last)            # NHWC encoder: its convolutions on the HIP kernels
     sampler = DDIMSampler(model, opt_epochs=opt.opt_epochs, loss_model=loss_model, outdir=opt.outdir, save_images=not opt.skip_save,
-                          latent_guidance=_txt2img_common.make_guidance(opt, model))
+                          latent_guidance=_txt2img_common.make_guidance(opt, model),
+                          canvas_guidance=_txt2img_common.make_canvas_guidance(opt, model))
     sampler.make_schedule(opt.ddim_steps, ddim_eta=opt.ddim_eta, verbose=False)
     os.makedirs(opt.outdir, exist_ok=True)
     shape = (1, opt.C, size // opt.f, size // opt.f) if grid is None else (1, opt.C, grid.Hc, grid.Wc)

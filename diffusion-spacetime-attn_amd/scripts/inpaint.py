@@ -53,6 +53,9 @@ def check_options(opt):
         raise SystemExit("--n_samples must be 1 (the blocks reshape to the CFG batch of 2, attention.py:282)")
     if not 0.0 < opt.strength <= 1.0:
         raise SystemExit("--strength must be in (0, 1]")
+    if opt.canvas_guidance is not None:
+        raise SystemExit("--canvas_guidance %s needs --canvas HxW: inpaint.py repaints square images (--attn_guidance), a canvas is "
+                         "outpaint.py's" % opt.canvas_guidance)
     if (opt.mask is None) == (opt.mask_from_layout is None):
         raise SystemExit("exactly one of --mask and --mask_from_layout must be given")
     if opt.mask_from_layout is not None and not opt.mask_from_layout > 0.0:

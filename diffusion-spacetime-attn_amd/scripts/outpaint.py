@@ -16,6 +16,9 @@ The flags of scripts/img2img.py (same parser, same seed discipline), plus
 cells) and keep_px the same in pixels. The centres of --layout are normalised to the canvas. DDIM by default, DPM-Solver++ with
 --dpm_solver. The output is the composite canvas image: the picture's 8-bit values exactly where keep_px == 1, one decode of the whole
 canvas elsewhere. Fixed blend weights (--opt_epochs 0 or 1; the default here is 0).
+  --canvas_guidance ETA    attention guidance on the canvas (sta.guidance.CanvasGuidance; --attn_guidance_steps / --attn_guidance_iters /
+                           --attn_res as in the txt2img scripts): the objects of the new area are steered into their discs, the kept
+                           picture is not guided.
 
 Refused before a model is built: --plms, --strength != 1 (the new area starts from noise), --opt_epochs > 1, --attn_maps / --attn_loss /
 --attn_guidance, --n_samples != 1, --place or --seam that is not a multiple of --f, a footprint outside the canvas, a seam that leaves
@@ -131,7 +134,8 @@ def main(argv=None):
     vae = model.first_stage_model
     vae.encoder.to(memory_format=torch.channels_last)            # NHWC encoder: its convolutions on the HIP kernels
     cls = DPMSolverSampler if opt.dpm_solver else DDIMSampler
-    sampler = cls(model, opt_epochs=opt.opt_epochs, loss_model=None, outdir=opt.outdir, save_images=not opt.skip_save)
+    sampler = cls(model, opt_epochs=opt.opt_epochs, loss_model=None, outdir=opt.outdir, save_images=not opt.skip_save,
+                  canvas_guidance=_txt2img_common.make_canvas_guidance(opt, model))
     encoder = sampler                                            # the fused encode step lives on the DDIM sampler (its tables)
     if opt.dpm_solver:
         encoder = DDIMSampler(model, opt_epochs=0, save_images=False)
@@ -178,6 +182,7 @@ def main(argv=None):
                                object_names=[list(l.keys()) for _, _, l, _ in group], local_conditionings=[c[2] for c in conds],
                                curr_texts=[p for _, p, _, _ in group], x_T=x_T, unconditional_guidance_scale=opt.scale, eta=opt.ddim_eta,
                                seed=opt.seed, prompt_indices=[i for i, _, _, _ in group], channels=opt.C, wrap=grid.wrap)
+        _txt2img_common.report_guidance(sampler, [i for i, _, _, _ in group])
 
     by_k = {}
     for it in items:

@@ -81,8 +81,11 @@ class AttnLayoutLoss:
         """Explicit readouts for the following trajectories (see AttnCapture.set_readouts)."""
         self._explicit = (list(sel_ctx), torch.as_tensor(w, dtype=torch.float32), objects, found)
 
-    def begin(self, centres, texts=None, names=None, n_calls=1):
-        """Start a new trajectory of `n_calls` UNet calls (the k over which the per-call energies are averaged)."""
+    def begin(self, centres, texts=None, names=None, n_calls=1, disc_required=False):
+        """Start a new trajectory of `n_calls` UNet calls (the k over which the per-call energies are averaged).
+        disc_required (default False: today's rule): a readout also needs a disc with at least one set pixel at the recording resolution
+        in its image — on a canvas an object lies outside most windows, and a window image without a valid readout gives exactly 0 and
+        no gradient (layout_energy's rule)."""
         helper = _am.AttnCapture(None, self.resolution, tokenize=self.tokenize, M=self.M)
         helper._explicit = self._explicit
         helper.begin(centres, texts=texts, names=names)                 # the same readouts, objects and refusals as the capture
@@ -102,7 +105,7 @@ class AttnLayoutLoss:
             for r, o in enumerate(self.objects):
                 if o >= 0 and masks is not None:
                     disc[i, r] = masks[o]
-                    valid[i, r] = bool(found[i, r])
+                    valid[i, r] = bool(found[i, r]) and (not disc_required or bool(masks[o].any()))
         self._disc, self._valid = disc, valid
         return self
 

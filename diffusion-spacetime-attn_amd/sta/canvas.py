@@ -33,6 +33,11 @@ dispatchers call the `_ring` siblings of the five entry points; a grid without w
 img2img on a canvas (`encode_step_windows`, restatement `encode_step_windows_reference`): from the VAE encoder's output on the whole canvas
 to the canvas state noised to the decode's start and the first call's window input pairs, one sta_vae_encode_step_windows launch
 (sta_vae_encode_step and sta_window_split in one); DDIMSampler.encode_step_canvas / decode_canvas are its users.
+
+Attention guidance on a canvas (`latent_guide_windows`, restatement `guide_windows_reference`, `guide_count`): the gradient of the
+attention-layout energy w.r.t. the window input pairs goes back to the canvas state through the split's adjoint (a sum over the covering
+windows), the state steps as in sta.guidance and the next window inputs are written, one sta_latent_guide_windows launch;
+sta.guidance.CanvasGuidance is its user.
 """
 import ctypes
 from collections import namedtuple
@@ -220,6 +225,53 @@ def encode_step_windows_reference(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, d
     return x, (z0 if want_z0 else None), (window_split_reference(x, grid, dtype or h.dtype) if want_xin else None)
 
 
+def guide_count(grid, contributing, C):
+    """The `count` of latent_guide_windows: per canvas the number of canvas elements (the C channels included) covered by at least one
+    CONTRIBUTING window. contributing [P, T] bool (window order) -> [P] float32. All windows contributing: C Hc Wc; none: 0."""
+    contributing = torch.as_tensor(contributing, dtype=torch.bool).reshape(-1, grid.T)
+    out = torch.zeros(contributing.shape[0], dtype=torch.float32)
+    for p in range(contributing.shape[0]):
+        hit = torch.zeros((grid.Hc, grid.Wc), dtype=torch.bool)
+        for w, (y0, x0) in enumerate(windows(grid)):
+            if contributing[p, w]:
+                hit[_region(grid, y0, x0)] = True
+        out[p] = float(C * int(hit.sum()))
+    return out
+
+
+def guide_windows_reference(g, x, step, count, grid, keep=None, normalize=True, inv_scale=1.0):
+    """The attention-guidance update on a canvas, restated in torch, arithmetic in x's dtype (float64 x: the oracle) -> (x_out, rms [P]).
+    g [2 P T, C, s, s]: the gradient w.r.t. the window input pairs; x [P, C, Hc, Wc]; step, count [P] (or numbers); keep [P, 1, Hc, Wc]
+    or None. The windows are window_split(x), so the gradient w.r.t. x is the split's adjoint: per canvas element the covering windows'
+    (g_u + g_c) summed in ascending w, starting from the first one's value (a sum, not the overlap mean), times (1 - keep);
+    rms_p = sqrt(sum d^2 / count[p]), s_p = step_p / rms_p (normalize) or step_p inv_scale, x_out = x - s_p d where rms_p is finite and
+    > 0, else x itself. With one window this is sta.guidance.guide_reference."""
+    s = grid.s
+    if x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
+        raise ValueError("guide_windows: the state %s is not a [P, C, %d, %d] canvas" % (tuple(x.shape), grid.Hc, grid.Wc))
+    P, C = x.shape[0], x.shape[1]
+    if tuple(g.shape) != (2 * P * grid.T, C, s, s):
+        raise ValueError("g %s must be the gradient of the window pair batch [%d, %d, %d, %d] of x %s" % (tuple(g.shape), 2 * P * grid.T, C, s, s, tuple(x.shape)))
+    gw = g.detach().reshape(P, grid.T, 2, C, s, s).to(x.dtype)
+    d = torch.zeros_like(x)
+    seen = torch.zeros((grid.Hc, grid.Wc), dtype=torch.bool, device=x.device)
+    for w, (y0, x0) in enumerate(windows(grid)):
+        v = gw[:, w, 0] + gw[:, w, 1]
+        at = _region(grid, y0, x0, x.device)
+        region = d[(Ellipsis,) + at]
+        d[(Ellipsis,) + at] = torch.where(seen[at], region + v, v)          # the first covering window's value starts the sum
+        seen[at] = True
+    if keep is not None:
+        d = d * (1.0 - keep.to(x.device, x.dtype))
+    as_p = lambda v: torch.as_tensor(v, dtype=x.dtype, device=x.device).reshape(-1).expand(P)
+    rms = (d.reshape(P, -1).square().sum(1) / as_p(count)).sqrt()
+    live = torch.isfinite(rms) & (rms > 0)
+    step = as_p(step)
+    sc = torch.where(live, step / rms if normalize else step * inv_scale, torch.zeros_like(rms))
+    b = lambda v: v.reshape(-1, 1, 1, 1)
+    return torch.where(b(live), x - b(sc) * d, x), rms
+
+
 # ---------------------------------------------------------------------------------------------------- HIP entry points
 _TABLES = {}
 
@@ -354,6 +406,40 @@ def window_blend(x, bl, grid, dtype=None, want_xin=False):
     lib.check(fn(x.data_ptr(), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(), out.data_ptr(), _ptr(xin), P, C, grid.Hc, grid.Wc,
                  *_grid_args(grid), bl.q_a, bl.q_b, _DT[dtype], _stream(x)), name)
     return out, xin
+
+
+def latent_guide_windows(g, x, step, count, grid, keep=None, normalize=True, inv_scale=1.0, dtype=None, want_xin=False, want_stats=True):
+    """One attention-guidance update of a canvas state -> (x_out, xin or None, rms [P] or None): g [2 P T, C, s, s] the gradient w.r.t.
+    the window input pairs, x [P, C, Hc, Wc] float32, step / count [P] (or numbers), keep [P, 1, Hc, Wc] or None. CUDA: ONE
+    sta_latent_guide_windows launch (the `_ring` sibling on a wrapped grid; g must be the UNet's 16-bit gradient, xin comes in the same
+    type): the adjoint gather, sta_latent_guide and sta_window_split in one; CPU: guide_windows_reference and window_split_reference
+    (xin in `dtype`, default g's)."""
+    if x.dtype != torch.float32:
+        raise TypeError("sampler state x must be float32, got %s" % x.dtype)
+    if x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
+        raise ValueError("latent_guide_windows: the state must be a float32 [P, C, %d, %d] canvas, got %s" % (grid.Hc, grid.Wc, tuple(x.shape)))
+    P, C = x.shape[0], x.shape[1]
+    if tuple(g.shape) != (2 * P * grid.T, C, grid.s, grid.s):
+        raise ValueError("g %s must be the gradient of the window pair batch [%d, %d, %d, %d] of x %s"
+                         % (tuple(g.shape), 2 * P * grid.T, C, grid.s, grid.s, tuple(x.shape)))
+    if keep is not None and tuple(keep.shape) != (P, 1, grid.Hc, grid.Wc):
+        raise ValueError("keep %s must be [P, 1, Hc, Wc] of the state %s" % (tuple(keep.shape), tuple(x.shape)))
+    if not x.is_cuda:
+        x_out, rms = guide_windows_reference(g, x, step, count, grid, keep, normalize, inv_scale)
+        return x_out, (window_split_reference(x_out, grid, dtype or g.dtype) if want_xin else None), (rms if want_stats else None)
+    if g.dtype not in _DT:
+        raise TypeError("sta_latent_guide_windows takes the gradient in the UNet's 16-bit type, got %s" % g.dtype)
+    g, xc = g.detach().contiguous(), x.detach().contiguous()
+    kp = None if keep is None else keep.detach().to(x.device, torch.float32).contiguous()
+    per_canvas = lambda v: torch.as_tensor(v, dtype=torch.float32, device=x.device).reshape(-1).expand(P).contiguous()
+    st, cnt = per_canvas(step), per_canvas(count)
+    x_out = torch.empty_like(xc)
+    xin = torch.empty_like(g) if want_xin else None
+    stats = torch.empty(P, dtype=torch.float32, device=x.device) if want_stats else None
+    fn, name = _entry("sta_latent_guide_windows", grid)
+    lib.check(fn(g.data_ptr(), xc.data_ptr(), _ptr(kp), st.data_ptr(), cnt.data_ptr(), x_out.data_ptr(), _ptr(xin), _ptr(stats), P, C,
+                 grid.Hc, grid.Wc, *_grid_args(grid), int(bool(normalize)), float(inv_scale), _DT[g.dtype], _stream(x)), name)
+    return x_out, xin, stats
 
 
 def encode_step_windows(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, dtype=None, want_z0=False, want_xin=True):

@@ -12,6 +12,8 @@ and the input gradients of the trunk (sta.fused.tracked, the attention backwards
   guide_reference   the update formula in torch (the CPU path and the test oracle)
   latent_guide      CUDA: sta_latent_guide (csrc/sta_guide.hip), CPU: guide_reference
   AttnGuidance      owns an AttnLayoutLoss, evaluates E and dE / d(input pair) with one eager UNet call and applies the update
+  CanvasGuidance    the same on a canvas sampled as overlapping windows (sta.canvas): one energy per window image, the gradient w.r.t.
+                    the window pairs, the update on the canvas state through sta.canvas.latent_guide_windows
 
 The UNet's input is the 16-bit CFG pair (x, x) per image, so autograd returns the gradient as a pair; dE / dx is the sum of its two
 rows, which the kernel forms in fp32 (a 16-bit sum on the host would round once more and cost a launch).
@@ -206,3 +208,91 @@ class AttnGuidance:
         rms = torch.stack([r[3] for r in self._rec]).cpu()
         skipped = int((~(torch.isfinite(rms) & (rms > 0))).sum())
         return dict(calls=[(r[0], r[1]) for r in self._rec], energy=energy, rms=rms, skipped=skipped)
+
+
+class CanvasGuidance(AttnGuidance):
+    """Latent guidance of a canvas trajectory (`canvas_guidance=` of the samplers: sample_canvas, inpaint_canvas, decode_canvas; never
+    used by sample / sample_batch). Same constructor as AttnGuidance; `resolution` must be a level of the WINDOW.
+
+    The evaluation is the canvas trajectory's own UNet call run eagerly: the 2 P T window rows, every window with its own centres. The
+    loss is begun on the per-window centres (sta.canvas.window_centres, batch order p T + w) with disc_required=True: a window in which
+    no disc has a set pixel at the recording resolution has no valid readout, gives exactly 0 and no gradient — it is NON-CONTRIBUTING.
+        E[p] = sum_w E[p, w] / max(1, number of contributing windows of p);   differentiated: sum_p sum_w E[p, w] x the fp16 loss scale
+    The gradient w.r.t. the window pairs goes through sta.canvas.latent_guide_windows (the split's adjoint: a sum over the covering
+    windows) with step_p = scale (1 - acp_t), 0 where E[p] <= threshold, and count_p = the canvas elements covered by a contributing
+    window, so that the part of the canvas that receives gradient moves by step_p in rms.
+
+    result(): dict(calls=[(call, iteration)], energy [n, P], window_energy [n, P, T], rms [n, P], skipped=int)."""
+
+    grid = contributing = None
+
+    def begin(self, centres, texts=None, names=None, grid=None):
+        """A new canvas trajectory: centres normalised to the canvas, per canvas; texts / names per canvas (repeated per window here)."""
+        from . import canvas as _cv
+        self._rec, self._call, self.ready, self.grid, self.contributing, self._counts = [], None, False, grid, None, {}
+        if not self.enabled:
+            return self
+        if grid is None:
+            raise ValueError("CanvasGuidance.begin needs grid= (the sta.canvas.Grid of the trajectory)")
+        if grid.s % self.resolution:
+            raise ValueError("a %d x %d window has no level of side %d" % (grid.s, grid.s, self.resolution))
+        P = len(centres)
+        rep = lambda v: None if v is None else [v[p] for p in range(P) for _ in range(grid.T)]
+        self.loss.begin([wc for bx in centres for wc in _cv.window_centres(bx, grid)], texts=rep(texts), names=rep(names), n_calls=1,
+                        disc_required=True)
+        self.ready = self.loss.sel_ctx is not None
+        if self.ready:
+            self.contributing = self.loss._valid.any(1).reshape(P, grid.T).cpu()
+        return self
+
+    def _count(self, C, device):
+        from . import canvas as _cv
+        if (C, device) not in self._counts:
+            self._counts[(C, device)] = _cv.guide_count(self.grid, self.contributing, C).to(device)
+        return self._counts[(C, device)]
+
+    def update(self, x, xin, t, coef, call_index, alpha_cumprod_t, keep=None):
+        """`iters` updates before UNet call `call_index` -> (x, xin). x [P, C, Hc, Wc] fp32; xin: the 16-bit window input pairs
+        [2 P T, C, s, s] or None (then they are split here in the UNet's dtype and None is returned); t [P] / coef [P, K] belong to the
+        canvases (the bound call repeats them per window); keep [P, 1, Hc, Wc] or None."""
+        from . import canvas as _cv
+        if self._call is None:
+            raise RuntimeError("CanvasGuidance.update needs bind(call) first (the sampler does that per trajectory)")
+        loss, grid = self.loss, self.grid
+        P, T = x.shape[0], grid.T
+        wdtype = next(self.unet.parameters()).dtype
+        step_size = self.scale * (1.0 - float(alpha_cumprod_t))
+        n_contrib = self.contributing.sum(1).clamp(min=1).to(x.device, torch.float32)
+        count = self._count(x.shape[1], x.device)
+        for it in range(self.iters):
+            pair = (xin if xin is not None else _cv.window_split(x, grid, wdtype)).detach().requires_grad_(True)
+            loss.stop_after = self._last_block(grid.s) if self.blocks == "down" else None
+            try:
+                with torch.enable_grad(), _fused.tracked(True), loss:
+                    try:
+                        self._call(pair, t, coef)
+                    except _al._EarlyExit:
+                        pass
+                    energy = loss.take_call()                              # [P T], one energy per window image
+                    if energy is None:
+                        raise RuntimeError("the guidance recorded nothing: no %stransformer block works at %d x %d in this UNet"
+                                           % ("encoder-side " if self.blocks == "down" else "", self.resolution, self.resolution))
+                    total = energy.sum()
+                    ls = loss_scale_for(wdtype, float(total.detach())) if wdtype == torch.float16 else 1.0
+                    (g,) = torch.autograd.grad(total * ls if ls != 1.0 else total, pair)
+            finally:
+                loss.stop_after = None
+            ew = energy.detach().float().reshape(P, T)
+            e = ew.sum(1) / n_contrib
+            step = torch.where(e > self.threshold, torch.full_like(e, step_size), torch.zeros_like(e))
+            x, new_xin, rms = _cv.latent_guide_windows(g, x, step, count, grid, keep=keep, normalize=self.normalize, inv_scale=1.0 / ls,
+                                                       dtype=wdtype, want_xin=xin is not None)
+            xin = new_xin if xin is not None else None
+            self._rec.append((int(call_index), it, e, rms / ls, ew))
+        return x, xin
+
+    def result(self):
+        out = super().result()
+        if out is not None:
+            out["window_energy"] = torch.stack([r[4] for r in self._rec]).cpu()
+        return out

@@ -411,6 +411,25 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  * sta_vae_encode_step_windows_ring takes `int wrap` directly after s, as the other `_ring` siblings do (wrap = 0: the sibling, bit for bit).
  * Rules (STA_E_ARG with text, nothing launched): the grid rules above (C = 4); every tensor but z0 / xin non-NULL; h, n_post, n_enc, x, z0,
  * xin 16-byte aligned; wrap in 0 .. 3; dtype STA_BF16 / STA_F16.
+ *
+ * Attention guidance on a canvas: sta_latent_guide_windows is sta_latent_guide carried to a canvas, one launch from the gradient w.r.t. the
+ * WINDOW input pairs to the updated canvas state and the next call's window inputs. The windows are sta_window_split (rows = 1) of the canvas
+ * state, so the gradient w.r.t. the state is the split's adjoint: a SUM over the covering windows and both pair rows (not the overlap mean).
+ *   g: [2 P T][C][s][s] dtype;  x, x_out: [P][C][Hc][Wc] fp32;  keep: [P][Hc][Wc] fp32 or NULL (the kept region is not guided), broadcast over
+ *   the channels;  step, count: [P] fp32;  xin: NULL, or [2 P T][C][s][s] dtype;  stats: [P] fp32 or NULL.
+ * Per canvas p, fp32 arithmetic:
+ *     d[c][y][x] = (sum over the windows w covering (y, x), ascending w, of (g[2 (p T + w)] + g[2 (p T + w) + 1])[c][dy][dx]) (1 - keep[p][y][x])
+ *                  (each window's g_u + g_c is formed first; the sum starts from the first covering window's value)
+ *     rms_p = sqrt(sum d^2 / count[p])       count[p]: the number of canvas elements (channels included) that can receive gradient, the
+ *                                            host's; C Hc Wc on a canvas whose windows all contribute; 0 leaves the canvas untouched
+ *     s_p   = normalize ? step[p] / rms_p : step[p] inv_scale
+ *     x_out = x - s_p d  if rms_p is finite and > 0, else x_out = x bit for bit;  stats[p] = rms_p
+ *     xin   = sta_window_split (rows = 1) of x_out: the rounded vector in both rows of every covering window's pair
+ * Every workgroup of a canvas reduces the whole canvas's sum of squares in the same fixed order (no atomics, no hand-off): bit-reproducible,
+ * a canvas's outputs depend on that canvas's inputs alone. With T = 1 bit-equal to sta_latent_guide (b = P, n = C s s, hw = s s).
+ * sta_latent_guide_windows_ring takes `int wrap` directly after s (wrap = 0: the sibling, bit for bit).
+ * Rules (STA_E_ARG with text, nothing launched): the grid rules above; g, x, step, count, x_out non-NULL; g, x, keep, x_out, xin 16-byte
+ * aligned (step, count, stats: 4-byte); no output may overlap an input or another output; wrap in 0 .. 3; dtype STA_BF16 / STA_F16.
  */
 #define STA_MAX_WINDOW_OFFSETS 16
 #define STA_SRC_F32 2
@@ -447,6 +466,12 @@ int sta_vae_encode_step_windows(const void* h, const float* quant_w, const float
 int sta_vae_encode_step_windows_ring(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
                                      float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
                                      float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream);
+int sta_latent_guide_windows(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out, void* xin,
+                             float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int normalize,
+                             float inv_scale, int dtype, void* stream);
+int sta_latent_guide_windows_ring(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out,
+                                  void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                                  int wrap, int normalize, float inv_scale, int dtype, void* stream);
 
 /*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
