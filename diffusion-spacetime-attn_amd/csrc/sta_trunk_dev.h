@@ -18,8 +18,9 @@
 //   - anything of sta_ffgemm.hip. Its GELU folds 0.3275911 * 0.70710678 into one constant, which rounds differently from
 //     gelu_gate_parts below: it is another function and stays its own;
 //   - the per-channel-statistics branch (cs_a / cs_b) of gn_nhwc_apply_kernel: one user;
-//   - the C-ABI: no symbol, argument list, check order, error text, launch count, grid or block depends on this header
-//     (include/*.h, sta/lib.py's SYMBOLS and the Python callers are as they were).
+//   - the C-ABI: no symbol, argument list, check order, error text, launch count or grid depends on this header
+//     (include/*.h, sta/lib.py's SYMBOLS and the Python callers are as they were); of the blocks, only that of the NHWC GroupNorm
+//     forward (gn_nhwc_threads).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -104,6 +105,13 @@ inline int gn_nhwc_chunks(int HW) {
   if (n > 32) n = 32;
   if (n < 1) n = 1;
   return n;
+}
+
+// Threads the forward kernels are launched with: the R = GN_NT / (C / 8) working rows of gn_split, rounded up to whole waves (C = 2560:
+// 320 instead of 512, of which 192 would idle). gn_split itself does not depend on it, so the backward keeps GN_NT.
+inline int gn_nhwc_threads(int C) {
+  const int CV = C >> 3;
+  return (GN_NT / CV * CV + 63) & ~63;
 }
 
 // The shapes the split serves; `what` starts the error text ("groupnorm nhwc", "groupnorm nhwc bwd").

@@ -138,7 +138,36 @@ __global__ __launch_bounds__(NT) void gn_silu_kernel(const T* __restrict__ x, co
 // 8-channel column (16 bytes) of every R-th pixel. Kernel 1 writes per-chunk partial sums per group, kernel 2
 // folds them (tiny) and normalises. x is read twice (the second time mostly from L2 / Infinity Cache). The split, the workspace
 // layout and a group's mean / rstd come from sta_trunk_dev.h, as in the backward (sta_unet_bwd.hip).
+//
+// The streaming loop of both kernels takes U pixels per trip (statistics: GN_U; apply: 2 or 4, chosen by the launch): the U 16-byte
+// loads are issued first, from a pixel index clamped to the image's last pixel (always a valid address, so nothing branches around a
+// load), then the U transforms follow. The apply kernel's whole trips carry no predicate and one partial trip follows under p < p1;
+// the statistics kernel predicates its sums. The apply kernel issues its first trip's loads and its gamma / beta /
+// add vectors before the statistics fold and the barrier, so the fold runs under their latency. The fold gives 16 lanes to a
+// group: lane l adds the group's channels (or chunks) l, l + 16, ... in this order, one DPP row reduction adds the 16 lanes — a
+// fixed shape, no atomics. Both kernels are launched with gn_nhwc_threads(C) threads: the working rows, rounded up to whole waves.
 // --------------------------------------------------------------------------------------------------
+constexpr int GN_U = 2;             // pixels per trip of the statistics kernel
+constexpr int GN_LONG_TRIPS = 10;   // pixels per thread from which the apply kernel runs 4 per trip with streaming loads
+
+typedef __attribute__((ext_vector_type(4))) float gn_f4;
+typedef __attribute__((ext_vector_type(2))) float gn_f2;
+
+// the 8 pre-add values of image b's channels 8 col .. + 7 as two 16-byte loads (zeros without add)
+__device__ __forceinline__ void gn_load_add8(const float* __restrict__ add, int b, int C, int col, float* a) {
+  gn_f4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+  if (add) {
+    const gn_f4* ap = (const gn_f4*)(add + (size_t)b * C + col * 8);
+    a0 = ap[0];
+    a1 = ap[1];
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    a[e] = a0[e];
+    a[4 + e] = a1[e];
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(GN_NT) void gn_nhwc_stats_kernel(const T* __restrict__ x, const T* __restrict__ xb, int Ca, const float* __restrict__ add,
                                                              float* __restrict__ part, int C, int HW, int G, int chunk_px) {
@@ -151,25 +180,31 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_stats_kernel(const T* __restric
   __syncthreads();
   if (row < R) {
     float a[8], s[8], q[8];
+    gn_load_add8(add, b, C, col, a);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      a[e] = add ? add[(size_t)b * C + col * 8 + e] : 0.f;
       s[e] = 0.f;
       q[e] = 0.f;
     }
     const int p1 = min(HW, (chunk + 1) * chunk_px);
     // (xb: the input is the channel concatenation [x | xb] of two tensors with Ca and C - Ca channels, read in place)
     const bool second = xb && col * 8 >= Ca;
-    const T* src = second ? xb + (col * 8 - Ca) : x + col * 8;
     const int ld = xb ? (second ? C - Ca : Ca) : C;
-    for (int p = chunk * chunk_px + row; p < p1; p += R) {
-      const V8 v = *(const V8*)(src + ((size_t)b * HW + p) * ld);
+    const T* src = (second ? xb + (col * 8 - Ca) : x + col * 8) + (size_t)b * HW * ld;
+    for (int p = chunk * chunk_px + row; p < p1; p += GN_U * R) {
+      V8 v[GN_U];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float t = (float)v[e] + a[e];
-        s[e] += t;
-        q[e] += t * t;
-      }
+      for (int j = 0; j < GN_U; ++j) v[j] = *(const V8*)(src + (size_t)min(p + j * R, HW - 1) * ld);
+#pragma unroll
+      for (int j = 0; j < GN_U; ++j)
+        if (p + j * R < p1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float t = (float)v[j][e] + a[e];
+            s[e] += t;
+            q[e] += t * t;
+          }
+        }
     }
     // fold the 8 channels into their (at most two: Cg >= 8 or Cg == 4) groups, then one LDS atomic per group and moment
     // (gn_nhwc_bwd_kernel folds its two sums the same way)
@@ -194,7 +229,11 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_stats_kernel(const T* __restric
   if (threadIdx.x < 2 * G) part[gn_part_at(b, gridDim.x, chunk, G, 0) + threadIdx.x] = acc[threadIdx.x];
 }
 
-template <typename T>
+// U: pixels per trip. STREAM: x is loaded non-temporally (it is read for the last time here — the statistics kernel, where there
+// is one, has read it before). The launch picks <4, true> where a thread has at least GN_LONG_TRIPS pixels and <2, false> below:
+// measured per shape in profiles/gn_stream.md (U = 4 holds 74 VGPRs, 6 waves per SIMD, and wins only with the streaming loads and
+// enough trips to use them; U = 2 holds 62, 8 waves, and starts its few trips sooner).
+template <typename T, int U, bool STREAM>
 __global__ __launch_bounds__(GN_NT) void gn_nhwc_apply_kernel(const T* __restrict__ x, const T* __restrict__ xb, int Ca, const float* __restrict__ add,
                                                              const float* __restrict__ cs_a, const float* __restrict__ cs_b,
                                                              const T* __restrict__ gamma, const T* __restrict__ beta,
@@ -205,51 +244,86 @@ __global__ __launch_bounds__(GN_NT) void gn_nhwc_apply_kernel(const T* __restric
   const GnSplit sp = gn_split(C, G);
   const int R = sp.R, Cg = sp.Cg, row = sp.row, col = sp.col;
   const int b = blockIdx.y, chunk = blockIdx.x, nchunk = gridDim.x;
-  if (threadIdx.x < G) {
+  // A thread of a row past R (the last wave's spare lanes) keeps a valid column and an empty pixel range: it loads and stores nothing
+  // of its own but takes part in the fold.
+  const int p1 = min(HW, (chunk + 1) * chunk_px);
+  const bool second = xb && col * 8 >= Ca;
+  const int ld = xb ? (second ? C - Ca : Ca) : C;
+  const T* src = (second ? xb + (col * 8 - Ca) : x + col * 8) + (size_t)b * HW * ld;
+  T* dst = y + (size_t)b * HW * C + col * 8;
+  int p = row < R ? chunk * chunk_px + row : p1;
+  auto load = [&](int pix) {
+    const V8* at = (const V8*)(src + (size_t)min(pix, HW - 1) * ld);
+    if constexpr (STREAM) return __builtin_nontemporal_load(at);
+    else return *at;
+  };
+  // in flight across the fold: the first trip's pixels and the column's parameters
+  V8 v[U];
+#pragma unroll
+  for (int j = 0; j < U; ++j) v[j] = load(p + j * R);
+  const V8 gv = *(const V8*)(gamma + col * 8), bv = *(const V8*)(beta + col * 8);
+  float a[8];
+  gn_load_add8(add, b, C, col, a);
+
+  // The fold: lanes 16 g' .. 16 g' + 15 of the workgroup take group g' (+ blockDim / 16 per round), lane l its items l, l + 16, ...
+  const int l16 = threadIdx.x & 15;
+  for (int g = threadIdx.x >> 4; g < G; g += blockDim.x >> 4) {
     float s = 0.f, q = 0.f;
     if (cs_a) {
       // statistics accumulated per CHANNEL by the producing kernel (sum S_c, sum of squares Q_c of the stored values; csrc/sta_conv.hip,
       // sta_gemm.hip): with the per-(b, c) pre-add a, sum (x + a) = S + HW a and sum (x + a)^2 = Q + 2 a S + HW a^2
       const int Cb = C - Ca;
-      for (int c = threadIdx.x * Cg; c < (threadIdx.x + 1) * Cg; ++c) {
-        const float* st = (cs_b && c >= Ca) ? cs_b + ((size_t)b * Cb + (c - Ca)) * 2 : cs_a + ((size_t)b * (cs_b ? Ca : C) + c) * 2;
-        const float a = add ? add[(size_t)b * C + c] : 0.f;
-        s += st[0] + (float)HW * a;
-        q += st[1] + 2.f * a * st[0] + (float)HW * a * a;
+#pragma unroll 1
+      for (int c = g * Cg + l16; c < (g + 1) * Cg; c += 16) {
+        const gn_f2 st = *(const gn_f2*)((cs_b && c >= Ca) ? cs_b + ((size_t)b * Cb + (c - Ca)) * 2 : cs_a + ((size_t)b * (cs_b ? Ca : C) + c) * 2);
+        const float ac = add ? add[(size_t)b * C + c] : 0.f;
+        s += st[0] + (float)HW * ac;
+        q += st[1] + 2.f * ac * st[0] + (float)HW * ac * ac;
       }
-    } else
-      for (int k = 0; k < nchunk; ++k) {      // in chunk order
-        s += part[gn_part_at(b, nchunk, k, G, threadIdx.x)];
-        q += part[gn_part_at(b, nchunk, k, G, threadIdx.x) + 1];
+    } else {
+#pragma unroll 2
+      for (int k = l16; k < nchunk; k += 16) {
+        const gn_f2 pr = *(const gn_f2*)(part + gn_part_at(b, nchunk, k, G, g));
+        s += pr[0];
+        q += pr[1];
       }
-    gn_mean_rstd(s, q, 1.0f / ((float)Cg * (float)HW), eps, mean_s[threadIdx.x], rstd_s[threadIdx.x]);
+    }
+    s = row16_sum(s);
+    q = row16_sum(q);
+    if (l16 == 0) gn_mean_rstd(s, q, 1.0f / ((float)Cg * (float)HW), eps, mean_s[g], rstd_s[g]);
   }
   __syncthreads();
-  if (row >= R) return;
+  // a column lies in at most two groups (Cg >= 8 or Cg == 4): its first n0 channels in g0, the others in g0 + 1
+  const int g0 = (col * 8) / Cg, g1 = min(g0 + 1, G - 1), n0 = (g0 + 1) * Cg - col * 8;
+  const float mean0 = mean_s[g0], rstd0 = rstd_s[g0], mean1 = mean_s[g1], rstd1 = rstd_s[g1];
   float gm[8], bt[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const int c = col * 8 + e, g = c / Cg;
-    const float a = add ? add[(size_t)b * C + c] : 0.f;
-    gm[e] = (float)gamma[c] * rstd_s[g];
-    bt[e] = (float)beta[c] + (a - mean_s[g]) * gm[e];
+    gm[e] = (float)gv[e] * (e < n0 ? rstd0 : rstd1);
+    bt[e] = (float)bv[e] + (a[e] - (e < n0 ? mean0 : mean1)) * gm[e];
   }
-  const int p1 = min(HW, (chunk + 1) * chunk_px);
-  const bool second = xb && col * 8 >= Ca;
-  const T* src = second ? xb + (col * 8 - Ca) : x + col * 8;
-  const int ld = xb ? (second ? C - Ca : Ca) : C;
-  for (int p = chunk * chunk_px + row; p < p1; p += R) {
-    const size_t off = ((size_t)b * HW + p) * C + col * 8;
-    const V8 v = *(const V8*)(src + ((size_t)b * HW + p) * ld);
+  auto put = [&](int j) {
     V8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float t = (float)v[e] * gm[e] + bt[e];
+      float t = (float)v[j][e] * gm[e] + bt[e];
       if (silu) t = silu_f(t);
       o[e] = (T)t;
     }
-    *(V8*)(y + off) = o;
+    *(V8*)(dst + (size_t)(p + j * R) * C) = o;
+  };
+  // whole trips carry no predicate (every load is consumed before its registers are loaded again, so no wait drains the stores);
+  // the last, partial trip follows once
+  while (p + (U - 1) * R < p1) {
+#pragma unroll
+    for (int j = 0; j < U; ++j) put(j);
+    p += U * R;
+#pragma unroll
+    for (int j = 0; j < U; ++j) v[j] = load(p + j * R);
   }
+#pragma unroll
+  for (int j = 0; j < U - 1; ++j)
+    if (p + j * R < p1) put(j);
 }
 
 // partial[b][slot][c][2] (the epilogues of csrc/sta_conv.hip / sta_gemm.hip) -> stats[b][c][2]: fixed summation order, no atomics.
@@ -513,6 +587,19 @@ int gn_dispatch(const void* x, const float* add, const void* gamma, const void* 
 
 }  // namespace
 
+// the apply kernel's launch: pixels per trip and load policy by the pixels a thread has (chunk_px over the R rows of the split)
+template <typename T>
+static int gn_nhwc_apply_launch(const char* what, dim3 grid, hipStream_t st, const T* x, const T* xb, int Ca, const float* add, const float* cs_a,
+                                const float* cs_b, const T* gamma, const T* beta, const float* part, T* y, int C, int HW, int G, int chunk_px, float eps,
+                                int silu) {
+  const dim3 block(gn_nhwc_threads(C));
+  if (chunk_px / (GN_NT / (C >> 3)) >= GN_LONG_TRIPS)
+    return sta_launch<gn_nhwc_apply_kernel<T, 4, true>>(what, grid, block, 0, st, x, xb, Ca, add, cs_a, cs_b, gamma, beta, part, y, C, HW, G, chunk_px, eps,
+                                                        silu);
+  return sta_launch<gn_nhwc_apply_kernel<T, 2, false>>(what, grid, block, 0, st, x, xb, Ca, add, cs_a, cs_b, gamma, beta, part, y, C, HW, G, chunk_px, eps,
+                                                       silu);
+}
+
 extern "C" {
 
 int sta_groupnorm_silu(const void* x, const float* add, const void* gamma, const void* beta, void* y, int B, int C,
@@ -602,10 +689,10 @@ static int groupnorm_silu_nhwc_impl(const void* x, const void* xb, int Ca, const
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     const char* const what = "groupnorm_silu_nhwc launch";
-    if (const int rc = sta_launch<gn_nhwc_stats_kernel<T>>(what, grid, dim3(GN_NT), 0, st, (const T*)x, (const T*)xb, Ca, add, part, C, HW, G, chunk_px))
+    if (const int rc = sta_launch<gn_nhwc_stats_kernel<T>>(what, grid, dim3(gn_nhwc_threads(C)), 0, st, (const T*)x, (const T*)xb, Ca, add, part, C, HW, G, chunk_px))
       return rc;
-    return sta_launch<gn_nhwc_apply_kernel<T>>(what, grid, dim3(GN_NT), 0, st, (const T*)x, (const T*)xb, Ca, add, (const float*)nullptr,
-                                               (const float*)nullptr, (const T*)gamma, (const T*)beta, part, (T*)y, C, HW, G, chunk_px, eps, silu);
+    return gn_nhwc_apply_launch<T>(what, grid, st, (const T*)x, (const T*)xb, Ca, add, nullptr, nullptr, (const T*)gamma, (const T*)beta, part, (T*)y, C,
+                                   HW, G, chunk_px, eps, silu);
   });
 }
 
@@ -641,9 +728,8 @@ int sta_groupnorm_silu_nhwc_cstats(const void* xa, const void* xb, int Ca, const
   if (!xb) Ca = C;
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    return sta_launch<gn_nhwc_apply_kernel<T>>("groupnorm_silu_nhwc_cstats launch", grid, dim3(GN_NT), 0, st, (const T*)xa, (const T*)xb, Ca, add,
-                                               stats_a, stats_b, (const T*)gamma, (const T*)beta, (const float*)nullptr, (T*)y, C, HW, G, chunk_px,
-                                               eps, silu);
+    return gn_nhwc_apply_launch<T>("groupnorm_silu_nhwc_cstats launch", grid, st, (const T*)xa, (const T*)xb, Ca, add, stats_a, stats_b, (const T*)gamma,
+                                   (const T*)beta, nullptr, (T*)y, C, HW, G, chunk_px, eps, silu);
   });
 }
 

@@ -53,6 +53,7 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 # entry points included — falls under the rule)
 # (sta_rows640.hip: an included source is named by its own file; its kernels are looked for in the assembly of the unit that includes it)
 NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",), "sta_rows640.hip": ("rows640_kernel",), "sta_rowstail.hip": ("rows_tail_kernel",),
+                    "sta_unet.hip": ("gn_nhwc_apply_kernel", "gn_nhwc_stats_kernel"),
                     "sta_sampler.hip": ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel",
                                         "sampler_step_windows_masked_kernel", "window_blend_kernel", "vae_encode_step_windows_kernel",
                                         "latent_guide_windows_kernel")}
