@@ -39,13 +39,19 @@ __device__ __forceinline__ void quant_moments(const QuantConv& q, const typename
   }
 }
 
-// one channel of one pixel: the posterior's sample z0 = scale_factor (mean + exp(clamp(logvar, -30, 20) / 2) n_post) -> zz, and DDIM's
-// stochastic_encode x = sqrt_a z0 + sqrt_1ma n_enc -> the result
+// DDIM's stochastic_encode of one latent element: x = sqrt_a z0 + sqrt_1ma n_enc (the last step of encode1, and the noising of
+// latent_upscale_step_windows_kernel, sta_window.hip)
+__device__ __forceinline__ float noise1(float z0, float n_enc, float sqrt_a, float sqrt_1ma) {
+  return __builtin_fmaf(sqrt_1ma, n_enc, sqrt_a * z0);
+}
+
+// one channel of one pixel: the posterior's sample z0 = scale_factor (mean + exp(clamp(logvar, -30, 20) / 2) n_post) -> zz, and
+// noise1 of it -> the result
 __device__ __forceinline__ float encode1(float mean, float logvar_raw, float n_post, float n_enc, float scale_factor, float sqrt_a,
                                          float sqrt_1ma, float& zz) {
   const float logvar = fminf(fmaxf(logvar_raw, -30.f), 20.f);
   zz = scale_factor * __builtin_fmaf(expf(0.5f * logvar), n_post, mean);
-  return __builtin_fmaf(sqrt_1ma, n_enc, sqrt_a * zz);
+  return noise1(zz, n_enc, sqrt_a, sqrt_1ma);
 }
 
 }  // namespace

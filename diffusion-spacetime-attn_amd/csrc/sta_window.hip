@@ -16,6 +16,8 @@
 // sta_vae_encode_step (sta_encode.hip) uses for square images.
 // Attention guidance on a canvas (sta_latent_guide_windows and its `_ring` sibling): the adjoint of the split applied to the window pairs'
 // gradient, then sta_latent_guide's update (sta_guide.hip, included before this file: its guide_overlap and GUIDE_MAX_PARTS) and the split.
+// The hi-res fix on a canvas (sta_latent_upscale_step_windows and its `_ring` sibling): a smaller latent upscaled bilinearly to the canvas
+// (on a wrapped axis across the seam), noised with sta_encode_dev.h's noise1 and split, one launch.
 
 #include "sta_blend_dev.h"
 #include "sta_encode_dev.h"
@@ -275,6 +277,79 @@ __global__ __launch_bounds__(256) void vae_encode_step_windows_kernel(const T* _
       if (z0) store8(z0 + at, zz);
       if (xin) scatter<T, WRAP>(xin, g, q.row, 0, 1, 4, Hc, Wc, q, round8<T>(xx));
     }
+  }
+}
+
+// The hi-res fix on a canvas (sta_latent_upscale_step_windows and its `_ring` sibling): a finished trajectory's latent, upscaled
+// bilinearly to the canvas, noised to the decode's start and split, one launch.
+// The two taps and weights of output position d on one axis (source length L_in, scale = (float)L_in / (float)L_out, the host's):
+// src = (d + 0.5) scale - 0.5; a clamped axis takes max(src, 0), i0 = floor(src), i1 = min(i0 + 1, L_in - 1) — the rule of
+// torch.nn.functional.interpolate(mode="bilinear", align_corners=False); a WRAPPED axis does not clamp and takes both taps modulo L_in
+// (i0 lies in -1 .. L_in - 1: one conditional step each, no division), so the filter crosses the seam of a source that is itself a
+// ring. l1 = src - i0 (before the wrap), l0 = 1 - l1. Every operation is rounded on its own: no contraction in these two functions.
+struct Tap {
+  int i0, i1;
+  float l0, l1;
+};
+
+template <bool WRAPPED>
+__device__ __forceinline__ Tap upscale_tap(int d, float scale, int L_in) {
+#pragma clang fp contract(off)
+  float src = ((float)d + 0.5f) * scale;
+  src = src - 0.5f;
+  if constexpr (!WRAPPED) src = fmaxf(src, 0.f);
+  const float fl = floorf(src);
+  Tap t;
+  t.l1 = src - fl;
+  t.l0 = 1.0f - t.l1;
+  t.i0 = (int)fl;
+  if constexpr (WRAPPED) {
+    t.i0 += (t.i0 >> 31) & L_in;
+    t.i1 = t.i0 + 1;
+    t.i1 -= t.i1 >= L_in ? L_in : 0;
+  } else {
+    t.i0 = min(t.i0, L_in - 1);        // holds already for Hc >= h (src < L_in - 0.5); kept so that no tap can leave the source
+    t.i1 = min(t.i0 + 1, L_in - 1);
+  }
+  return t;
+}
+
+__device__ __forceinline__ float bilinear1(float z00, float z01, float z10, float z11, const Tap& ty, const Tap& tx) {
+#pragma clang fp contract(off)
+  const float a0 = tx.l0 * z00, a1 = tx.l1 * z01, b0 = tx.l0 * z10, b1 = tx.l1 * z11;
+  const float a = a0 + a1, b = b0 + b1;
+  const float ya = ty.l0 * a, yb = ty.l1 * b;
+  return ya + yb;
+}
+
+// z [P][C][h][w] fp32 -> x, z_up (null = not written) [P][C][Hc][Wc] fp32 and xin (null = not written) [2 P T][C][s][s]: z_up = the
+// bilinear upscale, x = noise1(z_up, noise) of sta_encode_dev.h, xin = window_split_kernel's (rows = 1) scatter of the rounded x.
+// A lane owns 8 consecutive canvas pixels of one row: the y taps and weights once per lane, the x taps per element; its 4 x 8 source
+// values are dword loads from the two source rows (at most 10 distinct columns per row; the source of one image stays in L2).
+template <typename T, int WRAP>
+__global__ __launch_bounds__(256) void latent_upscale_step_windows_kernel(const float* __restrict__ z, const float* __restrict__ noise,
+                                                                          float* __restrict__ x, float* __restrict__ z_up,
+                                                                          T* __restrict__ xin, long nvec, int C, int h, int w, int Hc, int Wc,
+                                                                          WinGrid g, float scale_y, float scale_x, float sqrt_a,
+                                                                          float sqrt_1ma) {
+  const long stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+    const CanvasPos q = canvas_pos(v, C, Hc, Wc / 8);
+    const Tap ty = upscale_tap<(WRAP & 2) != 0>(q.y, scale_y, h);
+    const float* plane = z + (q.row * C + q.c) * ((long)h * w);
+    const float* r0 = plane + (long)ty.i0 * w;
+    const float* r1 = plane + (long)ty.i1 * w;
+    float nz[8], zu[8], xx[8];
+    load8(noise + 8 * v, nz);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const Tap tx = upscale_tap<(WRAP & 1) != 0>(q.x + k, scale_x, w);
+      zu[k] = bilinear1(r0[tx.i0], r0[tx.i1], r1[tx.i0], r1[tx.i1], ty, tx);
+      xx[k] = noise1(zu[k], nz[k], sqrt_a, sqrt_1ma);
+    }
+    store8(x + 8 * v, xx);
+    if (z_up) store8(z_up + 8 * v, zu);
+    if (xin) scatter<T, WRAP>(xin, g, q.row, 0, 1, C, Hc, Wc, q, round8<T>(xx));
   }
 }
 
@@ -548,6 +623,30 @@ int encode_step_windows(const char* what, const void* h, const float* quant_w, c
   });
 }
 
+int upscale_step_windows(const char* what, const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w,
+                         int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float sqrt_a, float sqrt_1ma, int dtype,
+                         void* stream) {
+  g_sta_err[0] = 0;
+  if (!z || !noise || !x) return sta_fail(STA_E_ARG, "%s: null pointer", what);
+  WinGrid g;
+  if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
+  if (h < 8 || w < 8 || h % 8 || w % 8) return sta_fail(STA_E_ARG, "%s: source h=%d w=%d (need positive multiples of 8)", what, h, w);
+  if (Hc < h || Wc < w) return sta_fail(STA_E_ARG, "%s: canvas %d x %d is smaller than the source %d x %d (upscale only)", what, Hc, Wc, h, w);
+  if (!sta_aligned16(z) || !sta_aligned16(noise) || !sta_aligned16(x) || !sta_aligned16(z_up) || !sta_aligned16(xin))
+    return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_ARG, "%s: dtype %d (STA_BF16 or STA_F16)", what, dtype);
+  const long nvec = P * C * Hc * (Wc / 8);
+  const float scale_y = (float)h / (float)Hc, scale_x = (float)w / (float)Wc;
+  return sta_by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return by_wrap(wrap, [&](auto wr) {
+      return sta_launch<latent_upscale_step_windows_kernel<T, decltype(wr)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0,
+                                                                                    (hipStream_t)stream, z, noise, x, z_up, (T*)xin, nvec, C, h, w,
+                                                                                    Hc, Wc, g, scale_y, scale_x, sqrt_a, sqrt_1ma);
+    });
+  });
+}
+
 int latent_guide_windows(const char* what, const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out,
                          void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
                          int normalize, float inv_scale, int dtype, void* stream) {
@@ -588,6 +687,20 @@ int latent_guide_windows(const char* what, const void* g, const float* x, const 
 }  // namespace
 
 extern "C" {
+
+int sta_latent_upscale_step_windows(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
+                                    int Wc, int ny, int nx, const int* oy, const int* ox, int s, float sqrt_a, float sqrt_1ma, int dtype,
+                                    void* stream) {
+  return upscale_step_windows("latent_upscale_step_windows", z, noise, x, z_up, xin, P, C, h, w, Hc, Wc, ny, nx, oy, ox, s, 0, sqrt_a, sqrt_1ma,
+                              dtype, stream);
+}
+
+int sta_latent_upscale_step_windows_ring(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
+                                         int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float sqrt_a, float sqrt_1ma,
+                                         int dtype, void* stream) {
+  return upscale_step_windows("latent_upscale_step_windows_ring", z, noise, x, z_up, xin, P, C, h, w, Hc, Wc, ny, nx, oy, ox, s, wrap, sqrt_a,
+                              sqrt_1ma, dtype, stream);
+}
 
 int sta_latent_guide_windows(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out, void* xin,
                              float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int normalize,

@@ -111,16 +111,82 @@ class DDIMSampler(SolverSamplerBase):
             return x, z0, _cv.window_split(x, grid, h.dtype)
         return _cv.encode_step_windows(h, qc.weight, qc.bias, n_post, n_enc, sf, float(sa[t_enc]), float(s1m[t_enc]), grid, want_z0=want_z0)
 
+    def upscale_step_canvas(self, z, t_enc, noise, grid, want_z_up=False):
+        """The hi-res fix's entry into a canvas trajectory, the sibling of `encode_step_canvas` for a latent that is already on the
+        device: z [P, C, h, w] float32, the x0 of a finished trajectory (a square image or a smaller canvas) -> (x [P, C, Hc, Wc] fp32,
+        z_up or None, xin): z upscaled bilinearly to the grid's canvas (align_corners=False; across the seam on a wrapped axis) and noised
+        to table index t_enc with `noise` [P, C, Hc, Wc], and the first call's window input pairs [2 P T, C, s, s] in the UNet's type,
+        what `decode_canvas(..., xin=xin)` feeds the first UNet call. The coefficient tables are encode_step's (`_encode_coefs`). GPU: one
+        sta_latent_upscale_step_windows launch (sta.canvas.upscale_step_windows); `canvas_fused_step = False`: the torch restatement +
+        window_split, the launch sequence it replaces (tests, A/B runs); CPU tensors: the restatement."""
+        from sta import canvas as _cv
+        sa, s1m = self._encode_coefs()
+        sa, s1m = float(sa[t_enc]), float(s1m[t_enc])
+        wdtype = next(self.model.model.parameters()).dtype
+        if z.is_cuda and not self.canvas_fused_step:
+            x, z_up, _ = _cv.upscale_step_windows_reference(z, noise, sa, s1m, grid, want_z_up=want_z_up, want_xin=False)
+            return x, z_up, _cv.window_split(x, grid, wdtype)
+        return _cv.upscale_step_windows(z, noise, sa, s1m, grid, dtype=wdtype, want_z_up=want_z_up)
+
+    def hires_canvas(self, x_latents, canvas, window, stride=None, *, t_start, disc_scale=None, wrap="", noise=None, seed=1, **kwargs):
+        """The hi-res fix under a layout: x_latents [P, C, h, w], the x0 of a first pass (`last_result["x0"]` of sample, sample_batch or
+        sample_canvas), is upscaled in latent space to the canvas (Hc, Wc) >= (h, w), noised to table index t_start
+        (`upscale_step_canvas`, one launch on the GPU) and refined by `decode_canvas(x, ..., t_start=t_start, xin=xin, disc_scale=...)`,
+        whose other keywords these are (conditionings, unconditional_conditionings, bboxs, object_names, local_conditionings,
+        unconditional_guidance_scale, prompt_indices, curr_texts; mask= / x0= are passed through: the caller supplies an x0 of the
+        CANVAS's shape). The schedule is the one `make_schedule()` made.
+        disc_scale: None = Hc / h when Hc / h == Wc / w, so every object keeps its share of the picture ("the same layout"); a non-uniform
+        upscale needs an explicit disc_scale (a disc stays a circle in window coordinates).
+        Draws, in this order: (1) the encode noise, where encode_step_canvas's callers draw theirs — per canvas torch.manual_seed(seed),
+        then torch.randn([1, C, Hc, Wc]) on the latents' device — unless `noise=` [P, C, Hc, Wc] is given; (2) decode_canvas's draws
+        (blend draw of a call before its eta draw).
+        The noise level is img2img's (the reference's off-by-one, see the module docstring): table index t_start, one DDIM step above
+        the first call's own timestep; at t_start = S, where the tables end, the last entry, which is the first call's own level.
+        ValueError before any UNet call: what decode_canvas refuses; before any draw or launch: no schedule, t_start outside 1 .. S, a
+        canvas smaller than the latents, a non-uniform upscale without disc_scale, a disc_scale the grid refuses."""
+        from sta import canvas as _cv
+        if self.tables is None:
+            raise ValueError("hires_canvas: make_schedule() first (the refine runs the last t_start calls of the schedule it made)")
+        S = len(self.tables["t_in"])
+        if not 1 <= int(t_start) <= S:
+            raise ValueError("hires_canvas: t_start must be in 1 .. %d, got %s" % (S, t_start))
+        if x_latents is None or x_latents.dim() != 4:
+            raise ValueError("hires_canvas: x_latents must be the first pass's latents [P, C, h, w]")
+        Hc, Wc = canvas
+        grid = _cv.window_grid(Hc, Wc, window, window // 2 if stride is None else stride, wrap)
+        P, C, h, w = x_latents.shape
+        if grid.Hc < h or grid.Wc < w:
+            raise ValueError("hires_canvas: the canvas %d x %d is smaller than the first pass's latents %d x %d (upscale only)"
+                             % (grid.Hc, grid.Wc, h, w))
+        if disc_scale is None:
+            if grid.Hc * w != grid.Wc * h:
+                raise ValueError("hires_canvas: %d x %d -> %d x %d is not a uniform upscale; pass disc_scale (a disc stays a circle in "
+                                 "window coordinates)" % (h, w, grid.Hc, grid.Wc))
+            disc_scale = grid.Hc / h
+        disc_scale = _cv.check_disc_scale(grid, disc_scale)
+        z = x_latents.detach().float()
+        if noise is None:
+            draws = []
+            for _ in range(P):
+                torch.manual_seed(seed)
+                draws.append(torch.randn((1, C, grid.Hc, grid.Wc), device=z.device))
+            noise = torch.cat(draws)
+        elif tuple(noise.shape) != (P, C, grid.Hc, grid.Wc):
+            raise ValueError("hires_canvas: noise %s must be [P, C, Hc, Wc] = %s" % (tuple(noise.shape), (P, C, grid.Hc, grid.Wc)))
+        x, _, xin = self.upscale_step_canvas(z, min(int(t_start), len(self.tables["a"]) - 1), noise, grid)
+        return self.decode_canvas(x, canvas, window, stride, t_start=t_start, xin=xin, wrap=wrap, disc_scale=disc_scale, seed=seed, **kwargs)
+
     def decode_canvas(self, x_latents, canvas, window, stride=None, *, t_start, conditionings, unconditional_conditionings, bboxs,
                       object_names, local_conditionings, unconditional_guidance_scale=7.5, seed=1, prompt_indices=None, curr_texts=None,
-                      xin=None, mask=None, x0=None, image=None, mask_px=None, wrap=""):
+                      xin=None, mask=None, x0=None, image=None, mask_px=None, wrap="", disc_scale=1.0):
         """img2img on a canvas: the last t_start DDIM calls of the schedule `make_schedule()` made (not made again, as `decode`), from the
         canvas latents x_latents [P, 4, Hc, Wc] — an encoded picture noised by `encode_step_canvas` / `stochastic_encode`, or a canvas
         sampled earlier. Every call is one CFG batch of 2 P T window rows and the step runs on the canvas (`sample_canvas`, whose other
         keywords these are); call j runs at the timestep and with the weight column of call S - t_start + j. `last_result` as for
         sample_canvas. xin: the first call's window input pairs [2 P T, 4, s, s] (encode_step_canvas); without it they come from
         window_split. mask= / x0= (image= / mask_px=): the kept region is re-noised from x0 before every call as in `decode(mask=)` and
-        `inpaint_canvas`; the first call is blended too (sta_window_blend then replaces a given xin). Fixed weights only.
+        `inpaint_canvas`; the first call is blended too (sta_window_blend then replaces a given xin). disc_scale: sample_canvas's (the
+        discs have radius 0.2 disc_scale window sides). Fixed weights only.
         ValueError before any UNet call: everything sample_canvas / inpaint_canvas refuses apart from the start, t_start outside 1 .. S,
         x_latents or xin of another shape than the canvas's, no schedule made."""
         if self.tables is None:
@@ -154,7 +220,7 @@ class DDIMSampler(SolverSamplerBase):
         try:
             self._sample_canvas("decode_canvas", S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
                                 local_conditionings, x_latents.float(), unconditional_guidance_scale, None, seed, prompt_indices, curr_texts,
-                                channels, False, prepare=prepare, wrap=wrap, decode_from=S - int(t_start))
+                                channels, False, prepare=prepare, wrap=wrap, decode_from=S - int(t_start), disc_scale=disc_scale)
         finally:
             self._xin0, self._inpaint = None, None
         return self.last_result["x0"]

@@ -324,17 +324,20 @@ class PLMSSampler(object):
 
     _canvas = None               # the sta.canvas.Grid while sample_canvas / inpaint_canvas runs (set like _start / _inpaint, cleared in `finally`)
     canvas_fused_step = True     # step-kernel samplers on a canvas: one sta_sampler_step_windows launch per call (False: fuse + step + split)
+    _disc_scale = 1.0            # the discs' radius in units of 0.2 window sides while a canvas trajectory runs (set and cleared with _canvas)
     canvas_wrap_margin = 8       # wrapped canvases: latent cells of circular padding per side around the ONE decode (0: none; <= the axis)
 
     def sample_canvas(self, S, canvas, window, stride=None, conditionings=None, unconditional_conditionings=None, bboxs=None,
                       object_names=None, local_conditionings=None, x_T=None, unconditional_guidance_scale=7.5, eta=0.0, seed=1,
-                      prompt_indices=None, curr_texts=None, mask=None, x0=None, channels=4, verbose=False, wrap=""):
+                      prompt_indices=None, curr_texts=None, mask=None, x0=None, channels=4, verbose=False, wrap="", disc_scale=1.0):
         """P wide or tall canvases (same number of objects), each sampled as T overlapping square windows (sta.canvas): every UNet call
         sees the 2 P T window rows as one CFG batch — an ordinary batch of P T images for the blocks, graph replay included —, the T
         predictions are averaged where windows overlap and the sampler step runs on the canvas.
         canvas = (Hc, Wc), window = s, stride (default s / 2): latent pixels, the grid rules of sta.canvas.window_grid. The other
         arguments are per-canvas lists as in `sample_batch`; `bboxs` are normalised to the canvas (every window's blocks get them
-        re-expressed in its own coordinates: a disc has radius 0.2 s latent pixels everywhere); the prompt, the unconditional context,
+        re-expressed in its own coordinates: a disc has radius 0.2 disc_scale s latent pixels in every window; disc_scale = 1.0, the
+        default, is 0.2 s everywhere, and a refine of an upscaled picture passes the upscale factor so that an object keeps its share of
+        the canvas; on a wrapped axis of length L a disc_scale with L - s < 0.4 disc_scale s is refused); the prompt, the unconditional context,
         the local contexts and the blend weights W[p] belong to the canvas and are repeated per window. x_T: [P, channels, Hc, Wc].
         `last_result`: x0 [P, channels, Hc, Wc], image [P, 3, 8 Hc, 8 Wc] from ONE decode of the whole canvas, W [P, K, S].
         wrap = "x" | "y" | "xy": the canvas closes on itself along those axes (360 degree panorama: "x"; tileable image: "xy"): the
@@ -349,7 +352,7 @@ class PLMSSampler(object):
             raise ValueError("sample_canvas: mask= / x0= (inpainting) is not defined on a canvas (see inpaint_canvas)")
         return self._sample_canvas("sample_canvas", S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
                                    local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices, curr_texts, channels,
-                                   verbose, wrap=wrap)
+                                   verbose, wrap=wrap, disc_scale=disc_scale)
 
     def inpaint_canvas(self, S, canvas, window, stride=None, *, mask=None, x0=None, image=None, mask_px=None, **kwargs):
         """Inpainting / outpainting on a canvas: the step-kernel samplers only (SolverSamplerBase.inpaint_canvas), as `sample(mask=)`."""
@@ -358,7 +361,7 @@ class PLMSSampler(object):
 
     def _sample_canvas(self, what, S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs, object_names,
                        local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices, curr_texts, channels, verbose,
-                       prepare=None, wrap="", decode_from=None):
+                       prepare=None, wrap="", decode_from=None, disc_scale=1.0):
         """The body of sample_canvas, inpaint_canvas and DDIMSampler.decode_canvas: every refusal, then the epoch loop on the canvas with
         `_canvas` set. prepare(P, channels, grid): the caller's own checks and state once the canvas is known (inpaint_canvas: the inpaint
         state). decode_from: None, or the call decode_canvas starts at — its explicit permission for a non-zero `_start`, which it sets
@@ -374,6 +377,7 @@ class PLMSSampler(object):
             raise ValueError("%s: a trajectory that starts at call %d (img2img) is not defined on a canvas" % (what, self._start))
         Hc, Wc = canvas
         grid = _cv.window_grid(Hc, Wc, window, window // 2 if stride is None else stride, wrap)
+        disc_scale = _cv.check_disc_scale(grid, disc_scale)
         margin = int(self.canvas_wrap_margin)
         for axis, L in (("x", grid.Wc), ("y", grid.Hc)):
             if axis in grid.wrap and not 0 <= margin <= L:
@@ -390,7 +394,7 @@ class PLMSSampler(object):
             else unconditional_conditionings.expand(P, -1, -1)
         if prepare is not None:
             prepare(P, channels, grid)
-        self._canvas = grid
+        self._canvas, self._disc_scale = grid, disc_scale
         try:
             if decode_from is None:
                 self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
@@ -404,7 +408,7 @@ class PLMSSampler(object):
                                object_names=list(object_names),
                                local_conditionings=[loc for loc in local_conditionings for _ in range(grid.T)], batched=True)
         finally:
-            self._canvas = None
+            self._canvas, self._disc_scale = None, 1.0
             if decode_from is not None:
                 self._start = 0
         return None
@@ -492,7 +496,8 @@ class PLMSSampler(object):
         img_input = (torch.randn(shape, device=device) if x_T is None else x_T.to(device)).clone()
 
         # tell the 16 blocks a new prompt (batch) starts (replaces the `time == 981` test + cwd files)
-        _ps.begin_prompt(local if (batched or local is None) else local[0], first_timestep=int(time_range[self._first_call()]))
+        _ps.begin_prompt(local if (batched or local is None) else local[0], first_timestep=int(time_range[self._first_call()]),
+                         disc_radius=0.2 * self._disc_scale)      # 1.0 outside a canvas trajectory: `sample` and `sample_batch` never scale
         block_boxes = boxes if batched else boxes[0]
 
         W = torch.full((b, K, S), self.weight_init / K if K else 0.0, device=device, dtype=torch.float32)   # :204-209
@@ -912,12 +917,12 @@ class SolverSamplerBase(PLMSSampler):
     def inpaint_canvas(self, S, canvas, window, stride=None, *, mask=None, x0=None, image=None, mask_px=None, conditionings=None,
                        unconditional_conditionings=None, bboxs=None, object_names=None, local_conditionings=None, x_T=None,
                        unconditional_guidance_scale=7.5, eta=0.0, seed=1, prompt_indices=None, curr_texts=None, channels=4, verbose=False,
-                       wrap=""):
+                       wrap="", disc_scale=1.0):
         """`sample_canvas` with the kept region (mask == 1) of every canvas re-noised from x0 before every UNet call: outpainting (x0 holds
         an existing picture's latent on its footprint, mask is 1 there) and the repaint of a region of a canvas sampled earlier.
         mask [P, 1, Hc, Wc] in [0, 1], 1 = keep; x0 [P, channels, Hc, Wc]; image [P, 3, 8 Hc, 8 Wc] in [0, 1] / mask_px [P, 1, 8 Hc, 8 Wc]:
         the original and its keep mask for the pixel-space paste over the ONE decode of the whole canvas (sta_image_composite); the other
-        keywords are sample_canvas's (wrap= included: the `_ring` launches, and the pixel-space paste on the cropped decode). On the GPU
+        keywords are sample_canvas's (disc_scale= and wrap= included: the `_ring` launches, and the pixel-space paste on the cropped decode). On the GPU
         one sta_window_blend launch runs before call 0, one sta_sampler_step_windows_masked launch after calls 0 .. S - 2 and the plain
         sta_sampler_step_windows after the last call. The blend draws are canvas-shaped, in the order of `sample(mask=)`: blend draw of call i, eta draw of call i, blend draw of call i + 1, ...
         ValueError before any UNet call: what sample_canvas refuses, a missing mask or x0, shapes that are not the canvas's, mask values
@@ -939,7 +944,7 @@ class SolverSamplerBase(PLMSSampler):
         try:
             return self._sample_canvas("inpaint_canvas", S, canvas, window, stride, conditionings, unconditional_conditionings, bboxs,
                                        object_names, local_conditionings, x_T, unconditional_guidance_scale, eta, seed, prompt_indices,
-                                       curr_texts, channels, verbose, prepare=prepare, wrap=wrap)
+                                       curr_texts, channels, verbose, prepare=prepare, wrap=wrap, disc_scale=disc_scale)
         finally:
             self._inpaint = None
 

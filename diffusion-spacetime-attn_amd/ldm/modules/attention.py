@@ -281,7 +281,7 @@ class BasicTransformerBlock(nn.Module):
             else:
                 cache.packed_proj, cache.qfrag, cache.ofrag = None, False, False
             if K:
-                m = torch.stack([_ops.disc_mask_bits(c, dim) for c in centres]).to(context.device)   # [I, N]
+                m = torch.stack([_ops.disc_mask_bits(c, dim, _ps.disc_radius_sq()) for c in centres]).to(context.device)   # [I, N]
                 if cache.mask is None:
                     cache.mask = m
                 else:

@@ -11,7 +11,11 @@ img2img.py and inpaint.py through add_guidance_arguments / check_guidance_option
 --canvas HxW / --canvas_stride PX (a wide or tall canvas sampled as overlapping --H x --W windows, sta.canvas; the layout's centres are
 then normalised to the canvas; fixed blend weights only; --canvas_guidance ETA: attention guidance on the canvas, sta.guidance.
 CanvasGuidance), --canvas_wrap x|y|xy (the canvas closes on itself along those axes: a 360 degree
-panorama or a tileable image).
+panorama or a tileable image), --hires HxW / --hires_strength F / --hires_stride PX (the hi-res fix: every first pass — a --H x --W image
+or a --canvas, any of the three samplers — is followed by a second, DDIM pass on the same model that upscales the first pass's latent on
+the GPU to H x W pixels (DDIMSampler.hires_canvas: one sta_latent_upscale_step_windows launch), noises it to t_start = int(F x
+--ddim_steps) and refines it as overlapping --H x --W windows under the same layout, the discs scaled with the picture; fixed blend
+weights in the second pass; both passes' images are saved, the second pass's in the subdirectory hires/ of the first pass's).
 With torch.distributed.run the prompts are sharded round-robin over the ranks (one GPU each).
 """
 import argparse
@@ -103,6 +107,17 @@ def build_parser(default_dataset):
                    help="the --canvas closes on itself along these axes (x: a 360 degree panorama whose right edge continues into the left "
                         "one; xy: a tileable image): the windows run over the seam. A wrapped axis must be a multiple of the stride and at "
                         "least 1.5 windows long")
+    p.add_argument("--hires", type=str, default=None, metavar="HxW",
+                   help="the hi-res fix: after the first pass (--H x --W, or --canvas) upscale its latent on the GPU to H x W pixels "
+                        "(multiples of 64, at least the first pass's size, the same ratio on both axes) and refine it with DDIM "
+                        "(--ddim_steps, --ddim_eta) as overlapping --H x --W windows under the same layout, every disc scaled by the "
+                        "upscale factor; needs --hires_strength; --canvas_wrap and --canvas_guidance carry over to the second pass; the "
+                        "second pass runs with fixed blend weights (handing it weights optimised in the first pass is out of scope); no "
+                        "--attn_maps / --attn_loss; the second pass's images go to the subdirectory hires/ of the first pass's")
+    p.add_argument("--hires_strength", type=float, default=None, metavar="F",
+                   help="in (0, 1], required with --hires (no default): the second pass runs the last int(F x --ddim_steps) DDIM calls")
+    p.add_argument("--hires_stride", type=int, default=None, metavar="PX",
+                   help="distance between neighbouring windows of the second pass in pixels (default: half the window)")
     add_guidance_arguments(p)
     return p
 
@@ -224,7 +239,7 @@ def canvas_grid(opt):
             raise SystemExit("--canvas_stride %d needs --canvas HxW" % opt.canvas_stride)
         if wrap:
             raise SystemExit("--canvas_wrap %s needs --canvas HxW" % wrap)
-        if getattr(opt, "canvas_guidance", None) is not None:
+        if getattr(opt, "canvas_guidance", None) is not None and getattr(opt, "hires", None) is None:      # --hires: its second pass is a canvas
             raise SystemExit("--canvas_guidance %s needs --canvas HxW (a square image is guided with --attn_guidance)" % opt.canvas_guidance)
         return None
     parts = opt.canvas.lower().split("x")
@@ -254,6 +269,58 @@ def canvas_grid(opt):
         return canvas.window_grid(Hpx // opt.f, Wpx // opt.f, opt.H // opt.f, stride // opt.f, wrap)
     except ValueError as e:
         raise SystemExit("--canvas %s (latent pixels): %s" % (opt.canvas, e))
+
+
+def hires_plan(opt):
+    """--hires / --hires_strength / --hires_stride -> (the second pass's sta.canvas.Grid in latent pixels, t_start, disc_scale), or None
+    without --hires; every refusal that needs no GPU."""
+    if opt.hires is None:
+        for flag, v in (("--hires_strength", opt.hires_strength), ("--hires_stride", opt.hires_stride)):
+            if v is not None:
+                raise SystemExit("%s %s needs --hires HxW" % (flag, v))
+        return None
+    parts = opt.hires.lower().split("x")
+    if len(parts) != 2 or not all(v.isdigit() for v in parts):
+        raise SystemExit("--hires %s: expected HxW in pixels, e.g. 1024x1024" % opt.hires)
+    Hpx, Wpx = int(parts[0]), int(parts[1])
+    unit = max(64, 8 * opt.f)
+    if opt.H != opt.W:
+        raise SystemExit("--hires refines square windows: --H %d and --W %d differ" % (opt.H, opt.W))
+    stride = opt.H // 2 if opt.hires_stride is None else opt.hires_stride
+    for name, v, u in (("--hires height", Hpx, unit), ("--hires width", Wpx, unit), ("--H / --W", opt.H, 8 * opt.f),
+                       ("--hires_stride", stride, 8 * opt.f)):
+        if v <= 0 or v % u:
+            raise SystemExit("%s %d is not a positive multiple of %d pixels" % (name, v, u))
+    first = canvas_grid(opt)
+    H1, W1 = (opt.H, opt.W) if first is None else (first.Hc * opt.f, first.Wc * opt.f)
+    if Hpx < H1 or Wpx < W1:
+        raise SystemExit("--hires %s is smaller than the first pass's %d x %d pixels (upscale only)" % (opt.hires, H1, W1))
+    if Hpx * W1 != Wpx * H1:
+        raise SystemExit("--hires %s is not a uniform upscale of the first pass's %d x %d pixels (a non-uniform ratio would turn the "
+                         "layout's discs into ellipses)" % (opt.hires, H1, W1))
+    if opt.hires_strength is None:
+        raise SystemExit("--hires needs --hires_strength F in (0, 1] (there is no default)")
+    if not 0.0 < opt.hires_strength <= 1.0:
+        raise SystemExit("--hires_strength %s must be in (0, 1]" % opt.hires_strength)
+    t_start = int(opt.hires_strength * opt.ddim_steps)
+    if not 1 <= t_start <= opt.ddim_steps:
+        raise SystemExit("t_start = int(hires_strength * ddim_steps) = %d must be in 1 .. %d" % (t_start, opt.ddim_steps))
+    for flag, on in (("--attn_maps", opt.attn_maps), ("--attn_loss", opt.attn_loss is not None)):
+        if on:
+            raise SystemExit("%s reads one square image's attention maps and is not defined on the canvas of --hires" % flag)
+    if getattr(opt, "canvas_guidance", None) is not None:
+        levels = [opt.H // opt.f // d for d in (1, 2, 4, 8)]
+        if opt.attn_res not in levels:
+            raise SystemExit("--attn_res %d: no transformer level of a %d x %d window has that side (levels: %s)"
+                             % (opt.attn_res, opt.H, opt.H, ", ".join(str(v) for v in levels)))
+    from sta import canvas
+    disc_scale = Hpx / H1
+    try:
+        grid = canvas.window_grid(Hpx // opt.f, Wpx // opt.f, opt.H // opt.f, stride // opt.f, getattr(opt, "canvas_wrap", None) or "")
+        canvas.check_disc_scale(grid, disc_scale)
+    except ValueError as e:
+        raise SystemExit("--hires %s (latent pixels): %s" % (opt.hires, e))
+    return grid, t_start, disc_scale
 
 
 def builtin_clip(opt):
@@ -310,6 +377,7 @@ def check_options(opt):
     if opt.mxfp8 and opt.opt_epochs > 0:
         raise SystemExit("--mxfp8 is an inference option: use --opt_epochs 0")
     canvas_grid(opt)
+    hires_plan(opt)
     check_clip_option(opt, (opt.H, opt.W))
     check_attn_option(opt)
 
@@ -406,6 +474,11 @@ def run(kind, default_dataset):
                                           attn_loss=attn_loss, attn_loss_weight=opt.attn_loss if attn_loss is not None else 1.0,
                                           latent_guidance=make_guidance(opt, model), canvas_guidance=make_canvas_guidance(opt, model))
     os.makedirs(opt.outdir, exist_ok=True)
+    hires = hires_plan(opt)
+    if hires is not None:       # the second pass: DDIM on the same model, fixed weights, its own output directory
+        hires_sampler = sampler_class("DDIMSampler")(model, opt_epochs=0, outdir=os.path.join(sampler.outdir, "hires"),
+                                                     canvas_guidance=make_canvas_guidance(opt, model))
+        hires_sampler.make_schedule(opt.ddim_steps, ddim_eta=opt.ddim_eta, verbose=False)
 
     seed = 1                                                            # txt2img-gpt.py:304
     shape = [opt.C, opt.H // opt.f, opt.W // opt.f]
@@ -422,6 +495,22 @@ def run(kind, default_dataset):
                                              None if image is None else image[j], index=j):
                 print("[rank %d] %s" % (rank, line))
 
+    def refine(group):
+        """--hires: the second pass on the latents the first pass just left in sampler.last_result["x0"] (one per prompt of `group`)."""
+        if hires is None:
+            return
+        g2, t_start, disc_scale = hires
+        conds = [conditionings(model, p, list(l.keys()), dtype) for _, p, l in group]
+        print("[rank %d] hi-res fix for prompts %s: %s pixels, %d windows each, the last %d of %d DDIM calls, discs x %g"
+              % (rank, [i for i, _, _ in group], opt.hires, g2.T, t_start, opt.ddim_steps, disc_scale))
+        hires_sampler.hires_canvas(sampler.last_result["x0"], (g2.Hc, g2.Wc), g2.s, g2.stride, t_start=t_start, disc_scale=disc_scale,
+                                   wrap=g2.wrap, seed=seed, conditionings=[c[1] for c in conds],
+                                   unconditional_conditionings=[c[0] for c in conds], bboxs=[[l[n] for n in l] for _, _, l in group],
+                                   object_names=[list(l.keys()) for _, _, l in group], local_conditionings=[c[2] for c in conds],
+                                   unconditional_guidance_scale=opt.scale, prompt_indices=[i for i, _, _ in group],
+                                   curr_texts=[p for _, p, _ in group])
+        report_guidance(hires_sampler, [i for i, _, _ in group], "[rank %d] hires: " % rank)
+
     def run_one(prompt_idx, prompt, layout):
         torch.manual_seed(seed)                                         # seed_everything(seed), :306
         print("[rank %d] Start inference for %dth prompt: %s" % (rank, prompt_idx, prompt))
@@ -434,6 +523,7 @@ def run(kind, default_dataset):
                        prompt_idx=prompt_idx, object_names=names, local_conditionings=local_c)
         report_attn([(prompt_idx, prompt, layout)])
         report_guidance(sampler, [prompt_idx], "[rank %d] " % rank)
+        refine([(prompt_idx, prompt, layout)])
 
     def run_group(group):
         """Prompts with the same number of objects share one CFG batch; every image keeps the reference's
@@ -450,6 +540,7 @@ def run(kind, default_dataset):
                              seed=seed, prompt_indices=[i for i, _, _ in group])
         report_attn(group)
         report_guidance(sampler, [i for i, _, _ in group], "[rank %d] " % rank)
+        refine(group)
 
     grid = canvas_grid(opt)
 
@@ -467,6 +558,7 @@ def run(kind, default_dataset):
                               x_T=x1.expand(len(group), -1, -1, -1).contiguous(), unconditional_guidance_scale=opt.scale, eta=eta, seed=seed,
                               prompt_indices=[i for i, _, _ in group], channels=opt.C, wrap=grid.wrap)
         report_guidance(sampler, [i for i, _, _ in group], "[rank %d] " % rank)
+        refine(group)
 
     items = [(i, p, datasets.layout_for(layouts, p, i) or {}) for i, p in mine]
     if grid is not None:

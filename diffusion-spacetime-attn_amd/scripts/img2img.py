@@ -17,11 +17,13 @@ as overlapping --window x --window windows (sta.canvas; the flags mean what they
 padding, so the encoder sees across the seam), one sta_vae_encode_step_windows launch writes the canvas state and the first call's window
 inputs, and DDIMSampler.decode_canvas runs the last t_enc calls. The layout's centres are normalised to the canvas; prompts with the same
 object count run as P canvases of one batch (--batch_prompts); the draws below are canvas-shaped. --canvas_guidance ETA guides the decode
-from its first call (sta.guidance.CanvasGuidance; needs --canvas). Refused with --canvas before a model is
+from its first call (sta.guidance.CanvasGuidance; needs --canvas). --disc_scale F (default 1.0; needs --canvas): the layout's discs have radius 0.2 F
+window sides in every window; an upscale-and-refine pass gives the upscale factor (2.0 for 512^2 -> 1024x1024) so that every object keeps
+its share of the picture. Refused with --canvas before a model is
 built: --opt_epochs > 1, --attn_guidance, a --window that is no multiple of 8 x --f, and every refusal of the txt2img scripts' canvas
 grid. Not claimed: image quality or seam visibility with real weights; the VAE's mid-block attention is global over the canvas, O((Hc
-Wc)^2) memory in its chunked form, for the encoder as for the one decode; a disc keeps its radius of 0.2 window sides, so objects shrink
-relative to an upscaled canvas.
+Wc)^2) memory in its chunked form, for the encoder as for the one decode; without --disc_scale a disc keeps its radius of 0.2 window sides, so
+objects shrink relative to an upscaled canvas.
 
 Refused before anything is built: --plms (the reference raises NotImplementedError too), --dpm_solver, t_enc = int(strength S) outside
 1 .. S - 1 (at t_enc = S the reference indexes past its tables), --n_samples != 1, a non-square image or a side that is not a multiple
@@ -97,6 +99,9 @@ def add_canvas_arguments(p):
     p.add_argument("--canvas_wrap", type=str, default=None, choices=("x", "y", "xy"),
                    help="the --canvas closes on itself along these axes (x: a 360 degree panorama)")
     p.add_argument("--window", type=int, default=512, metavar="PX", help="side of the square windows of --canvas in pixels")
+    p.add_argument("--disc_scale", type=float, default=1.0, metavar="F",
+                   help="the layout's discs have radius 0.2 F window sides on the --canvas (default 1.0); the upscale factor keeps every "
+                        "object's share of an upscaled picture")
 
 
 def canvas_grid(opt):
@@ -106,9 +111,18 @@ def canvas_grid(opt):
                               f=opt.f, opt_epochs=opt.opt_epochs, attn_maps=False, attn_loss=None, attn_guidance=opt.attn_guidance,
                               canvas_guidance=opt.canvas_guidance, attn_res=opt.attn_res)
     try:
-        return _txt2img_common.canvas_grid(view)
+        grid = _txt2img_common.canvas_grid(view)
     except SystemExit as e:
         raise SystemExit(str(e).replace("--H / --W", "--window").replace("--H x --W", "--window x --window"))
+    if grid is None and opt.disc_scale != 1.0:
+        raise SystemExit("--disc_scale %s needs --canvas HxW" % opt.disc_scale)
+    if grid is not None:
+        from sta import canvas
+        try:
+            canvas.check_disc_scale(grid, opt.disc_scale)
+        except ValueError as e:
+            raise SystemExit("--disc_scale %s: %s" % (opt.disc_scale, e))
+    return grid
 
 
 def check_options(opt):
@@ -290,7 +304,7 @@ def main(argv=None):
                                   unconditional_conditionings=[c[0] for c in conds], bboxs=[[l[n] for n in l] for _, _, l, _ in group],
                                   object_names=[list(l.keys()) for _, _, l, _ in group], local_conditionings=[c[2] for c in conds],
                                   unconditional_guidance_scale=opt.scale, seed=opt.seed, prompt_indices=[i for i, _, _, _ in group],
-                                  curr_texts=[p for _, p, _, _ in group], xin=xin, wrap=grid.wrap)
+                                  curr_texts=[p for _, p, _, _ in group], xin=xin, wrap=grid.wrap, disc_scale=opt.disc_scale)
         elif len(group) == 1:
             (i, p, l, _), (uc, c, local) = group[0], conds[0]
             names = list(l.keys())

@@ -20,6 +20,7 @@ import torch
 
 from . import attnmaps as _am
 from . import ops as _ops
+from . import prompt_state as _ps
 
 
 def layout_energy(maps, disc, valid):
@@ -47,7 +48,8 @@ class AttnLayoutLoss:
     otherwise: one attribute test per ordinary call, as `_attn_capture`). The readouts are AttnCapture's: begin(centres, texts,
     names, n_calls) derives the 2 K rows of attnmaps.token_weights over the prompts with local prompts "a photo of <name>", or
     set_readouts(...) fixes them. A readout counts iff its name tokens were found and it has an object; its disc is the object's
-    ops.disc_masks at the recording resolution.
+    ops.disc_masks at the recording resolution, with the radius of the prompt announced last (sta.prompt_state.disc_radius_sq: 0.2
+    image sides unless a canvas trajectory scales its discs).
 
     A new UNet call starts when a block records a second time (as AttnCapture recognises it) or when the sampler says so
     (next_call()). value() closes the open call and returns sum_images mean_k E_k over the calls recorded under plain autograd plus
@@ -101,7 +103,7 @@ class AttnLayoutLoss:
         valid = torch.zeros((I, R), dtype=torch.bool)
         found = torch.ones((I, R), dtype=torch.bool) if self.found is None else torch.as_tensor(self.found, dtype=torch.bool).reshape(-1, R).expand(I, R)
         for i in range(I):
-            masks = _ops.disc_masks(self.centres[i], res).float() if self.centres[i] else None
+            masks = _ops.disc_masks(self.centres[i], res, _ps.disc_radius_sq()).float() if self.centres[i] else None
             for r, o in enumerate(self.objects):
                 if o >= 0 and masks is not None:
                     disc[i, r] = masks[o]

@@ -11,7 +11,9 @@ window, then (uncond, cond): row 2 (p T + w) + r, the pair layout of PLMSSampler
 
 Layout: centres are normalised to the canvas (x in [0, 1] of the width, y of the height); window (j, i) gets
 ((x Wc - ox[i]) / s, (y Hc - oy[j]) / s), in Python floats, and its blocks rasterise that with the unchanged disc rule (sta.ops.disc_masks):
-the disc has radius 0.2 s latent pixels everywhere, and an object outside a window sets no mask bit there.
+the disc has radius 0.2 disc_scale s latent pixels in every window (`disc_scale`, a keyword of the samplers' canvas methods, default 1.0:
+0.2 s everywhere; an upscaled refine passes the upscale factor, so an object keeps its share of the canvas), and an object outside a
+window sets no mask bit there. `check_disc_scale` holds the one extra rule of a wrapped axis.
 
 Fuse: per canvas element the covering windows are summed in ascending w in fp32, starting from the first one's value, and divided by their
 count with an IEEE fp32 division; a 16-bit result is rounded to nearest even once. One writer per element: bit-reproducible.
@@ -33,6 +35,10 @@ dispatchers call the `_ring` siblings of the five entry points; a grid without w
 img2img on a canvas (`encode_step_windows`, restatement `encode_step_windows_reference`): from the VAE encoder's output on the whole canvas
 to the canvas state noised to the decode's start and the first call's window input pairs, one sta_vae_encode_step_windows launch
 (sta_vae_encode_step and sta_window_split in one); DDIMSampler.encode_step_canvas / decode_canvas are its users.
+
+The hi-res fix on a canvas (`upscale_step_windows`, restatement `upscale_step_windows_reference`): from a smaller latent, the x0 of a
+finished trajectory, to the bilinearly upscaled canvas state noised to the decode's start and the first call's window input pairs, one
+sta_latent_upscale_step_windows launch; DDIMSampler.upscale_step_canvas / hires_canvas are its users.
 
 Attention guidance on a canvas (`latent_guide_windows`, restatement `guide_windows_reference`, `guide_count`): the gradient of the
 attention-layout energy w.r.t. the window input pairs goes back to the canvas state through the split's adjoint (a sum over the covering
@@ -223,6 +229,77 @@ def encode_step_windows_reference(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, d
     z0 = sf * (mo[:, :4] + torch.exp(0.5 * mo[:, 4:].clamp(-30.0, 20.0)) * n_post)
     x = sa * z0 + s1m * n_enc
     return x, (z0 if want_z0 else None), (window_split_reference(x, grid, dtype or h.dtype) if want_xin else None)
+
+
+def check_disc_scale(grid, disc_scale):
+    """disc_scale (discs of radius 0.2 disc_scale window sides) on this grid -> float(disc_scale). ValueError unless it is positive and
+    finite, and on a wrapped axis of length L unless L - s >= 0.4 disc_scale s: a disc must not enter one window from both sides (at
+    disc_scale 1 the 1.5-window rule of the ring offsets already says so)."""
+    d = float(disc_scale)
+    if not 0.0 < d < float("inf"):
+        raise ValueError("disc_scale = %r must be positive and finite" % (disc_scale,))
+    for axis, L in (("x", grid.Wc), ("y", grid.Hc)):
+        if axis in grid.wrap and L - grid.s < 0.4 * d * grid.s:
+            raise ValueError("wrapped %s axis: length %d leaves %d beside a window of %d, less than a disc's diameter 0.4 x %g x %d (a disc "
+                             "could enter one window from both sides)" % (axis, L, L - grid.s, grid.s, d, grid.s))
+    return d
+
+
+def _upscale_taps(L_out, L_in, wrapped, device):
+    """The taps and weights of one axis of the bilinear upscale -> (i0, i1 long [L_out], l0, l1 float32 [L_out]); every operation is one
+    float32 torch operation, in the kernel's order."""
+    f32 = torch.float32
+    scale = torch.tensor(float(L_in), dtype=f32, device=device) / torch.tensor(float(L_out), dtype=f32, device=device)
+    src = (torch.arange(L_out, dtype=f32, device=device) + 0.5) * scale - 0.5
+    if not wrapped:
+        src = src.clamp_min(0.0)
+    fl = src.floor()
+    l1 = src - fl
+    l0 = 1.0 - l1
+    i0 = fl.to(torch.long)
+    if wrapped:
+        i0 = i0 % L_in
+        i1 = (i0 + 1) % L_in
+    else:
+        i0 = i0.clamp_max(L_in - 1)
+        i1 = (i0 + 1).clamp_max(L_in - 1)
+    return i0, i1, l0, l1
+
+
+def _check_upscale(z, noise, grid):
+    if z.dim() != 4 or z.dtype != torch.float32:
+        raise ValueError("upscale_step_windows: z must be a float32 latent [P, C, h, w], got %s %s" % (z.dtype, tuple(z.shape)))
+    P, C, h, w = z.shape
+    if h <= 0 or w <= 0 or h % 8 or w % 8:
+        raise ValueError("upscale_step_windows: the source %d x %d is not made of positive multiples of 8" % (h, w))
+    if grid.Hc < h or grid.Wc < w:
+        raise ValueError("upscale_step_windows: the canvas %d x %d is smaller than the source %d x %d (upscale only)" % (grid.Hc, grid.Wc, h, w))
+    if tuple(noise.shape) != (P, C, grid.Hc, grid.Wc):
+        raise ValueError("upscale_step_windows: noise %s must be [P, C, Hc, Wc] = %s" % (tuple(noise.shape), (P, C, grid.Hc, grid.Wc)))
+
+
+def upscale_step_windows_reference(z, noise, sa, s1m, grid, dtype=None, want_z_up=False, want_xin=True):
+    """The hi-res fix's entry into a canvas trajectory, restated: z [P, C, h, w] float32 (the x0 of a finished trajectory) -> (x, z_up,
+    xin). Per canvas element and axis (output length L_out, source length L_in), float32, one torch operation per rounding, in the
+    kernel's order: scale = float32(L_in) / float32(L_out); src = (d + 0.5) scale - 0.5; a clamped axis takes max(src, 0), i0 =
+    floor(src), i1 = min(i0 + 1, L_in - 1) — torch.nn.functional.interpolate(mode="bilinear", align_corners=False); a wrapped axis of
+    the grid does not clamp and takes both taps modulo L_in (index tensors: the source is itself closed on that axis and the filter
+    crosses the seam); l1 = src - i0, l0 = 1 - l1; z_up = l0y (l0x z00 + l1x z01) + l1y (l0x z10 + l1x z11); x = sa z_up + s1m noise.
+    x, z_up [P, C, Hc, Wc] float32 (z_up None unless want_z_up); xin (want_xin) = window_split_reference(x) in `dtype` (default: x's).
+    sa, s1m Python floats, rounded to float32 as the C-ABI takes them."""
+    _check_upscale(z, noise, grid)
+    f32 = torch.float32
+    z = z.detach()
+    noise = noise.detach().to(z.device, f32)
+    h, w = z.shape[-2:]
+    y0, y1, l0y, l1y = _upscale_taps(grid.Hc, h, "y" in grid.wrap, z.device)
+    x0, x1, l0x, l1x = _upscale_taps(grid.Wc, w, "x" in grid.wrap, z.device)
+    l0y, l1y = l0y[:, None], l1y[:, None]
+    r0, r1 = z[:, :, y0], z[:, :, y1]
+    z_up = l0y * (l0x * r0[..., x0] + l1x * r0[..., x1]) + l1y * (l0x * r1[..., x0] + l1x * r1[..., x1])
+    sa, s1m = (torch.tensor(float(v), dtype=f32, device=z.device) for v in (sa, s1m))
+    x = sa * z_up + s1m * noise
+    return x, (z_up if want_z_up else None), (window_split_reference(x, grid, dtype or x.dtype) if want_xin else None)
 
 
 def guide_count(grid, contributing, C):
@@ -463,3 +540,25 @@ def encode_step_windows(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, dtype=None,
     lib.check(fn(h.data_ptr(), qw.data_ptr(), qb.data_ptr(), n_post.data_ptr(), n_enc.data_ptr(), x.data_ptr(), _ptr(z0), _ptr(xin), P,
                  grid.Hc, grid.Wc, *_grid_args(grid), float(sf), float(sa), float(s1m), _DT[h.dtype], _stream(h)), name)
     return x, z0, xin
+
+
+def upscale_step_windows(z, noise, sa, s1m, grid, dtype=None, want_z_up=False, want_xin=True):
+    """A smaller latent z [P, C, h, w] float32 (the x0 of a finished trajectory, a square image or a canvas) -> (x, z_up, xin): the canvas
+    state x [P, C, Hc, Wc] float32, z upscaled bilinearly and noised to the decode's start (x = sa z_up + s1m noise), the upscaled latent
+    z_up (want_z_up) and the first UNet call's window input pairs xin [2 P T, C, s, s] in `dtype`, the UNet's 16-bit type (want_xin).
+    CUDA: ONE sta_latent_upscale_step_windows launch (the `_ring` sibling on a wrapped grid); CPU: upscale_step_windows_reference."""
+    if not z.is_cuda:
+        return upscale_step_windows_reference(z, noise, sa, s1m, grid, dtype, want_z_up, want_xin)
+    _check_upscale(z, noise, grid)
+    if want_xin and dtype not in _DT:
+        raise TypeError("sta_latent_upscale_step_windows writes 16-bit window inputs (dtype %s)" % dtype)
+    P, C, h, w = z.shape
+    z = z.detach().contiguous()
+    noise = noise.detach().to(device=z.device, dtype=torch.float32).contiguous()
+    x = torch.empty((P, C, grid.Hc, grid.Wc), dtype=torch.float32, device=z.device)
+    z_up = torch.empty_like(x) if want_z_up else None
+    xin = torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=z.device) if want_xin else None
+    fn, name = _entry("sta_latent_upscale_step_windows", grid)
+    lib.check(fn(z.data_ptr(), noise.data_ptr(), x.data_ptr(), _ptr(z_up), _ptr(xin), P, C, h, w, grid.Hc, grid.Wc, *_grid_args(grid),
+                 float(sa), float(s1m), _DT[dtype] if want_xin else lib.STA_F16, _stream(z)), name)
+    return x, z_up, xin

@@ -24,7 +24,8 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # attention-guided sampling and is built with the sampler step (no -ffinite-math-only there: it tests for Inf / NaN).
 # sta_window.hip (sta_window_split / sta_window_fuse / sta_sampler_step_windows and their inpainting forms sta_sampler_step_windows_masked /
 # sta_window_blend, and the entry of img2img sta_vae_encode_step_windows, whose per-pixel arithmetic csrc/sta_encode_dev.h shares with
-# sta_encode.hip, and the canvas form of the guidance update sta_latent_guide_windows: canvases sampled as overlapping windows) runs the sampler step on overlap means and is built with it for the same
+# sta_encode.hip, the canvas form of the guidance update sta_latent_guide_windows, and the entry of the hi-res fix sta_latent_upscale_step_windows, which
+# takes its noising from the same header: canvases sampled as overlapping windows) runs the sampler step on overlap means and is built with it for the same
 # reason: no fast-math flag (its mean is a correctly rounded fp32 division). The step itself and the helpers of all three are defined
 # once, in csrc/sta_step_dev.h, which sta_inpaint.hip includes as well. sta_rows640.hip (sta_rows_c640: the level-1 Linear + residual
 # (+ LayerNorm) pass) is the C = 640 sibling of sta_rowgemm.hip's kernel and shares its headers and -ffinite-math-only. sta_rowstail.hip
@@ -56,7 +57,7 @@ NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip"
                     "sta_unet.hip": ("gn_nhwc_apply_kernel", "gn_nhwc_stats_kernel"),
                     "sta_sampler.hip": ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel",
                                         "sampler_step_windows_masked_kernel", "window_blend_kernel", "vae_encode_step_windows_kernel",
-                                        "latent_guide_windows_kernel")}
+                                        "latent_guide_windows_kernel", "latent_upscale_step_windows_kernel")}
 
 STA_BF16, STA_F16 = 0, 1
 STA_MX8_GEGLU, STA_MX8_MX_OUT = 1, 2
@@ -184,6 +185,9 @@ SYMBOLS = {
     # attention guidance on a canvas: the window pairs' gradient -> the updated canvas state + the next window inputs
     "sta_latent_guide_windows": (_i, [_vp] * 8 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i, _f, _i, _vp]),
     "sta_latent_guide_windows_ring": (_i, [_vp] * 8 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    # the hi-res fix on a canvas: a smaller latent -> the upscaled, noised canvas state + first window inputs
+    "sta_latent_upscale_step_windows": (_i, [_vp] * 5 + [_l] + [_i] * 7 + [_vp, _vp, _i, _f, _f, _i, _vp]),
+    "sta_latent_upscale_step_windows_ring": (_i, [_vp] * 5 + [_l] + [_i] * 7 + [_vp, _vp, _i, _i, _f, _f, _i, _vp]),
 }
 
 

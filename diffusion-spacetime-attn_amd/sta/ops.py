@@ -57,9 +57,9 @@ def mask_bits(mask_kn):
     return (mask_kn.to(torch.int32).ne(0).to(torch.int32) * weights).sum(0).to(torch.uint8)
 
 
-def disc_mask_bits(centres, dim):
+def disc_mask_bits(centres, dim, radius_sq=0.04):
     """Disc masks of all objects as the [N] uint8 bit field (CPU tensor)."""
-    return mask_bits(disc_masks(centres, dim))
+    return mask_bits(disc_masks(centres, dim, radius_sq))
 
 
 class PackedKV:

@@ -19,14 +19,21 @@ class _State:
         self.version = 0
         self.local_ctx = None      # list of [1, M, Dc] tensors or None (-> file side channel)
         self.first_timestep = 981  # first DDIM timestep of a 50-step schedule (attention.py:240)
+        self.disc_radius = 0.2     # the discs' radius in sides of the image a block sees (attention.py:251-262: 0.2)
 
 
 _STATE = _State()
 
 
-def begin_prompt(local_ctx=None, first_timestep=None):
-    """Announce a new prompt. `local_ctx`: list of K tensors [1, M, Dc] ("a photo of <object i>")."""
+def begin_prompt(local_ctx=None, first_timestep=None, disc_radius=0.2):
+    """Announce a new prompt. `local_ctx`: list of K tensors [1, M, Dc] ("a photo of <object i>"). `disc_radius`: the radius of the
+    objects' discs in sides of the image a block sees, for this prompt (every announcement sets it: 0.2, the reference's, unless a canvas
+    trajectory passes 0.2 disc_scale)."""
+    disc_radius = float(disc_radius)
+    if not 0.0 < disc_radius < float("inf"):
+        raise ValueError("disc_radius = %r must be positive and finite" % (disc_radius,))
     _STATE.version += 1
+    _STATE.disc_radius = disc_radius
     if local_ctx is None:
         _STATE.local_ctx = None
     else:
@@ -42,6 +49,13 @@ def version():
 
 def first_timestep():
     return _STATE.first_timestep
+
+
+def disc_radius_sq():
+    """What dx^2 + dy^2 is compared against by everything that rasterises this prompt's discs (sta.ops.disc_masks' radius_sq): 0.04, the
+    constant of attention.py:251-262, at the radius 0.2, so that those masks are the bits they have always been; radius^2 otherwise."""
+    r = _STATE.disc_radius
+    return 0.04 if r == 0.2 else r * r
 
 
 def local_contexts(num_objects, n_img, device, dtype):

@@ -430,6 +430,22 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  * sta_latent_guide_windows_ring takes `int wrap` directly after s (wrap = 0: the sibling, bit for bit).
  * Rules (STA_E_ARG with text, nothing launched): the grid rules above; g, x, step, count, x_out non-NULL; g, x, keep, x_out, xin 16-byte
  * aligned (step, count, stats: 4-byte); no output may overlap an input or another output; wrap in 0 .. 3; dtype STA_BF16 / STA_F16.
+ *
+ * The hi-res fix on a canvas: sta_latent_upscale_step_windows goes from a smaller latent (the x0 of a finished trajectory, a square image or
+ * a canvas) to the upscaled canvas state, noised to the decode's start, and the first UNet call's window inputs in one launch.
+ *   z: [P][C][h][w] fp32;  noise, x, z_up: [P][C][Hc][Wc] fp32 (z_up may be NULL);  xin: NULL, or [2 P T][C][s][s] dtype = the rounded x in
+ *   both rows of every covering window's pair, in sta_window_split's order.
+ * Per canvas element and axis (output length L_out, source length L_in), fp32, every operation rounded on its own (no contraction):
+ *     scale = (float)L_in / (float)L_out;  src = (d + 0.5f) * scale - 0.5f
+ *     clamped axis: src = max(src, 0), i0 = floor(src), i1 = min(i0 + 1, L_in - 1)
+ *     wrapped axis (a set bit of wrap): no clamp, i0 = floor(src), both taps modulo L_in (the source is itself closed on that axis)
+ *     l1 = src - i0, l0 = 1 - l1
+ *     z_up = l0y (l0x z00 + l1x z01) + l1y (l0x z10 + l1x z11)
+ *     x    = sqrt_a z_up + sqrt_1ma noise      (the noising of sta_vae_encode_step: one device definition, csrc/sta_encode_dev.h)
+ * which is torch.nn.functional.interpolate(mode="bilinear", align_corners=False) on the clamped axes. No LDS, no atomics, one writer per
+ * element. sta_latent_upscale_step_windows_ring takes `int wrap` directly after s (wrap = 0: the sibling, bit for bit).
+ * Rules (STA_E_ARG with text, nothing launched): z, noise, x non-NULL; the grid rules above; h, w positive multiples of 8; Hc >= h and
+ * Wc >= w (upscale only); z, noise, x, z_up, xin 16-byte aligned; wrap in 0 .. 3; dtype STA_BF16 / STA_F16.
  */
 #define STA_MAX_WINDOW_OFFSETS 16
 #define STA_SRC_F32 2
@@ -472,6 +488,12 @@ int sta_latent_guide_windows(const void* g, const float* x, const float* keep, c
 int sta_latent_guide_windows_ring(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out,
                                   void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
                                   int wrap, int normalize, float inv_scale, int dtype, void* stream);
+int sta_latent_upscale_step_windows(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
+                                    int Wc, int ny, int nx, const int* oy, const int* ox, int s, float sqrt_a, float sqrt_1ma, int dtype,
+                                    void* stream);
+int sta_latent_upscale_step_windows_ring(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
+                                         int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float sqrt_a, float sqrt_1ma,
+                                         int dtype, void* stream);
 
 /*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows
