@@ -34,6 +34,7 @@
 #include "sta_internal.h"
 #include "sta_xattn_dev.h"
 #include "sta_wring_dev.h"
+#include "sta_rows_dev.h"
 
 namespace {
 

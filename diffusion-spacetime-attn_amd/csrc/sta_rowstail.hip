@@ -12,24 +12,19 @@
 // proj_out is no launch of its own. The per-image, per-channel sums the next GroupNorm needs leave in the epilogue, as they do from
 // gemm_rows_kernel today.
 //
-// Structure: that of csrc/sta_rows640.hip. Rows are the MFMA columns; persistent workgroups of 8 waves; a wave owns 32 rows (two
-// 16-row items) x 320 output channels = 2 x 20 accumulator tiles (160 registers), every weight fragment it reads from LDS serves both
-// items.
-//   C = 640: 4 row groups x 2 column halves, 128 rows per pass, 100 k-steps (80 of h, 20 of x2), 40 fragments (40 KiB) per k-step.
-//   C = 320: 8 row groups, no column halves, 256 rows per pass, 50 k-steps (40 of h, 10 of x2), 20 fragments (20 KiB) per k-step:
-//            the weight is streamed once per 256 rows.
-//   A operand = [W' | Wp] [C][inner + C] re-laid out once per model (rows_tail_pack_kernel): fragment (k-step f, row tile u) at [f][u],
-//               lane (g, c) holding row frag_sigma(u, c), columns 32 f + 8 g .. + 7; streamed through the 2-slot ring one k-step ahead.
-//   B operand = requested two k-steps ahead into one of four register sets. x2 and (C = 640) h are row-major: lane (g, c) = the 16
-//               bytes of row c at channel 32 f + 8 g. At C = 320 h arrives in the fragment order sta_ff_geglu_qfrag(h_frag = 1)
-//               writes: one coalesced 1-KiB load per (item, k-step). The source switches from h to x2 at k-step inner / 32.
+// Structure: the skeleton of csrc/sta_rows_dev.h (RowsShape<C>, the weight [W' | Wp] [C][inner + C] packed by rows_pack_kernel) with
+// its counted-wait invariant.
+//   C = 640: 100 k-steps (80 of h, 20 of x2).
+//   C = 320: 50 k-steps (40 of h, 10 of x2); the weight is streamed once per 256 rows.
+//   B operand = x2 and (C = 640) h are row-major: lane (g, c) = the 16 bytes of row c at channel 32 f + 8 g. At C = 320 h arrives in
+//               the fragment order sta_ff_geglu_qfrag(h_frag = 1) writes: one coalesced 1-KiB load per (item, k-step). The source
+//               switches from h to x2 at k-step inner / 32.
 // 50 k-steps are no multiple of the four register sets: at C = 320 the last two k-steps of a pass (sets 0 and 1) request the next
 // pass's first two BEHIND their own MFMAs, into the sets they just released, so that every pass starts with set 0; those loads land
 // under the epilogue.
 //
 // Roofline, level 0: 2 * 1600 * 320 flop per row against 2560 + 3 x 640 bytes: 229 flop/B; level 1: 4.1 MFLOP against 5120 + 3 x 1280
 // bytes: 457 flop/B — both between the two limits.
-
 //
 // Not a translation unit of its own: #included at the end of sta_ffgemm.hip (sta/lib.py::INCLUDED_SOURCES), whose headers, flags
 // (-ffinite-math-only) and hazard lint it shares.
@@ -37,37 +32,18 @@
 namespace {
 
 template <int C_>
-struct TailShape {
-  static_assert(C_ == 320 || C_ == 640, "SD-v1 level 0 or level 1");
-  static constexpr int C = C_, INNER = 4 * C, K = INNER + C;
-  static constexpr int NW = 8;
-  static constexpr int NH = C / 320;                 // column halves: 1 | 2
-  static constexpr int NG = NW / NH;                 // row groups of 32 rows: 8 | 4
-  static constexpr int ROWS = 32 * NG;               // rows per workgroup pass: 256 | 128
-  static constexpr int NRT = C / 16;                 // output row tiles = the fragments of one k-step: 20 | 40
-  static constexpr int HT = 20;                      // tiles per wave (320 channels)
-  static constexpr int NTP = HT / 2;                 // tile pairs per wave
-  static constexpr int QF = 5;                       // operand fragments read per group
+struct TailShape : RowsShape<C_> {
+  using RowsShape<C_>::C;
+  using RowsShape<C_>::SLOT;
+  static constexpr int INNER = 4 * C, K = INNER + C;
   static constexpr int NKS_H = INNER / 32;           // k-steps that read h: 40 | 80
   static constexpr int NKS = K / 32;                 // 50 | 100
   static constexpr bool HFRAG = C == 320;            // h in fragment order
   static constexpr unsigned HSTEP = HFRAG ? (unsigned)FRAG : 64u;      // bytes from one k-step of h to the next, per lane
-  using Ring = WRing<NW, NRT>;                       // 3 (4 padding copies) | 5 LDS-DMA instructions per wave per k-step
-  static constexpr int SLOT = Ring::SLOT;            // 24 | 40 KiB
   static constexpr int TAB = C * 4;                  // b' in fp32, behind the ring
   static constexpr int LDS = 2 * SLOT + TAB;
   static_assert(NKS % 2 == 0 && NKS_H % 2 == 0, "the ring slot of k-step 0 is slot 0 in every pass");
 };
-
-// [W' | Wp] [C][K] -> [k-step f][row tile u] fragments: lane (g, c) holds W[frag_sigma(u, c)][32 f + 8 g .. + 7]
-template <typename T>
-__global__ __launch_bounds__(64) void rows_tail_pack_kernel(const T* __restrict__ w, T* __restrict__ packed, int K, int nrt) {
-  const int fr = blockIdx.x;                   // f * nrt + u
-  const int f = fr / nrt, u = fr % nrt;
-  const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
-  const typename Tr<T>::V8 x = *(const typename Tr<T>::V8*)(w + (size_t)frag_sigma(u, c) * K + 32 * f + 8 * g);
-  *(typename Tr<T>::V8*)(packed + (size_t)fr * (FRAG / 2) + lane * 8) = x;
-}
 
 struct RT {
   const char* h;        // [R][inner] row-major (C = 640) or fragment order [R / 16][inner / 32][1 KiB] (C = 320)
@@ -81,13 +57,8 @@ struct RT {
   unsigned rows_img;
 };
 
-// THE counted-wait invariant of this kernel (that of rows640_kernel). vmcnt counts a wave's own memory instructions in issue order;
-// the waits in front of the barriers name "this k-step's DMA" only because every wave issues the same instructions on every path:
-//   - per k-step Ring::PER LDS-DMA copies (the spare positions of C = 320 copy too) and, behind them, the two B loads of k-step + 2
-//     (of the next pass's first two k-steps behind the last two; rows past R or no next pass: an offset the descriptor drops);
-//   - per pass 20 residual loads, 20 stores and, with statistics, 10 more stores (lanes that hold no piece: a dropped offset).
-// Hence vmcnt(2) in front of a k-step (the two B loads issued behind its DMA may fly) and vmcnt(20 | 30) in front of a pass's first
-// (the previous epilogue's stores may fly; its loads, the B loads and the DMA of k-step 0 are all older than those).
+// The counted-wait invariant of sta_rows_dev.h with this kernel's numbers: per pass 20 residual loads, 20 stores and, with
+// statistics, 10 more stores (lanes that hold no piece: a dropped offset): NST = 20 | 30.
 template <typename T, int C>
 __global__ __launch_bounds__(64 * TailShape<C>::NW, 2) void rows_tail_kernel(const RT p) {
   using S = TailShape<C>;
@@ -101,13 +72,7 @@ __global__ __launch_bounds__(64 * TailShape<C>::NW, 2) void rows_tail_kernel(con
   const __amdgpu_buffer_rsrc_t w_srd = make_srd(p.w, (unsigned)(S::NKS * S::NRT * FRAG));
   const unsigned lane16 = (unsigned)lane * 16u;
   auto stage = [&](int ks, int slot) __attribute__((always_inline)) {      // the fragments of k-step `ks` into ring slot `slot`
-#pragma unroll
-    for (int i = 0; i < S::Ring::PER; ++i) {
-      const int f = wv + S::NW * i;
-      const int fs = (i + 1) * S::NW <= S::NRT ? f : (f < S::NRT ? f : 0);       // (the spare positions copy fragment 0 into the slot's padding)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(w_srd, (__attribute__((address_space(3))) void*)(ring + slot * S::SLOT + f * FRAG), 16, lane16,
-                                               (unsigned)((ks * S::NRT + fs) * FRAG), 0, 0);
-    }
+    S::Ring::template stage<true>(w_srd, ring + slot * S::SLOT, 0u, ks * S::NRT, wv, lane16);
   };
   // (tensors of 4 GiB and above are refused by the host wrapper: 32-bit buffer offsets)
   const unsigned cbytes = (unsigned)((size_t)p.R * C * sizeof(T));
@@ -128,11 +93,6 @@ __global__ __launch_bounds__(64 * TailShape<C>::NW, 2) void rows_tail_kernel(con
     const int r0 = (blk * S::NG + rg) * 32 + 16 * it;
     return ((blk < nblk) & (r0 < R)) ? (unsigned)(r0 + (ln & 15)) * (unsigned)(C * sizeof(T)) + (unsigned)(ln >> 4) * 16u : SRD_DROP;
   };
-  auto opaque_lane = [&]() __attribute__((always_inline)) {
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    return ln;
-  };
   V8 b[4][2];                                  // B operands of four consecutive k-steps, both items
   stage(0, 0);
 #pragma unroll
@@ -144,7 +104,7 @@ __global__ __launch_bounds__(64 * TailShape<C>::NW, 2) void rows_tail_kernel(con
   const char* lbase = ring + hf * (S::HT * FRAG) + lane * 16;
 
   for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    const int lp = opaque_lane();
+    const int lp = rows_opaque_lane(lane);
     const unsigned vh[2] = {h_off(blk, 0, lp), h_off(blk, 1, lp)}, vx[2] = {x_off(blk, 0, lp), x_off(blk, 1, lp)};
     unsigned vn[2] = {0u, 0u};                  // the next pass's (C = 320: derived where they are used, no register across the loop)
     if constexpr (S::NKS % 4 == 0) { vn[0] = h_off(blk + gridDim.x, 0, lp); vn[1] = h_off(blk + gridDim.x, 1, lp); }
@@ -172,22 +132,9 @@ __global__ __launch_bounds__(64 * TailShape<C>::NW, 2) void rows_tail_kernel(con
 #pragma unroll
         for (int it = 0; it < 2; ++it) b[(J + 2) & 3][it] = srd_load16<V8>(srd, nxt ? vn[it] : xs ? vx[it] : vh[it], so);
       }
-      const V8* fr = (const V8*)(lbase + SLOT * S::SLOT);
-#pragma unroll
-      for (int q = 0; q < S::HT / S::QF; ++q) {
-        V8 wa[S::QF];
-#pragma unroll
-        for (int t = 0; t < S::QF; ++t) wa[t] = fr[(S::QF * q + t) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < S::QF; ++t) {
-          acc[0][S::QF * q + t] = Tr<T>::mfma(wa[t], b[J][0], acc[0][S::QF * q + t]);
-          acc[1][S::QF * q + t] = Tr<T>::mfma(wa[t], b[J][1], acc[1][S::QF * q + t]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      rows_mfma_step<T, S::HT, S::QF>((const V8*)(lbase + SLOT * S::SLOT), b[J][0], b[J][1], acc);
       if constexpr (TAIL) {                    // k-step J of the next pass into the set this k-step is done with: still two loads behind the DMA
-        const int lt = opaque_lane();
+        const int lt = rows_opaque_lane(lane);
 #pragma unroll
         for (int it = 0; it < 2; ++it) b[J][it] = srd_load16<V8>(h_srd, h_off(blk + gridDim.x, it, lt), S::HSTEP * (unsigned)J);
       }
@@ -211,10 +158,7 @@ __global__ __launch_bounds__(64 * TailShape<C>::NW, 2) void rows_tail_kernel(con
     }
     // ---- epilogue: + b' + x_in, 16-byte stores. ALWAYS 20 loads and 20 stores ---------------------------------------------------
     const int rbase = (blk * S::NG + rg) * 32;             // wave-uniform
-    // the lane's coordinates again, opaque to hipcc: what the epilogue derives from them is then computed here and not kept in
-    // registers across the MFMA loop
-    const int le = opaque_lane();
-    const int ge = le >> 4, ce = le & 15;
+    const int le = rows_opaque_lane(lane), ge = le >> 4, ce = le & 15;       // (the epilogue's offsets are derived here, not across the MFMA loop)
     constexpr int XG = 10;                     // residual loads in flight per item
     V8 xv[XG];
 #pragma unroll
@@ -288,13 +232,7 @@ int sta_ff_tail_pack_w(const void* wcat, void* packed, int C, int inner, int dty
   g_sta_err[0] = 0;
   if (!wcat || !packed) return sta_fail(STA_E_ARG, "null pointer");
   if (sta_ff_tail_packed_w_bytes(C, inner) == 0) return sta_fail(STA_E_UNSUP, TAIL_SHAPES, C, inner);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
-  hipStream_t st = (hipStream_t)stream;
-  const int K = inner + C, nrt = C / 16;
-  return sta_by_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    return sta_launch<rows_tail_pack_kernel<T>>("pack_rows_tail launch", dim3((K / 32) * nrt), dim3(64), 0, st, (const T*)wcat, (T*)packed, K, nrt);
-  });
+  return rows_pack_w("pack_rows_tail launch", wcat, packed, C, inner + C, dtype, STA_E_UNSUP, stream);
 }
 
 int sta_ff_tail(const void* h, const void* x2, const void* packed_w, const float* bias, const void* x_in, void* out, float* stats,
@@ -302,17 +240,12 @@ int sta_ff_tail(const void* h, const void* x2, const void* packed_w, const float
   g_sta_err[0] = 0;
   if (sta_ff_tail_packed_w_bytes(C, inner) == 0) return sta_fail(STA_E_UNSUP, TAIL_SHAPES, C, inner);
   if (!h || !x2 || !packed_w || !x_in || !out) return sta_fail(STA_E_ARG, "null pointer");
-  if (R <= 0 || R % 16) return sta_fail(STA_E_ARG, "ff_tail: R=%ld (need a positive multiple of 16 rows)", R);
-  if ((size_t)R * inner * 2 >= 0xfffffff0ull) return sta_fail(STA_E_UNSUP, "activations must stay below 4 GiB (R=%ld)", R);
-  if (max_workgroups < 0) return sta_fail(STA_E_ARG, "ff_tail: max_workgroups=%d", max_workgroups);
-  if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_UNSUP, "dtype %d", dtype);
+  if (const int rc = rows_refuse("ff_tail", R, (size_t)inner * 2, max_workgroups, dtype, STA_E_UNSUP)) return rc;
   const long rows = C == 320 ? TailShape<320>::ROWS : TailShape<640>::ROWS;
   if (stats && (rows_per_image <= 0 || rows_per_image % rows || R % rows_per_image))
     return sta_fail(STA_E_ARG, "ff_tail: rows_per_image=%ld (statistics need a multiple of the pass height %ld that divides R=%ld)", rows_per_image, rows, R);
   RT p{(const char*)h, (const char*)x2, (const char*)packed_w, bias, x_in, out, stats, R, stats ? (unsigned)rows_per_image : 0u};
-  const long nblk = (R + rows - 1) / rows;
-  const long cap = max_workgroups > 0 && max_workgroups < 256 ? max_workgroups : 256;     // one persistent workgroup per CU
-  const unsigned grid = (unsigned)(nblk < cap ? nblk : cap);
+  const unsigned grid = rows_grid(R, rows, max_workgroups);
   hipStream_t st = (hipStream_t)stream;
   return sta_by_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);

@@ -1,5 +1,6 @@
 // sta_wring_dev.h — the device-side pieces the streamed-weight passes share (sta_rowgemm.hip, sta_ffgemm.hip, sta_lnqkv.hip,
-// sta_gemm.hip, sta_conv.hip): the 2-slot LDS weight ring, the row permutation of their packed weights, the wave reduction of
+// sta_gemm.hip, sta_conv.hip; sta_rows_dev.h builds the skeleton of sta_rows640.hip and sta_rowstail.hip on them): the 2-slot LDS
+// weight ring, the row permutation of their packed weights, the wave reduction of
 // the LayerNorm kernels, the DPP row sum of the statistics epilogues, the dropped buffer offset and a compile-time loop. gfx950 only. Needs nothing but the HIP runtime, so
 // the glue kernels (sta_unet.hip, sta_unet_bwd.hip) take wave_sum from here too.
 #ifndef STA_WRING_DEV_H
@@ -69,12 +70,17 @@ struct WRing {
   // (the buffer form keeps the per-lane part of the address in ONE register, the fragment is a scalar offset). A caller gives the
   // chunk's position in ONE of the two units and 0 in the other — the row passes count fragments (signed: (first + f) * FRAG),
   // sta_gemm.hip / sta_conv.hip bytes (unsigned: src + f * FRAG); hipcc selects different scalar code for the two spellings, and each
-  // kernel keeps the one it was tuned and measured with.
+  // kernel keeps the one it was tuned and measured with. The same holds for the select of the spare positions: written for every
+  // position, hipcc emits a scalar compare + select even where i alone shows that the position is never spare. STATIC_SPARE
+  // leaves the select to the positions that can be spare. The row passes of sta_rows_dev.h were tuned and measured that way and
+  // pass `true`; every other user was tuned with the plain form, and turning the flag on there changes hot machine code: it
+  // wants its own measurement (profiles/rows_one_core.md).
+  template <bool STATIC_SPARE = false>
   static __device__ __forceinline__ void stage(__amdgpu_buffer_rsrc_t srd, char* slot, unsigned src, int first, int wv, unsigned lane16) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const int f = wv + NW * i;
-      const int fs = f < NFR ? f : 0;
+      const int fs = (STATIC_SPARE && (i + 1) * NW <= NFR) || f < NFR ? f : 0;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (__attribute__((address_space(3))) void*)(slot + f * FRAG), 16, lane16,
                                                src + (unsigned)((first + fs) * FRAG), 0, 0);
     }

@@ -30,7 +30,8 @@ SOURCES = [os.path.join(CSRC, n) for n in ("sta_xattn.hip", "sta_xattn_bwd.hip",
 # once, in csrc/sta_step_dev.h, which sta_inpaint.hip includes as well. sta_rows640.hip (sta_rows_c640: the level-1 Linear + residual
 # (+ LayerNorm) pass) is the C = 640 sibling of sta_rowgemm.hip's kernel and shares its headers and -ffinite-math-only. sta_rowstail.hip
 # (sta_ff_tail: the feed-forward output Linear + proj_out of a SpatialTransformer as one pass) continues the feed-forward passes of
-# sta_ffgemm.hip and is built with them: the set of translation units is pinned (tests/test_abi_dtype_cpu.py).
+# sta_ffgemm.hip and is built with them: the set of translation units is pinned (tests/test_abi_dtype_cpu.py). What these two row
+# passes share (shape traits, pack kernel, MFMA block, counted-wait invariant, host-side refusals and grid) is csrc/sta_rows_dev.h.
 INCLUDED_SOURCES = {"sta_xattn_maps_bwd.hip": "sta_xattn_bwd.hip", "sta_guide.hip": "sta_sampler.hip", "sta_window.hip": "sta_sampler.hip",
                     "sta_rows640.hip": "sta_rowgemm.hip", "sta_rowstail.hip": "sta_ffgemm.hip"}
 

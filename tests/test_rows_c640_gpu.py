@@ -145,6 +145,29 @@ def test_rows_c640_refusals():
     assert not fused.rows_c640_supported(x[:R], torch.nn.Linear(640, 640).to("cuda", torch.bfloat16))
 
 
+@pytest.mark.parametrize("entry,c,K", [("rows_c640", 640, 640), ("rows_c640", 640, 2560), ("ff_tail", 320, 1600), ("ff_tail", 640, 3200)])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_row_pass_packed_weight_layout(entry, c, K, dtype):
+    """The packed image both row passes stream (csrc/sta_rows_dev.h::rows_pack_kernel, behind sta_rows_c640_pack_w and sta_ff_tail_pack_w)
+    at every shape the two entry points accept, bit for bit against the layout restated in numpy: fragment f * nrt + u (nrt = C / 16),
+    lane (g, c), the 8 values W[frag_sigma(u, c)][32 f + 8 g .. + 7]. The weight is a hash of the flat index, as 16-bit patterns (the
+    pack is a copy: NaN patterns travel like any other), so a transposed or shifted index shows."""
+    from sta import fused
+    idx = np.arange(c * K, dtype=np.uint64)
+    bits = (((idx * np.uint64(2654435761)) >> np.uint64(7)) & np.uint64(0xffff)).astype(np.uint16).view(np.int16).reshape(c, K)
+    w = torch.from_numpy(bits).view(dtype).cuda()
+    packed = fused.pack_rows_c640_weight(w) if entry == "rows_c640" else fused.pack_ff_tail_weight(w)
+    torch.cuda.synchronize()
+    nrt, nks = c // 16, K // 32
+    assert packed.dtype == torch.uint8 and packed.numel() == c * K * 2
+    got = packed.cpu().numpy().view(np.int16).reshape(nks, nrt, 4, 16, 8)              # [f][u][g][c][8]
+    u, rho = np.arange(nrt)[:, None], np.arange(16)[None, :]
+    sigma = 32 * (u >> 1) + 8 * (rho >> 2) + 4 * (u & 1) + (rho & 3)                     # frag_sigma(u, c): [nrt][16]
+    col = 32 * np.arange(nks)[:, None, None] + 8 * np.arange(4)[None, :, None] + np.arange(8)[None, None, :]     # [f][g][8]
+    want = bits[sigma[None, :, None, :, None], col[:, None, :, None, :]]
+    assert want.shape == got.shape and np.array_equal(got, want)
+
+
 @pytest.mark.parametrize("K", [640, 2560])
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_rows_c640_graph_replay_is_bit_equal(dtype, K):
