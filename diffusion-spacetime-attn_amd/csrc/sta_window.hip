@@ -1,9 +1,9 @@
 // sta_window.hip — wide canvases sampled as overlapping square windows (gfx950). C-ABI in include/sta_unet.h (sta_window_split /
 // sta_window_fuse / sta_sampler_step_windows / sta_sampler_step_windows_masked / sta_window_blend / sta_vae_encode_step_windows /
-// sta_latent_guide_windows, and their
-// `_ring` siblings for canvases that close on themselves: WRAP, a compile-time mask of the cyclic axes, 0 in the clamped entry points). #included at the end of
-// sta_sampler.hip (its flags: no fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division). The step on the overlap means
-// is step1 of sta_step_dev.h, the definition the square kernels use, with that header's V8T / F4 / load8 / store8 / round8 / StepCoef.
+// sta_latent_guide_windows / sta_latent_upscale_step_windows; each takes `wrap`, the mask of the axes on which the canvas closes on
+// itself, which the kernels take at compile time as WRAP: 0 = the clamped grid). #included at the end of sta_sampler.hip (its flags: no
+// fast-math flag of any kind, the overlap mean relies on hipcc's correctly rounded fp32 division). The step on the overlap means is
+// step1 of sta_step_dev.h, the definition the square kernels use, with that header's V8T / F4 / load8 / store8 / round8 / StepCoef.
 // Conventions of sta_sampler.hip: 256-lane groups, grid-stride, a lane owns 8 consecutive elements of one CANVAS row, 16-byte loads and
 // stores, fp32 arithmetic. Window sides, offsets and canvas sides are multiples of 8, so a lane's vector lies inside or outside a window
 // as a whole. The offset tables travel by value in the kernel arguments: nothing device-side to fill, the launches are capturable.
@@ -11,12 +11,12 @@
 // one writer per output element, the same bits from launch to launch.
 // Inpainting on a canvas (sta_sampler_step_windows_masked / sta_window_blend): the blend is blend1 of sta_blend_dev.h, the definition
 // sta_inpaint.hip uses for square images.
-// img2img on a canvas (sta_vae_encode_step_windows and its `_ring` sibling): from the encoder's output on the whole canvas to the canvas
+// img2img on a canvas (sta_vae_encode_step_windows): from the encoder's output on the whole canvas to the canvas
 // state and the first call's window inputs in one launch; the per-pixel arithmetic is sta_encode_dev.h's, the definition
 // sta_vae_encode_step (sta_encode.hip) uses for square images.
-// Attention guidance on a canvas (sta_latent_guide_windows and its `_ring` sibling): the adjoint of the split applied to the window pairs'
+// Attention guidance on a canvas (sta_latent_guide_windows): the adjoint of the split applied to the window pairs'
 // gradient, then sta_latent_guide's update (sta_guide.hip, included before this file: its guide_overlap and GUIDE_MAX_PARTS) and the split.
-// The hi-res fix on a canvas (sta_latent_upscale_step_windows and its `_ring` sibling): a smaller latent upscaled bilinearly to the canvas
+// The hi-res fix on a canvas (sta_latent_upscale_step_windows): a smaller latent upscaled bilinearly to the canvas
 // (on a wrapped axis across the seam), noised with sta_encode_dev.h's noise1 and split, one launch.
 
 #include "sta_blend_dev.h"
@@ -62,26 +62,36 @@ __device__ __forceinline__ int window_dist(int at, int o, int L) {
   return d;
 }
 
-// sum over the covering windows of pair row r (ascending w, fp32, starting from the first one's value) -> count.
-// WRAP: the cyclic axes, bit 0 = x (length Wc), bit 1 = y (length Hc); 0 = the clamped grid
-template <typename T, int WRAP>
-__device__ __forceinline__ int gather_sum(const T* __restrict__ eps, const WinGrid& g, long p, int r, int C, int Hc, int Wc, const CanvasPos& q,
-                                          float* acc) {
-  using V8 = typename V8T<T>::type;
-  const long T_ = (long)g.ny * g.nx;
-  int n = 0;
+// The windows that cover the lane's vector at q, visited in ascending w = j nx + i: body(j, i, dy, dx) with (dy, dx) the vector's position
+// inside window (j, i). The one statement of the rule that the bit-for-bit determinism of every canvas launch rests on.
+// WRAP: the cyclic axes, bit 0 = x (length Wc), bit 1 = y (length Hc); 0 = the clamped grid.
+// The bodies are lambdas marked always_inline, so that walk and body are inlined in the same pass (profiles/window_one_entry.md).
+template <int WRAP, typename F>
+__device__ __forceinline__ void for_covering_windows(const WinGrid& g, int Hc, int Wc, const CanvasPos& q, F&& body) {
   for (int j = 0; j < g.ny; ++j) {
     const int dy = window_dist<(WRAP & 2) != 0>(q.y, g.oy[j], Hc);
     if ((unsigned)dy >= (unsigned)g.s) continue;
     for (int i = 0; i < g.nx; ++i) {
       const int dx = window_dist<(WRAP & 1) != 0>(q.x, g.ox[i], Wc);
       if ((unsigned)dx >= (unsigned)g.s) continue;
-      const V8 e = *(const V8*)(eps + window_at(2 * (p * T_ + j * g.nx + i) + r, C, q.c, g.s, dy, dx));
-#pragma unroll
-      for (int k = 0; k < 8; ++k) acc[k] = n ? acc[k] + (float)e[k] : (float)e[k];
-      ++n;
+      body(j, i, dy, dx);
     }
   }
+}
+
+// sum over the covering windows of pair row r (fp32, starting from the first one's value) -> count
+template <typename T, int WRAP>
+__device__ __forceinline__ int gather_sum(const T* __restrict__ eps, const WinGrid& g, long p, int r, int C, int Hc, int Wc, const CanvasPos& q,
+                                          float* acc) {
+  using V8 = typename V8T<T>::type;
+  const long T_ = (long)g.ny * g.nx;
+  int n = 0;
+  for_covering_windows<WRAP>(g, Hc, Wc, q, [&](int j, int i, int dy, int dx) __attribute__((always_inline)) {
+    const V8 e = *(const V8*)(eps + window_at(2 * (p * T_ + j * g.nx + i) + r, C, q.c, g.s, dy, dx));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = n ? acc[k] + (float)e[k] : (float)e[k];
+    ++n;
+  });
   return n;
 }
 
@@ -91,15 +101,9 @@ __device__ __forceinline__ void scatter(T* __restrict__ xin, const WinGrid& g, l
                                         const typename V8T<T>::type o) {
   using V8 = typename V8T<T>::type;
   const long T_ = (long)g.ny * g.nx;
-  for (int j = 0; j < g.ny; ++j) {
-    const int dy = window_dist<(WRAP & 2) != 0>(q.y, g.oy[j], Hc);
-    if ((unsigned)dy >= (unsigned)g.s) continue;
-    for (int i = 0; i < g.nx; ++i) {
-      const int dx = window_dist<(WRAP & 1) != 0>(q.x, g.ox[i], Wc);
-      if ((unsigned)dx >= (unsigned)g.s) continue;
-      for (int r = r0; r <= r1; ++r) *(V8*)(xin + window_at(2 * (p * T_ + j * g.nx + i) + r, C, q.c, g.s, dy, dx)) = o;
-    }
-  }
+  for_covering_windows<WRAP>(g, Hc, Wc, q, [&](int j, int i, int dy, int dx) __attribute__((always_inline)) {
+    for (int r = r0; r <= r1; ++r) *(V8*)(xin + window_at(2 * (p * T_ + j * g.nx + i) + r, C, q.c, g.s, dy, dx)) = o;
+  });
 }
 
 // src [P rows][C][Hc][Wc] (S = float or T) -> xin [2 P T][C][s][s]; rows == 1: the canvas state goes to both rows of every pair
@@ -280,7 +284,7 @@ __global__ __launch_bounds__(256) void vae_encode_step_windows_kernel(const T* _
   }
 }
 
-// The hi-res fix on a canvas (sta_latent_upscale_step_windows and its `_ring` sibling): a finished trajectory's latent, upscaled
+// The hi-res fix on a canvas (sta_latent_upscale_step_windows): a finished trajectory's latent, upscaled
 // bilinearly to the canvas, noised to the decode's start and split, one launch.
 // The two taps and weights of output position d on one axis (source length L_in, scale = (float)L_in / (float)L_out, the host's):
 // src = (d + 0.5) scale - 0.5; a clamped axis takes max(src, 0), i0 = floor(src), i1 = min(i0 + 1, L_in - 1) — the rule of
@@ -353,7 +357,7 @@ __global__ __launch_bounds__(256) void latent_upscale_step_windows_kernel(const 
   }
 }
 
-// Attention guidance on a canvas (sta_latent_guide_windows and its `_ring` sibling): latent_guide_kernel of sta_guide.hip carried to a
+// Attention guidance on a canvas (sta_latent_guide_windows): latent_guide_kernel of sta_guide.hip carried to a
 // canvas. g [2 P T][C][s][s] is the gradient w.r.t. the window input pairs; the windows are window_split(x), so the gradient w.r.t. the
 // canvas state is the split's adjoint, a SUM over the covering windows and both pair rows (not the overlap mean).
 // d of one lane's 8 canvas elements: the covering windows' (g_u + g_c) in ascending w, fp32, starting from the first one's value, times
@@ -364,22 +368,16 @@ __device__ __forceinline__ void guide_windows_d(const T* __restrict__ g, const W
   using V8 = typename V8T<T>::type;
   const long T_ = (long)gr.ny * gr.nx;
   int n = 0;
-  for (int j = 0; j < gr.ny; ++j) {
-    const int dy = window_dist<(WRAP & 2) != 0>(q.y, gr.oy[j], Hc);
-    if ((unsigned)dy >= (unsigned)gr.s) continue;
-    for (int i = 0; i < gr.nx; ++i) {
-      const int dx = window_dist<(WRAP & 1) != 0>(q.x, gr.ox[i], Wc);
-      if ((unsigned)dx >= (unsigned)gr.s) continue;
-      const long at = window_at(2 * (q.row * T_ + j * gr.nx + i), C, q.c, gr.s, dy, dx);
-      const V8 gu = *(const V8*)(g + at), gc = *(const V8*)(g + at + (long)C * gr.s * gr.s);
+  for_covering_windows<WRAP>(gr, Hc, Wc, q, [&](int j, int i, int dy, int dx) __attribute__((always_inline)) {
+    const long at = window_at(2 * (q.row * T_ + j * gr.nx + i), C, q.c, gr.s, dy, dx);
+    const V8 gu = *(const V8*)(g + at), gc = *(const V8*)(g + at + (long)C * gr.s * gr.s);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float sum = (float)gu[k] + (float)gc[k];
-        d[k] = n ? d[k] + sum : sum;
-      }
-      ++n;
+    for (int k = 0; k < 8; ++k) {
+      const float sum = (float)gu[k] + (float)gc[k];
+      d[k] = n ? d[k] + sum : sum;
     }
-  }
+    ++n;
+  });
   if (kp) {
     float k8[8];
     load8(kp, k8);
@@ -442,45 +440,34 @@ __global__ __launch_bounds__(256) void latent_guide_windows_kernel(const T* __re
   if (stats && part == 0 && tid == 0) stats[p] = rms;
 }
 
-// offsets along one axis of length L: 0 first, multiples of 8, ascending, no gap (step <= s), the last window ends at L
-int window_axis_ok(const char* what, const char* axis, int n, const int* o, int s, int L) {
+// offsets along one axis of length L: 0 first, multiples of 8, ascending, no gap (step <= s), the last window ends at L. ring: the axis
+// is CYCLIC (s <= L is the caller's rule: a window covers an element at most once): every offset on the axis instead (o < L; a window
+// may run over the seam), and the ring closes (L - last <= s)
+int window_axis_ok(const char* what, const char* axis, int n, const int* o, int s, int L, bool ring) {
   if (n < 1 || n > STA_MAX_WINDOW_OFFSETS) return sta_fail(STA_E_ARG, "%s: n%s=%d (need 1 .. %d offsets)", what, axis, n, STA_MAX_WINDOW_OFFSETS);
   for (int k = 0; k < n; ++k) {
     const int prev = k ? o[k - 1] : 0;
     if (o[k] % 8) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d is not a multiple of 8", what, axis, k, o[k]);
-    if (o[k] < 0 || (long)o[k] + s > L) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d out of range (s=%d, length %d)", what, axis, k, o[k], s, L);
+    if (ring && (o[k] < 0 || o[k] >= L)) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d is not on the wrapped axis (length %d)", what, axis, k, o[k], L);
+    if (!ring && (o[k] < 0 || (long)o[k] + s > L)) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d out of range (s=%d, length %d)", what, axis, k, o[k], s, L);
     if (k ? o[k] <= prev : o[k] != 0) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d unsorted (after %d; the first offset is 0)", what, axis, k, o[k], prev);
     if (o[k] - prev > s) return sta_fail(STA_E_ARG, "%s: gap between o%s[%d]=%d and o%s[%d]=%d (s=%d)", what, axis, k - 1, prev, axis, k, o[k], s);
   }
-  if (o[n - 1] + s != L) return sta_fail(STA_E_ARG, "%s: gap behind o%s[%d]=%d (s=%d, length %d)", what, axis, n - 1, o[n - 1], s, L);
-  return STA_OK;
-}
-
-// offsets along one CYCLIC axis of length L (s <= L is the caller's rule: a window covers an element at most once): 0 first, multiples
-// of 8, ascending, every one on the axis (o < L; a window may run over the seam), no gap (step <= s), the ring closes (L - last <= s)
-int window_ring_axis_ok(const char* what, const char* axis, int n, const int* o, int s, int L) {
-  if (n < 1 || n > STA_MAX_WINDOW_OFFSETS) return sta_fail(STA_E_ARG, "%s: n%s=%d (need 1 .. %d offsets)", what, axis, n, STA_MAX_WINDOW_OFFSETS);
-  for (int k = 0; k < n; ++k) {
-    const int prev = k ? o[k - 1] : 0;
-    if (o[k] % 8) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d is not a multiple of 8", what, axis, k, o[k]);
-    if (o[k] < 0 || o[k] >= L) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d is not on the wrapped axis (length %d)", what, axis, k, o[k], L);
-    if (k ? o[k] <= prev : o[k] != 0) return sta_fail(STA_E_ARG, "%s: o%s[%d]=%d unsorted (after %d; the first offset is 0)", what, axis, k, o[k], prev);
-    if (o[k] - prev > s) return sta_fail(STA_E_ARG, "%s: gap between o%s[%d]=%d and o%s[%d]=%d (s=%d)", what, axis, k - 1, prev, axis, k, o[k], s);
-  }
-  if (L - o[n - 1] > s)
+  if (ring && L - o[n - 1] > s)
     return sta_fail(STA_E_ARG, "%s: the ring does not close behind o%s[%d]=%d (s=%d, wrapped length %d)", what, axis, n - 1, o[n - 1], s, L);
+  if (!ring && o[n - 1] + s != L) return sta_fail(STA_E_ARG, "%s: gap behind o%s[%d]=%d (s=%d, length %d)", what, axis, n - 1, o[n - 1], s, L);
   return STA_OK;
 }
 
-// wrap: the cyclic axes (bit 0 = x, bit 1 = y); the other axes keep window_axis_ok
+// wrap: the cyclic axes (bit 0 = x, bit 1 = y), 0 = the clamped grid
 int window_grid_ok(const char* what, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, WinGrid* g) {
   if (!oy || !ox) return sta_fail(STA_E_ARG, "null pointer");
   if (wrap < 0 || wrap > 3) return sta_fail(STA_E_ARG, "%s: wrap=%d (need 0 .. 3: bit 0 = x, bit 1 = y)", what, wrap);
   if (P <= 0 || C <= 0) return sta_fail(STA_E_ARG, "%s: P=%ld C=%d", what, P, C);
   if (s < 8 || Hc < s || Wc < s || s % 8 || Hc % 8 || Wc % 8)
     return sta_fail(STA_E_ARG, "%s: s=%d Hc=%d Wc=%d (need multiples of 8 and 8 <= s <= Hc, Wc)", what, s, Hc, Wc);
-  if (const int rc = (wrap & 2 ? window_ring_axis_ok : window_axis_ok)(what, "y", ny, oy, s, Hc)) return rc;
-  if (const int rc = (wrap & 1 ? window_ring_axis_ok : window_axis_ok)(what, "x", nx, ox, s, Wc)) return rc;
+  if (const int rc = window_axis_ok(what, "y", ny, oy, s, Hc, wrap & 2)) return rc;
+  if (const int rc = window_axis_ok(what, "x", nx, ox, s, Wc, wrap & 1)) return rc;
   *g = WinGrid{};
   g->ny = ny, g->nx = nx, g->s = s;
   for (int k = 0; k < ny; ++k) g->oy[k] = oy[k];
@@ -488,174 +475,181 @@ int window_grid_ok(const char* what, long P, int C, int Hc, int Wc, int ny, int 
   return STA_OK;
 }
 
-// f(std::integral_constant<int, wrap>) for a wrap window_grid_ok has accepted (0 .. 3): the kernels take the cyclic axes at compile time
-template <typename F>
-int by_wrap(int wrap, F&& f) {
-  switch (wrap) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-    default: return f(std::integral_constant<int, 0>{});
-  }
+// every listed pointer is null or 16-byte aligned
+bool all_aligned16(std::initializer_list<const void*> tensors) {
+  for (const void* p : tensors)
+    if (!sta_aligned16(p)) return false;
+  return true;
 }
 
-// The five launches; `what` names the entry point in the texts (the clamped entry points are wrap = 0 of these).
-int window_split(const char* what, const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy,
-                 const int* ox, int s, int wrap, int src_dtype, int dtype, void* stream) {
+// The tail of every launcher: f(T{}, std::integral_constant<int, wrap>{}) with T = the element type of `dtype` (sta_by_dtype refuses any
+// other) and a wrap window_grid_ok has accepted (0 .. 3) — the kernels take the cyclic axes at compile time — ...
+template <typename F>
+int by_dtype_and_wrap(int dtype, int wrap, F&& f) {
+  return sta_by_dtype(dtype, [&](auto tag) {
+    switch (wrap) {
+      case 1: return f(tag, std::integral_constant<int, 1>{});
+      case 2: return f(tag, std::integral_constant<int, 2>{});
+      case 3: return f(tag, std::integral_constant<int, 3>{});
+      default: return f(tag, std::integral_constant<int, 0>{});
+    }
+  });
+}
+
+// ... where f launches its kernel on `groups` 256-lane groups
+template <auto Kernel, typename... A>
+STA_INLINE int launch_groups(const char* what, unsigned groups, void* stream, A... a) {
+  return sta_launch<Kernel>(what, dim3(groups), dim3(256), 0, (hipStream_t)stream, a...);
+}
+
+}  // namespace
+
+// The launches (C-ABI); `what` names the entry point in the texts.
+extern "C" {
+
+int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                     int wrap, int src_dtype, int dtype, void* stream) {
+  const char* what = "window_split";
   g_sta_err[0] = 0;
   if (!src || !xin) return sta_fail(STA_E_ARG, "null pointer");
   WinGrid g;
   if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
   if (rows != 1 && rows != 2) return sta_fail(STA_E_ARG, "%s: rows=%d (1: canvas states, 2: input pairs)", what, rows);
-  if (!sta_aligned16(src) || !sta_aligned16(xin)) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  if (!all_aligned16({src, xin})) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
   if (src_dtype != STA_SRC_F32 && src_dtype != dtype)
     return sta_fail(STA_E_UNSUP, "%s: src_dtype %d (float32 = %d, or the output's dtype %d)", what, src_dtype, STA_SRC_F32, dtype);
   const long nvec = P * rows * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
+  return by_dtype_and_wrap(dtype, wrap, [&](auto tag, auto w) {
     using T = decltype(tag);
-    return by_wrap(wrap, [&](auto w) {
-      constexpr int W = decltype(w)::value;
-      if (src_dtype == STA_SRC_F32)
-        return sta_launch<window_split_kernel<float, T, W>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
-                                                            (T*)xin, nvec, rows, C, Hc, Wc, g);
-      return sta_launch<window_split_kernel<T, T, W>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)src, (T*)xin,
-                                                      nvec, rows, C, Hc, Wc, g);
-    });
+    constexpr int W = decltype(w)::value;
+    if (src_dtype == STA_SRC_F32)
+      return launch_groups<window_split_kernel<float, T, W>>(what, sta_grid_for(nvec), stream, (const float*)src, (T*)xin, nvec, rows, C, Hc, Wc, g);
+    return launch_groups<window_split_kernel<T, T, W>>(what, sta_grid_for(nvec), stream, (const T*)src, (T*)xin, nvec, rows, C, Hc, Wc, g);
   });
 }
 
-int window_fuse(const char* what, const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
-                int wrap, int dtype, void* stream) {
+int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                    int dtype, void* stream) {
+  const char* what = "window_fuse";
   g_sta_err[0] = 0;
   if (!eps || !out) return sta_fail(STA_E_ARG, "null pointer");
   WinGrid g;
   if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
-  if (!sta_aligned16(eps) || !sta_aligned16(out)) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  if (!all_aligned16({eps, out})) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
   const long nvec = 2 * P * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
+  return by_dtype_and_wrap(dtype, wrap, [&](auto tag, auto w) {
     using T = decltype(tag);
-    return by_wrap(wrap, [&](auto w) {
-      return sta_launch<window_fuse_kernel<T, decltype(w)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
-                                                                   (const T*)eps, (T*)out, nvec, C, Hc, Wc, g);
-    });
+    return launch_groups<window_fuse_kernel<T, decltype(w)::value>>(what, sta_grid_for(nvec), stream, (const T*)eps, (T*)out, nvec, C, Hc, Wc, g);
   });
 }
 
-int step_windows(const char* what, const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin,
-                 long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, const StepCoef& c, int dtype,
-                 void* stream) {
+int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin, long P,
+                             int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t,
+                             float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream) {
+  const char* what = "sampler_step_windows";
+  const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
   g_sta_err[0] = 0;
   WinGrid g;
   if (const int rc = sta_step_args_ok(what, eps, x, m_prev, noise, x_next, m, xin, false, nullptr, nullptr, nullptr, c.alpha_t,
                                       [&] { return window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g); }))
     return rc;
   const long nvec = P * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
+  return by_dtype_and_wrap(dtype, wrap, [&](auto tag, auto w) {
     using T = decltype(tag);
-    return by_wrap(wrap, [&](auto w) {
-      return sta_launch<sampler_step_windows_kernel<T, decltype(w)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
-                                                                            (const T*)eps, x, m_prev, noise, x_next, m, (T*)xin, nvec, C, Hc,
-                                                                            Wc, g, c);
-    });
+    return launch_groups<sampler_step_windows_kernel<T, decltype(w)::value>>(what, sta_grid_for(nvec), stream, (const T*)eps, x, m_prev, noise,
+                                                                             x_next, m, (T*)xin, nvec, C, Hc, Wc, g, c);
   });
 }
 
-int step_windows_masked(const char* what, const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
-                        const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc, int ny, int nx,
-                        const int* oy, const int* ox, int s, int wrap, const StepCoef& c, float q_a, float q_b, int dtype, void* stream) {
+int sta_sampler_step_windows_masked(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
+                                    const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc,
+                                    int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t, float alpha_t,
+                                    float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream) {
+  const char* what = "sampler_step_windows_masked";
+  const StepCoef c{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n};
   g_sta_err[0] = 0;
   WinGrid g;
   if (const int rc = sta_step_args_ok(what, eps, x, m_prev, noise, x_next, m, xin, true, x0, keep, qnoise, c.alpha_t,
                                       [&] { return window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g); }))
     return rc;
   const long nvec = P * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
+  return by_dtype_and_wrap(dtype, wrap, [&](auto tag, auto w) {
     using T = decltype(tag);
-    return by_wrap(wrap, [&](auto w) {
-      auto launch = [&](auto mp, auto nz) {
-        return sta_launch<sampler_step_windows_masked_kernel<T, decltype(mp)::value, decltype(nz)::value, decltype(w)::value>>(
-            what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const T*)eps, x, m_prev, noise, x0, keep, qnoise, x_next, m,
-            (T*)xin, nvec, C, Hc, Wc, g, c, q_a, q_b);
-      };
-      using Yes = std::true_type;
-      using No = std::false_type;
-      return m_prev ? (noise ? launch(Yes{}, Yes{}) : launch(Yes{}, No{})) : (noise ? launch(No{}, Yes{}) : launch(No{}, No{}));
-    });
+    auto launch = [&](auto mp, auto nz) {
+      return launch_groups<sampler_step_windows_masked_kernel<T, decltype(mp)::value, decltype(nz)::value, decltype(w)::value>>(
+          what, sta_grid_for(nvec), stream, (const T*)eps, x, m_prev, noise, x0, keep, qnoise, x_next, m, (T*)xin, nvec, C, Hc, Wc, g, c, q_a, q_b);
+    };
+    using Yes = std::true_type;
+    using No = std::false_type;
+    return m_prev ? (noise ? launch(Yes{}, Yes{}) : launch(Yes{}, No{})) : (noise ? launch(No{}, Yes{}) : launch(No{}, No{}));
   });
 }
 
-int window_blend(const char* what, const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C,
-                 int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream) {
+int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
+                     int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream) {
+  const char* what = "window_blend";
   g_sta_err[0] = 0;
   if (!x || !x0 || !keep || !noise || !x_out) return sta_fail(STA_E_ARG, "%s: null pointer", what);
   WinGrid g;
   if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
-  if (!sta_aligned16(x) || !sta_aligned16(x0) || !sta_aligned16(keep) || !sta_aligned16(noise) || !sta_aligned16(x_out) || !sta_aligned16(xin))
-    return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  if (!all_aligned16({x, x0, keep, noise, x_out, xin})) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
   const long nvec = P * C * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
+  return by_dtype_and_wrap(dtype, wrap, [&](auto tag, auto w) {
     using T = decltype(tag);
-    return by_wrap(wrap, [&](auto w) {
-      return sta_launch<window_blend_kernel<T, decltype(w)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, x, x0,
-                                                                    keep, noise, x_out, (T*)xin, nvec, C, Hc, Wc, g, q_a, q_b);
-    });
+    return launch_groups<window_blend_kernel<T, decltype(w)::value>>(what, sta_grid_for(nvec), stream, x, x0, keep, noise, x_out, (T*)xin, nvec, C,
+                                                                     Hc, Wc, g, q_a, q_b);
   });
 }
 
-int encode_step_windows(const char* what, const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc,
-                        float* x, float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
-                        float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream) {
+int sta_vae_encode_step_windows(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
+                                float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                                float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream) {
+  const char* what = "vae_encode_step_windows";
   g_sta_err[0] = 0;
   if (!h || !quant_w || !quant_b || !n_post || !n_enc || !x) return sta_fail(STA_E_ARG, "%s: null pointer", what);
   WinGrid g;
   if (const int rc = window_grid_ok(what, P, 4, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
-  if (!sta_aligned16(h) || !sta_aligned16(n_post) || !sta_aligned16(n_enc) || !sta_aligned16(x) || !sta_aligned16(z0) || !sta_aligned16(xin))
-    return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  if (!all_aligned16({h, n_post, n_enc, x, z0, xin})) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
   if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_ARG, "%s: dtype %d (STA_BF16 or STA_F16)", what, dtype);
   const long nvec = P * Hc * (Wc / 8);
-  return sta_by_dtype(dtype, [&](auto tag) {
+  return by_dtype_and_wrap(dtype, wrap, [&](auto tag, auto w) {
     using T = decltype(tag);
-    return by_wrap(wrap, [&](auto w) {
-      return sta_launch<vae_encode_step_windows_kernel<T, decltype(w)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream,
-                                                                               (const T*)h, quant_w, quant_b, n_post, n_enc, x, z0, (T*)xin, nvec,
-                                                                               Hc, Wc, g, scale_factor, sqrt_a, sqrt_1ma);
-    });
+    return launch_groups<vae_encode_step_windows_kernel<T, decltype(w)::value>>(what, sta_grid_for(nvec), stream, (const T*)h, quant_w, quant_b,
+                                                                                n_post, n_enc, x, z0, (T*)xin, nvec, Hc, Wc, g, scale_factor,
+                                                                                sqrt_a, sqrt_1ma);
   });
 }
 
-int upscale_step_windows(const char* what, const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w,
-                         int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float sqrt_a, float sqrt_1ma, int dtype,
-                         void* stream) {
+int sta_latent_upscale_step_windows(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
+                                    int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float sqrt_a, float sqrt_1ma, int dtype,
+                                    void* stream) {
+  const char* what = "latent_upscale_step_windows";
   g_sta_err[0] = 0;
   if (!z || !noise || !x) return sta_fail(STA_E_ARG, "%s: null pointer", what);
   WinGrid g;
   if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &g)) return rc;
   if (h < 8 || w < 8 || h % 8 || w % 8) return sta_fail(STA_E_ARG, "%s: source h=%d w=%d (need positive multiples of 8)", what, h, w);
   if (Hc < h || Wc < w) return sta_fail(STA_E_ARG, "%s: canvas %d x %d is smaller than the source %d x %d (upscale only)", what, Hc, Wc, h, w);
-  if (!sta_aligned16(z) || !sta_aligned16(noise) || !sta_aligned16(x) || !sta_aligned16(z_up) || !sta_aligned16(xin))
-    return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
+  if (!all_aligned16({z, noise, x, z_up, xin})) return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned", what);
   if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_ARG, "%s: dtype %d (STA_BF16 or STA_F16)", what, dtype);
   const long nvec = P * C * Hc * (Wc / 8);
   const float scale_y = (float)h / (float)Hc, scale_x = (float)w / (float)Wc;
-  return sta_by_dtype(dtype, [&](auto tag) {
+  return by_dtype_and_wrap(dtype, wrap, [&](auto tag, auto wr) {
     using T = decltype(tag);
-    return by_wrap(wrap, [&](auto wr) {
-      return sta_launch<latent_upscale_step_windows_kernel<T, decltype(wr)::value>>(what, dim3(sta_grid_for(nvec)), dim3(256), 0,
-                                                                                    (hipStream_t)stream, z, noise, x, z_up, (T*)xin, nvec, C, h, w,
-                                                                                    Hc, Wc, g, scale_y, scale_x, sqrt_a, sqrt_1ma);
-    });
+    return launch_groups<latent_upscale_step_windows_kernel<T, decltype(wr)::value>>(what, sta_grid_for(nvec), stream, z, noise, x, z_up, (T*)xin,
+                                                                                     nvec, C, h, w, Hc, Wc, g, scale_y, scale_x, sqrt_a, sqrt_1ma);
   });
 }
 
-int latent_guide_windows(const char* what, const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out,
-                         void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
-                         int normalize, float inv_scale, int dtype, void* stream) {
+int sta_latent_guide_windows(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out, void* xin,
+                             float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                             int normalize, float inv_scale, int dtype, void* stream) {
+  const char* what = "latent_guide_windows";
   g_sta_err[0] = 0;
   if (!g || !x || !step || !count || !x_out) return sta_fail(STA_E_ARG, "%s: null pointer", what);
   WinGrid gr;
   if (const int rc = window_grid_ok(what, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, &gr)) return rc;
-  if (!sta_aligned16(g) || !sta_aligned16(x) || !sta_aligned16(keep) || !sta_aligned16(x_out) || !sta_aligned16(xin) || ((uintptr_t)step & 3) ||
-      ((uintptr_t)count & 3) || ((uintptr_t)stats & 3))
+  if (!all_aligned16({g, x, keep, x_out, xin}) || ((uintptr_t)step & 3) || ((uintptr_t)count & 3) || ((uintptr_t)stats & 3))
     return sta_fail(STA_E_ARG, "%s: every tensor must be 16-byte aligned (step, count and stats: 4-byte)", what);
   if (dtype != STA_BF16 && dtype != STA_F16) return sta_fail(STA_E_ARG, "%s: dtype %d (STA_BF16 or STA_F16)", what, dtype);
   const size_t plane = (size_t)Hc * Wc, f32 = (size_t)P * C * plane * 4, pairs = (size_t)2 * P * ny * nx * C * s * s * 2;
@@ -674,121 +668,12 @@ int latent_guide_windows(const char* what, const void* g, const float* x, const 
   if (parts > GUIDE_MAX_PARTS) parts = GUIDE_MAX_PARTS;
   const long chunk = (canvec + parts - 1) / parts;
   if (P * parts > 0x7fffffffL) return sta_fail(STA_E_UNSUP, "%s: P=%ld canvases need more than 2^31 - 1 workgroups", what, P);
-  return sta_by_dtype(dtype, [&](auto tag) {
+  return by_dtype_and_wrap(dtype, wrap, [&](auto tag, auto w) {
     using T = decltype(tag);
-    return by_wrap(wrap, [&](auto w) {
-      return sta_launch<latent_guide_windows_kernel<T, decltype(w)::value>>(what, dim3((unsigned)(P * parts)), dim3(256), 0, (hipStream_t)stream,
-                                                                            (const T*)g, x, keep, step, count, x_out, (T*)xin, stats, canvec, C,
-                                                                            Hc, Wc, gr, (int)parts, chunk, normalize, inv_scale);
-    });
+    return launch_groups<latent_guide_windows_kernel<T, decltype(w)::value>>(what, (unsigned)(P * parts), stream, (const T*)g, x, keep, step, count,
+                                                                             x_out, (T*)xin, stats, canvec, C, Hc, Wc, gr, (int)parts, chunk,
+                                                                             normalize, inv_scale);
   });
-}
-
-}  // namespace
-
-extern "C" {
-
-int sta_latent_upscale_step_windows(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
-                                    int Wc, int ny, int nx, const int* oy, const int* ox, int s, float sqrt_a, float sqrt_1ma, int dtype,
-                                    void* stream) {
-  return upscale_step_windows("latent_upscale_step_windows", z, noise, x, z_up, xin, P, C, h, w, Hc, Wc, ny, nx, oy, ox, s, 0, sqrt_a, sqrt_1ma,
-                              dtype, stream);
-}
-
-int sta_latent_upscale_step_windows_ring(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
-                                         int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float sqrt_a, float sqrt_1ma,
-                                         int dtype, void* stream) {
-  return upscale_step_windows("latent_upscale_step_windows_ring", z, noise, x, z_up, xin, P, C, h, w, Hc, Wc, ny, nx, oy, ox, s, wrap, sqrt_a,
-                              sqrt_1ma, dtype, stream);
-}
-
-int sta_latent_guide_windows(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out, void* xin,
-                             float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int normalize,
-                             float inv_scale, int dtype, void* stream) {
-  return latent_guide_windows("latent_guide_windows", g, x, keep, step, count, x_out, xin, stats, P, C, Hc, Wc, ny, nx, oy, ox, s, 0, normalize,
-                              inv_scale, dtype, stream);
-}
-
-int sta_latent_guide_windows_ring(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out,
-                                  void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
-                                  int wrap, int normalize, float inv_scale, int dtype, void* stream) {
-  return latent_guide_windows("latent_guide_windows_ring", g, x, keep, step, count, x_out, xin, stats, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap,
-                              normalize, inv_scale, dtype, stream);
-}
-
-int sta_vae_encode_step_windows(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
-                                float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
-                                float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream) {
-  return encode_step_windows("vae_encode_step_windows", h, quant_w, quant_b, n_post, n_enc, x, z0, xin, P, Hc, Wc, ny, nx, oy, ox, s, 0,
-                             scale_factor, sqrt_a, sqrt_1ma, dtype, stream);
-}
-
-int sta_vae_encode_step_windows_ring(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
-                                     float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
-                                     float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream) {
-  return encode_step_windows("vae_encode_step_windows_ring", h, quant_w, quant_b, n_post, n_enc, x, z0, xin, P, Hc, Wc, ny, nx, oy, ox, s, wrap,
-                             scale_factor, sqrt_a, sqrt_1ma, dtype, stream);
-}
-
-int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
-                     int src_dtype, int dtype, void* stream) {
-  return window_split("window_split", src, xin, P, rows, C, Hc, Wc, ny, nx, oy, ox, s, 0, src_dtype, dtype, stream);
-}
-
-int sta_window_split_ring(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox,
-                          int s, int wrap, int src_dtype, int dtype, void* stream) {
-  return window_split("window_split_ring", src, xin, P, rows, C, Hc, Wc, ny, nx, oy, ox, s, wrap, src_dtype, dtype, stream);
-}
-
-int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int dtype,
-                    void* stream) {
-  return window_fuse("window_fuse", eps, out, P, C, Hc, Wc, ny, nx, oy, ox, s, 0, dtype, stream);
-}
-
-int sta_window_fuse_ring(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
-                         int dtype, void* stream) {
-  return window_fuse("window_fuse_ring", eps, out, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, dtype, stream);
-}
-
-int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin, long P,
-                             int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t,
-                             float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream) {
-  return step_windows("sampler_step_windows", eps, x, m_prev, noise, x_next, m, xin, P, C, Hc, Wc, ny, nx, oy, ox, s, 0,
-                      StepCoef{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n}, dtype, stream);
-}
-
-int sta_sampler_step_windows_ring(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin,
-                                  long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale,
-                                  float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream) {
-  return step_windows("sampler_step_windows_ring", eps, x, m_prev, noise, x_next, m, xin, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap,
-                      StepCoef{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n}, dtype, stream);
-}
-
-int sta_sampler_step_windows_masked(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
-                                    const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc,
-                                    int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t, float alpha_t, float c_x,
-                                    float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream) {
-  return step_windows_masked("sampler_step_windows_masked", eps, x, m_prev, noise, x0, keep, qnoise, x_next, m, xin, P, C, Hc, Wc, ny, nx, oy, ox,
-                             s, 0, StepCoef{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n}, q_a, q_b, dtype, stream);
-}
-
-int sta_sampler_step_windows_masked_ring(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
-                                         const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc,
-                                         int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t,
-                                         float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype,
-                                         void* stream) {
-  return step_windows_masked("sampler_step_windows_masked_ring", eps, x, m_prev, noise, x0, keep, qnoise, x_next, m, xin, P, C, Hc, Wc, ny, nx,
-                             oy, ox, s, wrap, StepCoef{scale, sigma_t, alpha_t, c_x, c_m, c_p, c_e, c_n}, q_a, q_b, dtype, stream);
-}
-
-int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
-                     int Wc, int ny, int nx, const int* oy, const int* ox, int s, float q_a, float q_b, int dtype, void* stream) {
-  return window_blend("window_blend", x, x0, keep, noise, x_out, xin, P, C, Hc, Wc, ny, nx, oy, ox, s, 0, q_a, q_b, dtype, stream);
-}
-
-int sta_window_blend_ring(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
-                          int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream) {
-  return window_blend("window_blend_ring", x, x0, keep, noise, x_out, xin, P, C, Hc, Wc, ny, nx, oy, ox, s, wrap, q_a, q_b, dtype, stream);
 }
 
 }  // extern "C"

@@ -922,7 +922,7 @@ class SolverSamplerBase(PLMSSampler):
         an existing picture's latent on its footprint, mask is 1 there) and the repaint of a region of a canvas sampled earlier.
         mask [P, 1, Hc, Wc] in [0, 1], 1 = keep; x0 [P, channels, Hc, Wc]; image [P, 3, 8 Hc, 8 Wc] in [0, 1] / mask_px [P, 1, 8 Hc, 8 Wc]:
         the original and its keep mask for the pixel-space paste over the ONE decode of the whole canvas (sta_image_composite); the other
-        keywords are sample_canvas's (disc_scale= and wrap= included: the `_ring` launches, and the pixel-space paste on the cropped decode). On the GPU
+        keywords are sample_canvas's (disc_scale= and wrap= included: the launches take the grid's wrap mask, and the pixel-space paste on the cropped decode). On the GPU
         one sta_window_blend launch runs before call 0, one sta_sampler_step_windows_masked launch after calls 0 .. S - 2 and the plain
         sta_sampler_step_windows after the last call. The blend draws are canvas-shaped, in the order of `sample(mask=)`: blend draw of call i, eta draw of call i, blend draw of call i + 1, ...
         ValueError before any UNet call: what sample_canvas refuses, a missing mask or x0, shapes that are not the canvas's, mask values

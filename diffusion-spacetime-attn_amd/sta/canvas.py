@@ -30,7 +30,7 @@ Wrap-around canvases (`window_grid(..., wrap="x" | "y" | "xy")`: a 360 degree pa
 the offsets of a wrapped axis of length L are 0, stride, ..., L - stride (L % stride == 0, L >= 1.5 s), and the window at offset o covers
 the canvas positions (o + d) mod L, d = 0 .. s - 1: the last windows run over the seam, so the first and the last column share a UNet
 window. Every window sees a centre at the representative nearest to it (`window_centres`), the restatements index modulo L, and the CUDA
-dispatchers call the `_ring` siblings of the five entry points; a grid without wrap is the clamped grid above, code and bits unchanged.
+dispatchers hand the C entry points the grid's wrap mask; a grid without wrap (mask 0) is the clamped grid above.
 
 img2img on a canvas (`encode_step_windows`, restatement `encode_step_windows_reference`): from the VAE encoder's output on the whole canvas
 to the canvas state noised to the decode's start and the first call's window input pairs, one sta_vae_encode_step_windows launch
@@ -354,23 +354,34 @@ _TABLES = {}
 
 
 def _grid_args(grid):
-    """(ny, nx, oy, ox, s) as the C-ABI takes them, on a wrapped grid (ny, nx, oy, ox, s, wrap) as the `_ring` siblings take them; the
-    host offset arrays are kept per grid."""
+    """(ny, nx, oy, ox, s, wrap) as the C-ABI takes them; the host offset arrays are kept per grid."""
     key = (grid.oy, grid.ox)
     if key not in _TABLES:
         _TABLES[key] = ((ctypes.c_int * grid.ny)(*grid.oy), (ctypes.c_int * grid.nx)(*grid.ox))
     oy, ox = _TABLES[key]
-    return (grid.ny, grid.nx, ctypes.addressof(oy), ctypes.addressof(ox), grid.s) + ((WRAPS[grid.wrap],) if grid.wrap else ())
+    return grid.ny, grid.nx, ctypes.addressof(oy), ctypes.addressof(ox), grid.s, WRAPS[grid.wrap]
 
 
-def _entry(name, grid):
-    """(the C function, its name) of launch `name` on this grid: the `_ring` sibling when an axis wraps."""
-    name = name + "_ring" if grid.wrap else name
-    return getattr(lib.load(), name), name
+def _launch(name, *args):
+    lib.check(getattr(lib.load(), name)(*args), name)
 
 
 def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def _check_state(what, x, grid):
+    if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
+        raise ValueError("%s: the state must be a float32 [P, C, %d, %d] canvas, got %s %s" % (what, grid.Hc, grid.Wc, x.dtype, tuple(x.shape)))
+
+
+def _pairs(P, C, grid, dtype, device):
+    """The window pair batch [2 P T, C, s, s] of P canvases, not initialised."""
+    return torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=device)
 
 
 def window_split(src, grid, dtype=None, rows=1):
@@ -384,10 +395,9 @@ def window_split(src, grid, dtype=None, rows=1):
         raise ValueError("window_split: src %s, rows %s for a %d x %d canvas" % (tuple(src.shape), rows, grid.Hc, grid.Wc))
     P, C = _canvases(src.shape[0], rows, "src"), src.shape[1]
     src = src.detach().contiguous()
-    xin = torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=src.device)
-    fn, name = _entry("sta_window_split", grid)
-    lib.check(fn(src.data_ptr(), xin.data_ptr(), P, rows, C, grid.Hc, grid.Wc, *_grid_args(grid),
-                 lib.STA_SRC_F32 if src.dtype == torch.float32 else _DT[dtype], _DT[dtype], _stream(src)), name)
+    xin = _pairs(P, C, grid, dtype, src.device)
+    _launch("sta_window_split", src.data_ptr(), xin.data_ptr(), P, rows, C, grid.Hc, grid.Wc, *_grid_args(grid),
+            lib.STA_SRC_F32 if src.dtype == torch.float32 else _DT[dtype], _DT[dtype], _stream(src))
     return xin
 
 
@@ -402,8 +412,7 @@ def window_fuse(eps, grid):
     P, C = _canvases(eps.shape[0], 2 * grid.T, "eps"), eps.shape[1]
     eps = eps.detach().contiguous()
     out = torch.empty((2 * P, C, grid.Hc, grid.Wc), dtype=eps.dtype, device=eps.device)
-    fn, name = _entry("sta_window_fuse", grid)
-    lib.check(fn(eps.data_ptr(), out.data_ptr(), P, C, grid.Hc, grid.Wc, *_grid_args(grid), _DT[eps.dtype], _stream(eps)), name)
+    _launch("sta_window_fuse", eps.data_ptr(), out.data_ptr(), P, C, grid.Hc, grid.Wc, *_grid_args(grid), _DT[eps.dtype], _stream(eps))
     return out
 
 
@@ -416,15 +425,10 @@ def sampler_step_windows(eps, x, m_prev, noise, c, grid, dtype=None, want_xin=Fa
     return _step_windows(eps, x, m_prev, noise, c, None, grid, want_xin)
 
 
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
-
-
 def _prep_step(what, eps, x, m_prev, noise, c, grid):
     """The shape and dtype checks of a step on a canvas -> (eps, x, m_prev, noise) as the kernel takes them (m_prev / noise None where
     their coefficient is 0)."""
-    if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
-        raise ValueError("%s: the state must be a float32 [P, C, %d, %d] canvas, got %s %s" % (what, grid.Hc, grid.Wc, x.dtype, tuple(x.shape)))
+    _check_state(what, x, grid)
     if eps.dtype not in _DT:
         raise TypeError("sta_%s takes the UNet's 16-bit output, got %s" % (what, eps.dtype))
     P, C = x.shape[0], x.shape[1]
@@ -448,8 +452,7 @@ def _step_windows(eps, x, m_prev, noise, c, bl, grid, want_xin):
         blend, q = (x0.data_ptr(), keep.data_ptr(), qn.data_ptr()), (bl.q_a, bl.q_b)
     args = (eps.data_ptr(), x.data_ptr(), _ptr(m_prev), _ptr(noise)) + blend + (x_next.data_ptr(), m.data_ptr(), _ptr(xin))
     args += (x.shape[0], x.shape[1], grid.Hc, grid.Wc) + _grid_args(grid) + tuple(c) + q + (_DT[eps.dtype], _stream(x))
-    fn, name = _entry("sta_" + what, grid)
-    lib.check(fn(*args), name)
+    _launch("sta_" + what, *args)
     return x_next, m, xin
 
 
@@ -470,27 +473,24 @@ def window_blend(x, bl, grid, dtype=None, want_xin=False):
     CPU: window_blend_reference."""
     if not x.is_cuda:
         return window_blend_reference(x, bl, grid, dtype, want_xin)
-    if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
-        raise ValueError("window_blend: the state must be a float32 [P, C, %d, %d] canvas, got %s %s" % (grid.Hc, grid.Wc, x.dtype, tuple(x.shape)))
+    _check_state("window_blend", x, grid)
     if dtype not in _DT:
         raise TypeError("sta_window_blend writes 16-bit window inputs (dtype %s)" % dtype)
     x0, keep, qn, _ = solver._prep_blend(x, bl)
     x = x.detach().contiguous()
     P, C = x.shape[0], x.shape[1]
     out = torch.empty_like(x)
-    xin = torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=x.device) if want_xin else None
-    fn, name = _entry("sta_window_blend", grid)
-    lib.check(fn(x.data_ptr(), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(), out.data_ptr(), _ptr(xin), P, C, grid.Hc, grid.Wc,
-                 *_grid_args(grid), bl.q_a, bl.q_b, _DT[dtype], _stream(x)), name)
+    xin = _pairs(P, C, grid, dtype, x.device) if want_xin else None
+    _launch("sta_window_blend", x.data_ptr(), x0.data_ptr(), keep.data_ptr(), qn.data_ptr(), out.data_ptr(), _ptr(xin), P, C, grid.Hc, grid.Wc,
+            *_grid_args(grid), bl.q_a, bl.q_b, _DT[dtype], _stream(x))
     return out, xin
 
 
 def latent_guide_windows(g, x, step, count, grid, keep=None, normalize=True, inv_scale=1.0, dtype=None, want_xin=False, want_stats=True):
     """One attention-guidance update of a canvas state -> (x_out, xin or None, rms [P] or None): g [2 P T, C, s, s] the gradient w.r.t.
     the window input pairs, x [P, C, Hc, Wc] float32, step / count [P] (or numbers), keep [P, 1, Hc, Wc] or None. CUDA: ONE
-    sta_latent_guide_windows launch (the `_ring` sibling on a wrapped grid; g must be the UNet's 16-bit gradient, xin comes in the same
-    type): the adjoint gather, sta_latent_guide and sta_window_split in one; CPU: guide_windows_reference and window_split_reference
-    (xin in `dtype`, default g's)."""
+    sta_latent_guide_windows launch (g must be the UNet's 16-bit gradient, xin comes in the same type): the adjoint gather,
+    sta_latent_guide and sta_window_split in one; CPU: guide_windows_reference and window_split_reference (xin in `dtype`, default g's)."""
     if x.dtype != torch.float32:
         raise TypeError("sampler state x must be float32, got %s" % x.dtype)
     if x.dim() != 4 or tuple(x.shape[-2:]) != (grid.Hc, grid.Wc):
@@ -513,9 +513,8 @@ def latent_guide_windows(g, x, step, count, grid, keep=None, normalize=True, inv
     x_out = torch.empty_like(xc)
     xin = torch.empty_like(g) if want_xin else None
     stats = torch.empty(P, dtype=torch.float32, device=x.device) if want_stats else None
-    fn, name = _entry("sta_latent_guide_windows", grid)
-    lib.check(fn(g.data_ptr(), xc.data_ptr(), _ptr(kp), st.data_ptr(), cnt.data_ptr(), x_out.data_ptr(), _ptr(xin), _ptr(stats), P, C,
-                 grid.Hc, grid.Wc, *_grid_args(grid), int(bool(normalize)), float(inv_scale), _DT[g.dtype], _stream(x)), name)
+    _launch("sta_latent_guide_windows", g.data_ptr(), xc.data_ptr(), _ptr(kp), st.data_ptr(), cnt.data_ptr(), x_out.data_ptr(), _ptr(xin),
+            _ptr(stats), P, C, grid.Hc, grid.Wc, *_grid_args(grid), int(bool(normalize)), float(inv_scale), _DT[g.dtype], _stream(x))
     return x_out, xin, stats
 
 
@@ -523,7 +522,7 @@ def encode_step_windows(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, dtype=None,
     """The encoder's conv_out result h [P, 8, Hc, Wc] on the whole canvas (16-bit CUDA; taken as NHWC) -> (x, z0, xin): the canvas state
     x [P, 4, Hc, Wc] float32 noised to the decode's start, the posterior's sample z0 (want_z0) and the first UNet call's window input
     pairs xin [2 P T, 4, s, s] (want_xin). CUDA: ONE sta_vae_encode_step_windows launch (sta_vae_encode_step and sta_window_split in
-    one; the `_ring` sibling on a wrapped grid); CPU: encode_step_windows_reference."""
+    one); CPU: encode_step_windows_reference."""
     if not h.is_cuda:
         return encode_step_windows_reference(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, dtype, want_z0, want_xin)
     _check_encode(h, n_post, n_enc, grid)
@@ -535,10 +534,9 @@ def encode_step_windows(h, qw, qb, n_post, n_enc, sf, sa, s1m, grid, dtype=None,
     qw, qb, n_post, n_enc = f(qw.reshape(8, 8)), f(qb), f(n_post), f(n_enc)
     x = torch.empty((P, 4, grid.Hc, grid.Wc), dtype=torch.float32, device=h.device)
     z0 = torch.empty_like(x) if want_z0 else None
-    xin = torch.empty((2 * P * grid.T, 4, grid.s, grid.s), dtype=h.dtype, device=h.device) if want_xin else None
-    fn, name = _entry("sta_vae_encode_step_windows", grid)
-    lib.check(fn(h.data_ptr(), qw.data_ptr(), qb.data_ptr(), n_post.data_ptr(), n_enc.data_ptr(), x.data_ptr(), _ptr(z0), _ptr(xin), P,
-                 grid.Hc, grid.Wc, *_grid_args(grid), float(sf), float(sa), float(s1m), _DT[h.dtype], _stream(h)), name)
+    xin = _pairs(P, 4, grid, h.dtype, h.device) if want_xin else None
+    _launch("sta_vae_encode_step_windows", h.data_ptr(), qw.data_ptr(), qb.data_ptr(), n_post.data_ptr(), n_enc.data_ptr(), x.data_ptr(), _ptr(z0),
+            _ptr(xin), P, grid.Hc, grid.Wc, *_grid_args(grid), float(sf), float(sa), float(s1m), _DT[h.dtype], _stream(h))
     return x, z0, xin
 
 
@@ -546,7 +544,7 @@ def upscale_step_windows(z, noise, sa, s1m, grid, dtype=None, want_z_up=False, w
     """A smaller latent z [P, C, h, w] float32 (the x0 of a finished trajectory, a square image or a canvas) -> (x, z_up, xin): the canvas
     state x [P, C, Hc, Wc] float32, z upscaled bilinearly and noised to the decode's start (x = sa z_up + s1m noise), the upscaled latent
     z_up (want_z_up) and the first UNet call's window input pairs xin [2 P T, C, s, s] in `dtype`, the UNet's 16-bit type (want_xin).
-    CUDA: ONE sta_latent_upscale_step_windows launch (the `_ring` sibling on a wrapped grid); CPU: upscale_step_windows_reference."""
+    CUDA: ONE sta_latent_upscale_step_windows launch; CPU: upscale_step_windows_reference."""
     if not z.is_cuda:
         return upscale_step_windows_reference(z, noise, sa, s1m, grid, dtype, want_z_up, want_xin)
     _check_upscale(z, noise, grid)
@@ -557,8 +555,7 @@ def upscale_step_windows(z, noise, sa, s1m, grid, dtype=None, want_z_up=False, w
     noise = noise.detach().to(device=z.device, dtype=torch.float32).contiguous()
     x = torch.empty((P, C, grid.Hc, grid.Wc), dtype=torch.float32, device=z.device)
     z_up = torch.empty_like(x) if want_z_up else None
-    xin = torch.empty((2 * P * grid.T, C, grid.s, grid.s), dtype=dtype, device=z.device) if want_xin else None
-    fn, name = _entry("sta_latent_upscale_step_windows", grid)
-    lib.check(fn(z.data_ptr(), noise.data_ptr(), x.data_ptr(), _ptr(z_up), _ptr(xin), P, C, h, w, grid.Hc, grid.Wc, *_grid_args(grid),
-                 float(sa), float(s1m), _DT[dtype] if want_xin else lib.STA_F16, _stream(z)), name)
+    xin = _pairs(P, C, grid, dtype, z.device) if want_xin else None
+    _launch("sta_latent_upscale_step_windows", z.data_ptr(), noise.data_ptr(), x.data_ptr(), _ptr(z_up), _ptr(xin), P, C, h, w, grid.Hc, grid.Wc,
+            *_grid_args(grid), float(sa), float(s1m), _DT[dtype] if want_xin else lib.STA_F16, _stream(z))
     return x, z_up, xin

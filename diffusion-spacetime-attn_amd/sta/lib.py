@@ -51,8 +51,8 @@ PER_SOURCE_FLAGS = {"sta_selfattn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-f
 # that spills one (a spilled B fragment is a scratch round trip per MFMA: the pass would be slower than the pair it replaces).
 # (sta_conv.hip: the sub-pixel instantiations conv3x3_nhwc_kernel<T, GEO, NTW, true> — "Lb1E" is the mangled `true`)
 # (sta_sampler.hip: the window kernels index offset tables that arrive by value in the kernel arguments; a toolchain that copies the
-# tables to scratch to index them is refused; the names are substrings, so every instantiation — the four wrap masks of the `_ring`
-# entry points included — falls under the rule)
+# tables to scratch to index them is refused; the names are substrings, so every instantiation — the four wrap masks of each entry
+# point included — falls under the rule)
 # (sta_rows640.hip: an included source is named by its own file; its kernels are looked for in the assembly of the unit that includes it)
 NO_SPILL_KERNELS = {"sta_ffgemm.hip": ("ff_geglu_qfrag_kernel",), "sta_conv.hip": ("ELb1EEEvNS_2CVE",), "sta_rows640.hip": ("rows640_kernel",), "sta_rowstail.hip": ("rows_tail_kernel",),
                     "sta_unet.hip": ("gn_nhwc_apply_kernel", "gn_nhwc_stats_kernel"),
@@ -169,26 +169,18 @@ SYMBOLS = {
     "sta_image_composite": (_i, [_vp] * 4 + [_l, _l, _i, _vp]),
     "sta_image_composite_bwd": (_i, [_vp] * 4 + [_l, _l, _i, _vp]),
     "sta_latent_guide": (_i, [_vp] * 7 + [_l, _l, _l, _i, _f, _i, _vp]),
-    "sta_window_split": (_i, [_vp, _vp, _l] + [_i] * 6 + [_vp, _vp] + [_i] * 3 + [_vp]),
-    "sta_window_fuse": (_i, [_vp, _vp, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _vp]),
-    "sta_sampler_step_windows": (_i, [_vp] * 7 + [_l] + [_i] * 5 + [_vp, _vp, _i] + [_f] * 8 + [_i, _vp]),
-    "sta_sampler_step_windows_masked": (_i, [_vp] * 10 + [_l] + [_i] * 5 + [_vp, _vp, _i] + [_f] * 10 + [_i, _vp]),
-    "sta_window_blend": (_i, [_vp] * 6 + [_l] + [_i] * 5 + [_vp, _vp, _i, _f, _f, _i, _vp]),
-    # wrap-around canvases: the siblings of the five above with `int wrap` directly after s
-    "sta_window_split_ring": (_i, [_vp, _vp, _l] + [_i] * 6 + [_vp, _vp] + [_i] * 4 + [_vp]),
-    "sta_window_fuse_ring": (_i, [_vp, _vp, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _i, _vp]),
-    "sta_sampler_step_windows_ring": (_i, [_vp] * 7 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i] + [_f] * 8 + [_i, _vp]),
-    "sta_sampler_step_windows_masked_ring": (_i, [_vp] * 10 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i] + [_f] * 10 + [_i, _vp]),
-    "sta_window_blend_ring": (_i, [_vp] * 6 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i, _f, _f, _i, _vp]),
+    # canvases as overlapping windows: the grid is (ny, nx, oy, ox, s, wrap), wrap the mask of the cyclic axes (0 = the clamped grid)
+    "sta_window_split": (_i, [_vp, _vp, _l] + [_i] * 6 + [_vp, _vp] + [_i] * 4 + [_vp]),
+    "sta_window_fuse": (_i, [_vp, _vp, _l] + [_i] * 5 + [_vp, _vp, _i, _i, _i, _vp]),
+    "sta_sampler_step_windows": (_i, [_vp] * 7 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i] + [_f] * 8 + [_i, _vp]),
+    "sta_sampler_step_windows_masked": (_i, [_vp] * 10 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i] + [_f] * 10 + [_i, _vp]),
+    "sta_window_blend": (_i, [_vp] * 6 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i, _f, _f, _i, _vp]),
     # img2img on a canvas: the encoder's output -> canvas state + first window inputs
-    "sta_vae_encode_step_windows": (_i, [_vp] * 8 + [_l] + [_i] * 4 + [_vp, _vp, _i, _f, _f, _f, _i, _vp]),
-    "sta_vae_encode_step_windows_ring": (_i, [_vp] * 8 + [_l] + [_i] * 4 + [_vp, _vp, _i, _i, _f, _f, _f, _i, _vp]),
+    "sta_vae_encode_step_windows": (_i, [_vp] * 8 + [_l] + [_i] * 4 + [_vp, _vp, _i, _i, _f, _f, _f, _i, _vp]),
     # attention guidance on a canvas: the window pairs' gradient -> the updated canvas state + the next window inputs
-    "sta_latent_guide_windows": (_i, [_vp] * 8 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i, _f, _i, _vp]),
-    "sta_latent_guide_windows_ring": (_i, [_vp] * 8 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    "sta_latent_guide_windows": (_i, [_vp] * 8 + [_l] + [_i] * 5 + [_vp, _vp, _i, _i, _i, _f, _i, _vp]),
     # the hi-res fix on a canvas: a smaller latent -> the upscaled, noised canvas state + first window inputs
-    "sta_latent_upscale_step_windows": (_i, [_vp] * 5 + [_l] + [_i] * 7 + [_vp, _vp, _i, _f, _f, _i, _vp]),
-    "sta_latent_upscale_step_windows_ring": (_i, [_vp] * 5 + [_l] + [_i] * 7 + [_vp, _vp, _i, _i, _f, _f, _i, _vp]),
+    "sta_latent_upscale_step_windows": (_i, [_vp] * 5 + [_l] + [_i] * 7 + [_vp, _vp, _i, _i, _f, _f, _i, _vp]),
 }
 
 

@@ -392,12 +392,11 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  * sta_window_blend: the blend of the first call, x_out = keep (q_a x0 + q_b noise) + (1 - keep) x on [P][C][Hc][Wc] fp32, and xin (NULL =
  *   not written) = the windows of the rounded result: sta_latent_blend and sta_window_split (rows = 1) in one launch.
  *
- * Wrap-around canvases (360 degree panoramas: x closes on itself; tileable images: both axes): the five siblings sta_window_split_ring,
- * sta_window_fuse_ring, sta_sampler_step_windows_ring, sta_sampler_step_windows_masked_ring and sta_window_blend_ring take `int wrap`
- * directly after s and are otherwise their sibling, argument for argument. wrap: bit 0 = the x axis (columns, length Wc) is cyclic, bit 1 =
- * the y axis (rows, length Hc); wrap = 0 is the sibling itself, bit for bit. On a cyclic axis of length L the window at offset o covers the
- * canvas positions (o + d) mod L, d = 0 .. s - 1: a window may run over the seam, and the first and the last column share windows. The visiting
- * order (ascending w), the sum from the first covering window's value and the division by the count are unchanged.
+ * Wrap-around canvases (360 degree panoramas: x closes on itself; tileable images: both axes): every entry point of this section takes
+ * `int wrap` directly after s. wrap: bit 0 = the x axis (columns, length Wc) is cyclic, bit 1 = the y axis (rows, length Hc); wrap = 0 is
+ * the clamped grid above. On a cyclic axis of length L the window at offset o covers the canvas positions (o + d) mod L, d = 0 .. s - 1: a
+ * window may run over the seam, and the first and the last column share windows. The visiting order (ascending w), the sum from the first
+ * covering window's value and the division by the count are unchanged.
  * Rules of a cyclic axis (STA_E_ARG with text, nothing launched; a non-cyclic axis keeps the rules above): wrap in 0 .. 3; 1 ..
  * STA_MAX_WINDOW_OFFSETS offsets, the first 0, ascending multiples of 8, every offset < L (o + s <= L is NOT required), consecutive ones at
  * most s apart, and the ring closes without a gap: L - o[n - 1] <= s; s <= L (a window covers an element at most once).
@@ -408,7 +407,6 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  * n_enc), then sta_window_split (rows = 1, STA_SRC_F32) of x. Bit-equal to those two launches one after the other.
  *   h: [P][Hc][Wc][8] dtype (NHWC, 16-byte aligned);  quant_w [8][8], quant_b [8] fp32;  n_post, n_enc, x, z0: [P][4][Hc][Wc] fp32 (z0 may be
  *   NULL);  xin: NULL, or [2 P T][4][s][s] dtype = the rounded x in both rows of every covering window's pair, in sta_window_split's order.
- * sta_vae_encode_step_windows_ring takes `int wrap` directly after s, as the other `_ring` siblings do (wrap = 0: the sibling, bit for bit).
  * Rules (STA_E_ARG with text, nothing launched): the grid rules above (C = 4); every tensor but z0 / xin non-NULL; h, n_post, n_enc, x, z0,
  * xin 16-byte aligned; wrap in 0 .. 3; dtype STA_BF16 / STA_F16.
  *
@@ -427,7 +425,6 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  *     xin   = sta_window_split (rows = 1) of x_out: the rounded vector in both rows of every covering window's pair
  * Every workgroup of a canvas reduces the whole canvas's sum of squares in the same fixed order (no atomics, no hand-off): bit-reproducible,
  * a canvas's outputs depend on that canvas's inputs alone. With T = 1 bit-equal to sta_latent_guide (b = P, n = C s s, hw = s s).
- * sta_latent_guide_windows_ring takes `int wrap` directly after s (wrap = 0: the sibling, bit for bit).
  * Rules (STA_E_ARG with text, nothing launched): the grid rules above; g, x, step, count, x_out non-NULL; g, x, keep, x_out, xin 16-byte
  * aligned (step, count, stats: 4-byte); no output may overlap an input or another output; wrap in 0 .. 3; dtype STA_BF16 / STA_F16.
  *
@@ -443,57 +440,34 @@ int sta_latent_guide(const void* g, const float* x, const float* keep, const flo
  *     z_up = l0y (l0x z00 + l1x z01) + l1y (l0x z10 + l1x z11)
  *     x    = sqrt_a z_up + sqrt_1ma noise      (the noising of sta_vae_encode_step: one device definition, csrc/sta_encode_dev.h)
  * which is torch.nn.functional.interpolate(mode="bilinear", align_corners=False) on the clamped axes. No LDS, no atomics, one writer per
- * element. sta_latent_upscale_step_windows_ring takes `int wrap` directly after s (wrap = 0: the sibling, bit for bit).
+ * element.
  * Rules (STA_E_ARG with text, nothing launched): z, noise, x non-NULL; the grid rules above; h, w positive multiples of 8; Hc >= h and
  * Wc >= w (upscale only); z, noise, x, z_up, xin 16-byte aligned; wrap in 0 .. 3; dtype STA_BF16 / STA_F16.
  */
 #define STA_MAX_WINDOW_OFFSETS 16
 #define STA_SRC_F32 2
 int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
-                     int src_dtype, int dtype, void* stream);
-int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int dtype,
-                    void* stream);
+                     int wrap, int src_dtype, int dtype, void* stream);
+int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                    int dtype, void* stream);
 int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin, long P,
-                             int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t,
+                             int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t,
                              float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream);
 int sta_sampler_step_windows_masked(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
                                     const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc,
-                                    int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t, float alpha_t, float c_x,
-                                    float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream);
+                                    int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t, float alpha_t,
+                                    float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream);
 int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
-                     int Wc, int ny, int nx, const int* oy, const int* ox, int s, float q_a, float q_b, int dtype, void* stream);
-int sta_window_split_ring(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox,
-                          int s, int wrap, int src_dtype, int dtype, void* stream);
-int sta_window_fuse_ring(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
-                         int dtype, void* stream);
-int sta_sampler_step_windows_ring(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, float* m, void* xin,
-                                  long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale,
-                                  float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream);
-int sta_sampler_step_windows_masked_ring(const void* eps, const float* x, const float* m_prev, const float* noise, const float* x0,
-                                         const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc,
-                                         int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t,
-                                         float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype,
-                                         void* stream);
-int sta_window_blend_ring(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, long P, int C, int Hc,
-                          int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream);
+                     int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, void* stream);
 int sta_vae_encode_step_windows(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
-                                float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
+                                float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
                                 float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream);
-int sta_vae_encode_step_windows_ring(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x,
-                                     float* z0, void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
-                                     float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream);
 int sta_latent_guide_windows(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out, void* xin,
-                             float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int normalize,
-                             float inv_scale, int dtype, void* stream);
-int sta_latent_guide_windows_ring(const void* g, const float* x, const float* keep, const float* step, const float* count, float* x_out,
-                                  void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s,
-                                  int wrap, int normalize, float inv_scale, int dtype, void* stream);
+                             float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap,
+                             int normalize, float inv_scale, int dtype, void* stream);
 int sta_latent_upscale_step_windows(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
-                                    int Wc, int ny, int nx, const int* oy, const int* ox, int s, float sqrt_a, float sqrt_1ma, int dtype,
+                                    int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float sqrt_a, float sqrt_1ma, int dtype,
                                     void* stream);
-int sta_latent_upscale_step_windows_ring(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc,
-                                         int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float sqrt_a, float sqrt_1ma,
-                                         int dtype, void* stream);
 
 /*
  * The image front end of the CLIP fidelity loss (csrc/sta_clip.hip): the 224^2 views CLIP ViT-B/32 is fed, written directly as the rows

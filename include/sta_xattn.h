@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define STA_VERSION 0x000500 /* 0.5.0: one LDS-resident backward kernel for every head dim (round 6); 0.4.0: fragment-order entry points, trunk convolution / row GEMM / producer-side GroupNorm statistics (round 4) */
+#define STA_VERSION 0x000600 /* 0.6.0: the canvas entry points take `wrap` themselves, their `_ring` siblings are gone (an argument list changed); 0.5.0: one LDS-resident backward kernel for every head dim (round 6); 0.4.0: fragment-order entry points, trunk convolution / row GEMM / producer-side GroupNorm statistics (round 4) */
 
 enum { STA_BF16 = 0, STA_F16 = 1 };
 

@@ -199,12 +199,12 @@ def _ints(v):
 
 def _call(L, name, **kw):
     a = dict(src=PTR, xin=PTR + 0x100000, eps=PTR, out=PTR + 0x100000, x=PTR + 0x200000, m_prev=PTR + 0x300000, noise=PTR + 0x400000,
-             x_next=PTR + 0x500000, m=PTR + 0x600000, P=1, rows=1, C=4, Hc=16, Wc=40, oy=(0,), ox=(0, 16, 24), s=16, src_dtype=2, dtype=0)
+             x_next=PTR + 0x500000, m=PTR + 0x600000, P=1, rows=1, C=4, Hc=16, Wc=40, oy=(0,), ox=(0, 16, 24), s=16, wrap=0, src_dtype=2, dtype=0)
     a.update(kw)
     keep_y, oy = _ints(a["oy"]) if a["oy"] is not None else (None, 0)
     keep_x, ox = _ints(a["ox"]) if a["ox"] is not None else (None, 0)
     ny, nx = a.get("ny", len(a["oy"] or ())), a.get("nx", len(a["ox"] or ()))
-    grid = (ny, nx, oy, ox, a["s"])
+    grid = (ny, nx, oy, ox, a["s"], a["wrap"])
     if name == "sta_window_split":
         rc = L.sta_window_split(a["src"], a["xin"], a["P"], a["rows"], a["C"], a["Hc"], a["Wc"], *grid, a["src_dtype"], a["dtype"], None)
     elif name == "sta_window_fuse":
@@ -219,20 +219,21 @@ def test_abi_symbols_and_refusals_reach_no_launch():
     from sta import lib
     L = lib.load()
     vp, i, f, l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
-    assert lib.SYMBOLS["sta_window_split"] == (i, [vp, vp, l, i, i, i, i, i, i, vp, vp, i, i, i, vp])
-    assert lib.SYMBOLS["sta_window_fuse"] == (i, [vp, vp, l, i, i, i, i, i, vp, vp, i, i, vp])
-    assert lib.SYMBOLS["sta_sampler_step_windows"] == (i, [vp] * 7 + [l, i, i, i, i, i, vp, vp, i] + [f] * 8 + [i, vp])
+    assert lib.SYMBOLS["sta_window_split"] == (i, [vp, vp, l, i, i, i, i, i, i, vp, vp, i, i, i, i, vp])
+    assert lib.SYMBOLS["sta_window_fuse"] == (i, [vp, vp, l, i, i, i, i, i, vp, vp, i, i, i, vp])
+    assert lib.SYMBOLS["sta_sampler_step_windows"] == (i, [vp] * 7 + [l, i, i, i, i, i, vp, vp, i, i] + [f] * 8 + [i, vp])
+    assert not [name for name in lib.SYMBOLS if name.endswith("_ring")]         # one entry point per launch: `wrap` is an argument
     header = " ".join(open(os.path.join(ROOT, "include", "sta_unet.h")).read().split())
     for decl in ("int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, "
-                 "const int* ox, int s, int src_dtype, int dtype, void* stream);",
+                 "const int* ox, int s, int wrap, int src_dtype, int dtype, void* stream);",
                  "int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, "
-                 "int s, int dtype, void* stream);",
+                 "int s, int wrap, int dtype, void* stream);",
                  "int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, "
-                 "float* m, void* xin, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, "
-                 "float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream);",
+                 "float* m, void* xin, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, "
+                 "float scale, float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream);",
                  "#define STA_MAX_WINDOW_OFFSETS 16"):
         assert decl in header, decl
-    assert lib.MAX_WINDOW_OFFSETS == 16 and L.sta_version() == 0x000500
+    assert lib.MAX_WINDOW_OFFSETS == 16 and L.sta_version() == 0x000600
     # built as part of the sampler step's translation unit (its helpers and its flags: no fast-math flag), like sta_guide.hip:
     # tests/test_abi_dtype_cpu.py and tests/test_guidance_cpu.py pin the list of translation units
     assert lib.INCLUDED_SOURCES["sta_window.hip"] == "sta_sampler.hip" and "sta_sampler.hip" not in lib.PER_SOURCE_FLAGS

@@ -1,6 +1,6 @@
 """Attention guidance on canvases without a GPU: guide_windows_reference against the adjoint of the split (autograd, float64), the one
-window identity with guide_reference, `count` by hand, the contributing table, the refusals of sta_latent_guide_windows and its `_ring`
-sibling (fake pointers: none of these calls may reach a launch), CanvasGuidance on the host miniature of tests/test_canvas_cpu.py for
+window identity with guide_reference, `count` by hand, the contributing table, the refusals of sta_latent_guide_windows at every `wrap`
+(fake pointers: none of these calls may reach a launch), CanvasGuidance on the host miniature of tests/test_canvas_cpu.py for
 the three samplers, the off states and the CLI. The kernel is checked in test_canvas_guidance_gpu.py."""
 import ctypes
 import os
@@ -149,7 +149,7 @@ def _ints(v):
     return a, ctypes.addressof(a)
 
 
-def _call(L, ring=False, **kw):
+def _call(L, **kw):
     """P = 1, C = 4, canvas 16 x 40, windows of 16 at x = 0, 16, 24: g / xin 6 x 4 x 16 x 16 x 2 = 0x3000 bytes, x / x_out 0x2800."""
     a = dict(g=PTR, x=PTR + 0x10000, keep=PTR + 0x20000, step=PTR + 0x30000, count=PTR + 0x31000, x_out=PTR + 0x40000, xin=PTR + 0x50000,
              stats=PTR + 0x60000, P=1, C=4, Hc=16, Wc=40, oy=(0,), ox=(0, 16, 24), s=16, wrap=0, normalize=1, inv_scale=1.0, dtype=0)
@@ -158,9 +158,8 @@ def _call(L, ring=False, **kw):
     keep_x, ox = _ints(a["ox"]) if a["ox"] is not None else (None, 0)
     ny, nx = a.get("ny", len(a["oy"] or ())), a.get("nx", len(a["ox"] or ()))
     head = (a["g"], a["x"], a["keep"], a["step"], a["count"], a["x_out"], a["xin"], a["stats"], a["P"], a["C"], a["Hc"], a["Wc"], ny, nx, oy, ox,
-            a["s"])
-    tail = (a["normalize"], a["inv_scale"], a["dtype"], None)
-    rc = L.sta_latent_guide_windows_ring(*head, a["wrap"], *tail) if ring else L.sta_latent_guide_windows(*head, *tail)
+            a["s"], a["wrap"])
+    rc = L.sta_latent_guide_windows(*head, a["normalize"], a["inv_scale"], a["dtype"], None)
     return rc, L.sta_last_error().decode()
 
 
@@ -168,16 +167,13 @@ def test_abi_symbols_and_refusals_reach_no_launch():
     from sta import lib
     L = lib.load()
     vp, i, f, l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
-    assert lib.SYMBOLS["sta_latent_guide_windows"] == (i, [vp] * 8 + [l, i, i, i, i, i, vp, vp, i, i, f, i, vp])
-    assert lib.SYMBOLS["sta_latent_guide_windows_ring"] == (i, [vp] * 8 + [l, i, i, i, i, i, vp, vp, i, i, i, f, i, vp])
+    assert lib.SYMBOLS["sta_latent_guide_windows"] == (i, [vp] * 8 + [l, i, i, i, i, i, vp, vp, i, i, i, f, i, vp])
+    assert "sta_latent_guide_windows_ring" not in lib.SYMBOLS and not hasattr(L, "sta_latent_guide_windows_ring")
     header = " ".join(open(os.path.join(ROOT, "include", "sta_unet.h")).read().split())
-    for decl in ("int sta_latent_guide_windows(const void* g, const float* x, const float* keep, const float* step, const float* count, "
-                 "float* x_out, void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, "
-                 "int normalize, float inv_scale, int dtype, void* stream);",
-                 "int sta_latent_guide_windows_ring(const void* g, const float* x, const float* keep, const float* step, const float* count, "
-                 "float* x_out, void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, "
-                 "int wrap, int normalize, float inv_scale, int dtype, void* stream);"):
-        assert decl in header, decl
+    assert ("int sta_latent_guide_windows(const void* g, const float* x, const float* keep, const float* step, const float* count, "
+            "float* x_out, void* xin, float* stats, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, "
+            "int wrap, int normalize, float inv_scale, int dtype, void* stream);") in header
+    assert "sta_latent_guide_windows_ring" not in header
     assert "latent_guide_windows_kernel" in lib.NO_SPILL_KERNELS["sta_sampler.hip"]      # the by-value offset tables may not go to scratch
     assert "latent_guide_windows_kernel" in open(os.path.join(lib.CSRC, "sta_window.hip")).read()
     cases = [
@@ -200,12 +196,12 @@ def test_abi_symbols_and_refusals_reach_no_launch():
         (dict(ox=tuple(range(0, 136, 8)), Wc=16 + 8 * 16), "nx=17"),
         (dict(dtype=7), "dtype 7"), (dict(dtype=2), "dtype 2"),
     ]
-    for ring in (False, True):
-        for kw, text in cases:
-            rc, err = _call(L, ring, **kw)
-            assert rc == STA_E_ARG and text in err, (ring, kw, rc, err)
-        assert _call(L, ring, dtype=7)[1].startswith("latent_guide_windows_ring:" if ring else "latent_guide_windows:")
-        assert _call(L, ring, dtype=7, keep=0, xin=0, stats=0)[0] == STA_E_ARG      # the optional pointers may be NULL: the dtype is refused
+    for kw, text in cases:                                                      # wrap = 0: the rules of the clamped grid
+        rc, err = _call(L, **kw)
+        assert rc == STA_E_ARG and text in err, (kw, rc, err)
+    for wrap, ring in ((0, {}), (1, dict(Wc=48, ox=(0, 16, 32))), (3, dict(Wc=48, ox=(0, 16, 32), Hc=32, oy=(0, 16)))):
+        assert _call(L, wrap=wrap, dtype=7, **ring)[1].startswith("latent_guide_windows: dtype 7")       # one name whatever the wrap
+        assert _call(L, wrap=wrap, dtype=7, keep=0, xin=0, stats=0, **ring)[0] == STA_E_ARG      # the optional pointers may be NULL: the dtype is refused
     ring_cases = [
         (dict(wrap=4), "wrap=4"), (dict(wrap=-1), "wrap=-1"),
         (dict(wrap=1, Wc=48, ox=(0, 16)), "the ring does not close behind ox[1]=16"),
@@ -214,8 +210,8 @@ def test_abi_symbols_and_refusals_reach_no_launch():
         (dict(wrap=1, Wc=48, ox=(0, 16, 32), x_out=PTR + 0x10000), "aliases an input"),
     ]
     for kw, text in ring_cases:
-        rc, err = _call(L, True, **kw)
-        assert rc == STA_E_ARG and text in err, (kw, rc, err)
+        rc, err = _call(L, **kw)
+        assert rc == STA_E_ARG and text in err and err.startswith("latent_guide_windows: "), (kw, rc, err)
 
 
 # ---------------------------------------------------------------------------------------------------

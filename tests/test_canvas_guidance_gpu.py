@@ -1,6 +1,6 @@
 """sta_latent_guide_windows and attention guidance on canvases on the GPU: the kernel against guide_windows_reference in float64, the
 guarantees of its launch (one window bit-equal to sta_latent_guide, bit-reproducible, canvases independent, outputs overwritten
-completely and nothing else touched, wrap = 0 of the `_ring` symbol bit-equal to the clamped symbol, inert canvases bit-equal), the
+completely and nothing else touched, inert canvases bit-equal), the
 gradient that reaches the canvas latent on the miniature against the fp32 host chain, and the samplers end to end."""
 import pytest
 import torch
@@ -34,18 +34,14 @@ def _inputs(grid, dtype, P=2, C=4, seed=0):
     return x, gp, keep, step, count
 
 
-def _raw(grid, gp, x, keep, step, count, x_out, xin, stats, normalize=True, inv_scale=1.0, ring=None):
-    """The binding itself on caller-owned buffers. ring: None = the entry point the grid asks for, True = the `_ring` symbol whatever
-    the grid (wrap = 0 on a clamped one)."""
+def _raw(grid, gp, x, keep, step, count, x_out, xin, stats, normalize=True, inv_scale=1.0):
+    """The binding itself on caller-owned buffers."""
     from sta import canvas, lib
     ptr = lambda t: 0 if t is None else t.data_ptr()
-    args = canvas._grid_args(grid)
-    if ring and not grid.wrap:
-        args = args + (0,)
-    name = "sta_latent_guide_windows" + ("_ring" if (grid.wrap or ring) else "")
+    name = "sta_latent_guide_windows"
     lib.check(getattr(lib.load(), name)(gp.data_ptr(), x.data_ptr(), ptr(keep), step.data_ptr(), count.data_ptr(), x_out.data_ptr(), ptr(xin),
-                                        ptr(stats), x.shape[0], x.shape[1], grid.Hc, grid.Wc, *args, int(normalize), float(inv_scale),
-                                        lib.STA_BF16 if gp.dtype == torch.bfloat16 else lib.STA_F16,
+                                        ptr(stats), x.shape[0], x.shape[1], grid.Hc, grid.Wc, *canvas._grid_args(grid), int(normalize),
+                                        float(inv_scale), lib.STA_BF16 if gp.dtype == torch.bfloat16 else lib.STA_F16,
                                         torch.cuda.current_stream().cuda_stream), name)
     torch.cuda.synchronize()
 
@@ -101,7 +97,7 @@ def test_one_window_is_sta_latent_guide_bit_for_bit(dtype):
             assert torch.equal(got[0][1], x[1]) and not torch.equal(got[0][0], x[0])
 
 
-def test_launches_reproducible_canvases_independent_and_ring_symbol_with_wrap_0():
+def test_launches_reproducible_and_canvases_independent():
     from sta.canvas import latent_guide_windows
     grid = _grid(GRIDS[0])
     x, gp, keep, step, count = (t.cuda() for t in _inputs(grid, torch.float16, P=3, seed=1))
@@ -119,10 +115,6 @@ def test_launches_reproducible_canvases_independent_and_ring_symbol_with_wrap_0(
     alone = latent_guide_windows(gp[2 * rows:], x[2:3], step[2:3], count[2:3], grid, keep=keep[2:3], want_xin=True)
     torch.cuda.synchronize()
     assert torch.equal(alone[0], one[0][2:3]) and torch.equal(alone[1], one[1][2 * rows:]) and torch.equal(alone[2], one[2][2:3])
-    # the `_ring` symbol with wrap = 0 is the clamped symbol, bit for bit
-    x_out, xin, stats = torch.empty_like(x), torch.empty_like(gp), torch.empty(3, device="cuda")
-    _raw(grid, gp, x, keep, step, count, x_out, xin, stats, ring=True)
-    assert torch.equal(x_out, one[0]) and torch.equal(xin, one[1]) and torch.equal(stats, one[2])
 
 
 @pytest.mark.parametrize("grid", [GRIDS[1], GRIDS[3]])

@@ -19,7 +19,7 @@ from tests.test_img2img_cpu import _png, _script
 P = 2
 CENTRES = [[0.25, 0.4], [0.625, 0.6]]                  # canvas-normalised; on a 32 x 64 canvas the second disc straddles x = 0.5
 SF, SA, S1M = 0.18215, 0.5, 0.8660254                   # the constants of test_vae_encode_step_vs_float64
-NAMES = ("sta_vae_encode_step_windows", "sta_vae_encode_step_windows_ring")
+NAME = "sta_vae_encode_step_windows"
 
 
 def _grid(args):
@@ -33,18 +33,17 @@ def _grid(args):
 def test_symbols_are_declared_and_bound_with_matching_argument_counts():
     from sta import lib
     vp, i, f, l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
-    assert lib.SYMBOLS[NAMES[0]] == (i, [vp] * 8 + [l, i, i, i, i, vp, vp, i, f, f, f, i, vp])
-    assert lib.SYMBOLS[NAMES[1]] == (i, [vp] * 8 + [l, i, i, i, i, vp, vp, i, i, f, f, f, i, vp])
+    assert lib.SYMBOLS[NAME] == (i, [vp] * 8 + [l, i, i, i, i, vp, vp, i, i, f, f, f, i, vp])
+    assert NAME + "_ring" not in lib.SYMBOLS
     header = " ".join(open(os.path.join(ROOT, "include", "sta_unet.h")).read().split())
     head = ("(const void* h, const float* quant_w, const float* quant_b, const float* n_post, const float* n_enc, float* x, float* z0, "
-            "void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, ")
+            "void* xin, long P, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, ")
     tail = "float scale_factor, float sqrt_a, float sqrt_1ma, int dtype, void* stream);"
-    for name, mid in zip(NAMES, ("", "int wrap, ")):
-        decl = "int " + name + head + mid + tail
-        assert decl in header, decl
-        assert decl.count(",") + 1 == len(lib.SYMBOLS[name][1])
+    decl = "int " + NAME + head + tail
+    assert decl in header and NAME + "_ring" not in header, decl
+    assert decl.count(",") + 1 == len(lib.SYMBOLS[NAME][1])
     L = lib.load()
-    assert all(hasattr(L, n) for n in NAMES)
+    assert hasattr(L, NAME) and not hasattr(L, NAME + "_ring")
     # the kernel lives with the window kernels, in the sampler step's unit (no flags), under the no-scratch rule of its siblings
     assert "vae_encode_step_windows_kernel" in lib.NO_SPILL_KERNELS["sta_sampler.hip"] and "sta_sampler.hip" not in lib.PER_SOURCE_FLAGS
     window = open(os.path.join(lib.CSRC, "sta_window.hip")).read()
@@ -55,23 +54,22 @@ def test_symbols_are_declared_and_bound_with_matching_argument_counts():
     assert "expf" in open(os.path.join(lib.CSRC, "sta_encode_dev.h")).read()
 
 
-def _call(L, name, **kw):
+def _call(L, **kw):
     a = dict(h=PTR, qw=PTR + 0x100000, qb=PTR + 0x200000, n_post=PTR + 0x300000, n_enc=PTR + 0x400000, x=PTR + 0x500000, z0=PTR + 0x600000,
              xin=PTR + 0x700000, P=2, Hc=16, Wc=40, oy=(0,), ox=(0, 16, 24), s=16, wrap=0, dtype=0)
     a.update(kw)
     keep_y, oy = _ints(a["oy"]) if a["oy"] is not None else (None, 0)
     keep_x, ox = _ints(a["ox"]) if a["ox"] is not None else (None, 0)
     args = [a[k] for k in ("h", "qw", "qb", "n_post", "n_enc", "x", "z0", "xin", "P", "Hc", "Wc")] + [len(a["oy"] or ()), len(a["ox"] or ()), oy, ox,
-                                                                                                      a["s"]]
-    if name.endswith("_ring"):
-        args.append(a["wrap"])
-    rc = getattr(L, name)(*args, SF, SA, S1M, a["dtype"], None)
+                                                                                                      a["s"], a["wrap"]]
+    rc = getattr(L, NAME)(*args, SF, SA, S1M, a["dtype"], None)
     return rc, L.sta_last_error().decode()
 
 
-@pytest.mark.parametrize("name", NAMES)
-def test_argument_rules_reach_no_launch(name):
-    """Every pointer is fake: a call that reached a launch would fault (or, without a GPU, fail with a launch error, not STA_E_ARG)."""
+@pytest.mark.parametrize("wrap", [0, 1, 2, 3])
+def test_argument_rules_reach_no_launch(wrap):
+    """Every pointer is fake: a call that reached a launch would fault (or, without a GPU, fail with a launch error, not STA_E_ARG).
+    The default grid is valid at every wrap (40 - 24 <= 16: as a ring it closes); an axis is held to the clamped rules or to the ring's."""
     from sta import lib
     L = lib.load()
     bad = [(dict(oy=None), "null pointer"), (dict(ox=None), "null pointer")]
@@ -79,22 +77,28 @@ def test_argument_rules_reach_no_launch(name):
     bad += [({k: PTR + 0x800008}, "16-byte aligned") for k in ("h", "n_post", "n_enc", "x", "z0", "xin")]     # a misaligned pointer
     bad += [(dict(ox=(0, 12, 24)), "ox[1]=12 is not a multiple of 8"),                                        # the grid rules, verbatim
             (dict(ox=(0, 24)), "gap between ox[0]=0 and ox[1]=24"),
-            (dict(ox=(0, 16)), "gap behind ox[1]=16"),
-            (dict(ox=(0, 16, 32)), "ox[2]=32 out of range"),
             (dict(ox=(8, 16, 24)), "ox[0]=8 unsorted"),
             (dict(P=0), "P=0"), (dict(Wc=44), "Wc=44"), (dict(s=12), "s=12"), (dict(Hc=8), "Hc=8"),
             (dict(ox=tuple(range(0, 136, 8)), Wc=16 + 8 * 16), "nx=17"),
             (dict(dtype=7), "dtype 7"), (dict(dtype=2), "dtype 2")]                                           # a bad dtype
-    if name.endswith("_ring"):
-        bad += [(dict(wrap=4), "wrap=4"), (dict(wrap=-1), "wrap=-1"),
-                (dict(wrap=1, ox=(0, 16), Wc=40), "the ring does not close behind ox[1]=16"),                # a ring that does not close
-                (dict(wrap=1, ox=(0, 16, 40), Wc=40), "ox[2]=40 is not on the wrapped axis"),
-                (dict(wrap=2, oy=(0, 8), Hc=16, dtype=7), "dtype 7")]                                        # a valid ring reaches the dtype rule
+    bad += [(dict(wrap=4), "wrap=4"), (dict(wrap=-1), "wrap=-1")]
+    if wrap & 1:                                                                                              # x closes on itself: the ring's rules
+        bad += [(dict(ox=(0, 16)), "the ring does not close behind ox[1]=16"),
+                (dict(ox=(0, 16, 40)), "ox[2]=40 is not on the wrapped axis"),
+                (dict(ox=(0, 16, 32), dtype=7), "dtype 7")]                                                   # o + s > L is allowed there
+    else:
+        bad += [(dict(ox=(0, 16)), "gap behind ox[1]=16"), (dict(ox=(0, 16, 32)), "ox[2]=32 out of range")]
+    if wrap & 2:
+        bad += [(dict(oy=(0, 16), Hc=48), "the ring does not close behind oy[1]=16"),
+                (dict(oy=(0, 8), Hc=16, dtype=7), "dtype 7")]                                                 # a valid ring reaches the dtype rule
+    else:
+        bad += [(dict(oy=(0, 8)), "oy[1]=8 out of range")]
     for kw, text in bad:
-        rc, err = _call(L, name, **kw)
-        assert rc == STA_E_ARG and text in err, (name, kw, rc, err)
+        rc, err = _call(L, **dict(dict(wrap=wrap), **kw))
+        assert rc == STA_E_ARG and text in err, (wrap, kw, rc, err)
+        assert err == "null pointer" or err.startswith(NAME[len("sta_"):] + ": "), (wrap, kw, err)            # one name whatever the wrap
     # the optional tensors may be NULL: the call then gets as far as the last rule
-    rc, err = _call(L, name, z0=0, xin=0, dtype=7)
+    rc, err = _call(L, wrap=wrap, z0=0, xin=0, dtype=7)
     assert rc == STA_E_ARG and "dtype 7" in err
 
 

@@ -1,4 +1,4 @@
-"""img2img on canvases on the MI355X: the fused entry launch (sta_vae_encode_step_windows and its `_ring` sibling, csrc/sta_window.hip)
+"""img2img on canvases on the MI355X: the fused entry launch (sta_vae_encode_step_windows, csrc/sta_window.hip)
 against a float64 restatement, bit for bit against the two launches it replaces (sta_vae_encode_step + sta_window_split) and under rolls
 of a ring; `DDIMSampler.decode_canvas` against the fp32 host trajectory, `decode`, `decode_batch`, `sample_canvas`, the unfused entry and
 graph replay; scripts/img2img.py --canvas end to end."""
@@ -60,10 +60,9 @@ def test_kernel_vs_float64(shape, dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", CLAMPED + SHAPES)
-def test_kernel_is_the_two_launches_it_replaces(shape, dtype, monkeypatch):
-    """Bit for bit: x, z0, xin of the one launch == sta_vae_encode_step followed by sta_window_split[_ring](rows = 1, STA_SRC_F32); and the
-    `_ring` entry point with wrap = 0 on a clamped grid == the clamped entry point."""
-    from sta import canvas, fused, lib
+def test_kernel_is_the_two_launches_it_replaces(shape, dtype):
+    """Bit for bit: x, z0, xin of the one launch == sta_vae_encode_step followed by sta_window_split(rows = 1, STA_SRC_F32)."""
+    from sta import canvas, fused
     g = _grid(shape)
     h, qw, qb, n_post, n_enc = _tensors(g, dtype, seed=5)
     got = _launch(g, h, qw, qb, n_post, n_enc, want_z0=True, want_xin=True)
@@ -73,12 +72,6 @@ def test_kernel_is_the_two_launches_it_replaces(shape, dtype, monkeypatch):
     torch.cuda.synchronize()
     for a, b in zip(got, (x, z0, xin)):
         assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
-    if not g.wrap:
-        names, inner = [], canvas._grid_args
-        monkeypatch.setattr(canvas, "_grid_args", lambda grid: inner(grid)[:5] + (0,))
-        monkeypatch.setattr(canvas, "_entry", lambda name, grid: (names.append(name), (getattr(lib.load(), name + "_ring"), name + "_ring"))[1])
-        ring = _launch(g, h, qw, qb, n_post, n_enc, want_z0=True, want_xin=True)
-        assert names == ["sta_vae_encode_step_windows"] and all(torch.equal(a, b) for a, b in zip(ring, got))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

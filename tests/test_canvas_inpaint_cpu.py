@@ -102,11 +102,11 @@ def _ints(v):
 def _call(L, name, **kw):
     a = dict(eps=PTR, x=PTR + 0x200000, m_prev=PTR + 0x300000, noise=PTR + 0x400000, x_next=PTR + 0x500000, m=PTR + 0x600000,
              xin=PTR + 0x100000, x0=PTR + 0x700000, keep=PTR + 0x800000, qnoise=PTR + 0x900000, x_out=PTR + 0x500000, P=1, C=4, Hc=16,
-             Wc=40, oy=(0,), ox=(0, 16, 24), s=16, alpha_t=0.8, dtype=0)
+             Wc=40, oy=(0,), ox=(0, 16, 24), s=16, wrap=0, alpha_t=0.8, dtype=0)
     a.update(kw)
     keep_y, oy = _ints(a["oy"]) if a["oy"] is not None else (None, 0)
     keep_x, ox = _ints(a["ox"]) if a["ox"] is not None else (None, 0)
-    grid = (len(a["oy"] or ()), len(a["ox"] or ()), oy, ox, a["s"])
+    grid = (len(a["oy"] or ()), len(a["ox"] or ()), oy, ox, a["s"], a["wrap"])
     if name == "sta_sampler_step_windows_masked":
         rc = L.sta_sampler_step_windows_masked(a["eps"], a["x"], a["m_prev"], a["noise"], a["x0"], a["keep"], a["qnoise"], a["x_next"], a["m"],
                                                a["xin"], a["P"], a["C"], a["Hc"], a["Wc"], *grid, 7.5, 0.5, a["alpha_t"], 1.0, 0.1, 0.0, 0.2,
@@ -121,15 +121,15 @@ def test_abi_symbols_and_refusals_reach_no_launch():
     from sta import lib
     L = lib.load()
     vp, i, f, l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
-    assert lib.SYMBOLS["sta_sampler_step_windows_masked"] == (i, [vp] * 10 + [l, i, i, i, i, i, vp, vp, i] + [f] * 10 + [i, vp])
-    assert lib.SYMBOLS["sta_window_blend"] == (i, [vp] * 6 + [l, i, i, i, i, i, vp, vp, i, f, f, i, vp])
+    assert lib.SYMBOLS["sta_sampler_step_windows_masked"] == (i, [vp] * 10 + [l, i, i, i, i, i, vp, vp, i, i] + [f] * 10 + [i, vp])
+    assert lib.SYMBOLS["sta_window_blend"] == (i, [vp] * 6 + [l, i, i, i, i, i, vp, vp, i, i, f, f, i, vp])
     header = " ".join(open(os.path.join(ROOT, "include", "sta_unet.h")).read().split())
     for decl in ("int sta_sampler_step_windows_masked(const void* eps, const float* x, const float* m_prev, const float* noise, "
                  "const float* x0, const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, "
-                 "int Wc, int ny, int nx, const int* oy, const int* ox, int s, float scale, float sigma_t, float alpha_t, float c_x, "
+                 "int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t, float alpha_t, float c_x, "
                  "float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream);",
                  "int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, "
-                 "long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, float q_a, float q_b, int dtype, "
+                 "long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, int dtype, "
                  "void* stream);"):
         assert decl in header, decl
     # one definition of the blend, shared by the square-image kernels and the canvas kernels

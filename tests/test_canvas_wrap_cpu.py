@@ -1,6 +1,6 @@
 """Wrap-around canvases (360 degree panoramas, tileable images) without a GPU: the ring grid, the per-window centres against the CYCLIC
 canvas-level disc, the torch restatements of the window kernels on a ring (fuse of split, roll equivariance), the argument rules of the
-five `_ring` C entry points (fake pointers: none of these calls may reach a launch), `sample_canvas(wrap=)` / `inpaint_canvas(wrap=)`
+five C entry points on a wrapped grid (fake pointers: none of these calls may reach a launch), `sample_canvas(wrap=)` / `inpaint_canvas(wrap=)`
 of the samplers on the host miniature, the padded decode and the CLI. The kernels are checked in test_canvas_wrap_gpu.py."""
 import ctypes
 import os
@@ -22,8 +22,8 @@ COVER2 = [SHAPES[0], SHAPES[1], SHAPES[4]]             # at most two covering wi
 DTYPES = [torch.float16, torch.bfloat16]
 Q_A, Q_B = 0.8253, 0.5647
 S_LAT, STEPS, K = 32, 4, 2
-RING = ("sta_window_split_ring", "sta_window_fuse_ring", "sta_sampler_step_windows_ring", "sta_sampler_step_windows_masked_ring",
-        "sta_window_blend_ring")
+FIVE = ("sta_window_split", "sta_window_fuse", "sta_sampler_step_windows", "sta_sampler_step_windows_masked", "sta_window_blend")
+WINDOW_ENTRY_POINTS = FIVE + ("sta_vae_encode_step_windows", "sta_latent_guide_windows", "sta_latent_upscale_step_windows")
 
 
 def _grid(args):
@@ -263,64 +263,68 @@ def _call(L, name, **kw):
     ny, nx = a.get("ny", len(a["oy"] or ())), a.get("nx", len(a["ox"] or ()))
     grid = (ny, nx, oy, ox, a["s"], a["wrap"])
     coef = (7.5, 0.5, a["alpha_t"], 1.0, 0.1, 0.0, 0.2, 0.0)
-    if name == "sta_window_split_ring":
-        rc = L.sta_window_split_ring(a["src"], a["xin"], a["P"], a["rows"], a["C"], a["Hc"], a["Wc"], *grid, a["src_dtype"], a["dtype"], None)
-    elif name == "sta_window_fuse_ring":
-        rc = L.sta_window_fuse_ring(a["eps"], a["out"], a["P"], a["C"], a["Hc"], a["Wc"], *grid, a["dtype"], None)
-    elif name == "sta_sampler_step_windows_ring":
-        rc = L.sta_sampler_step_windows_ring(a["eps"], a["x"], a["m_prev"], a["noise"], a["x_next"], a["m"], a["xin"], a["P"], a["C"], a["Hc"],
-                                             a["Wc"], *grid, *coef, a["dtype"], None)
-    elif name == "sta_sampler_step_windows_masked_ring":
-        rc = L.sta_sampler_step_windows_masked_ring(a["eps"], a["x"], a["m_prev"], a["noise"], a["x0"], a["keep"], a["qnoise"], a["x_next"],
-                                                    a["m"], a["xin"], a["P"], a["C"], a["Hc"], a["Wc"], *grid, *coef, Q_A, Q_B, a["dtype"], None)
+    if name == "sta_window_split":
+        rc = L.sta_window_split(a["src"], a["xin"], a["P"], a["rows"], a["C"], a["Hc"], a["Wc"], *grid, a["src_dtype"], a["dtype"], None)
+    elif name == "sta_window_fuse":
+        rc = L.sta_window_fuse(a["eps"], a["out"], a["P"], a["C"], a["Hc"], a["Wc"], *grid, a["dtype"], None)
+    elif name == "sta_sampler_step_windows":
+        rc = L.sta_sampler_step_windows(a["eps"], a["x"], a["m_prev"], a["noise"], a["x_next"], a["m"], a["xin"], a["P"], a["C"], a["Hc"],
+                                        a["Wc"], *grid, *coef, a["dtype"], None)
+    elif name == "sta_sampler_step_windows_masked":
+        rc = L.sta_sampler_step_windows_masked(a["eps"], a["x"], a["m_prev"], a["noise"], a["x0"], a["keep"], a["qnoise"], a["x_next"],
+                                               a["m"], a["xin"], a["P"], a["C"], a["Hc"], a["Wc"], *grid, *coef, Q_A, Q_B, a["dtype"], None)
     else:
-        rc = L.sta_window_blend_ring(a["x"], a["x0"], a["keep"], a["qnoise"], a["x_next"], a["xin"], a["P"], a["C"], a["Hc"], a["Wc"], *grid,
-                                     Q_A, Q_B, a["dtype"], None)
+        rc = L.sta_window_blend(a["x"], a["x0"], a["keep"], a["qnoise"], a["x_next"], a["xin"], a["P"], a["C"], a["Hc"], a["Wc"], *grid,
+                                Q_A, Q_B, a["dtype"], None)
     return rc, L.sta_last_error().decode()
 
 
 def test_ring_abi_symbols_and_signatures():
+    """One entry point per launch: `int wrap` directly after s in each of them, no `_ring` sibling left in the binding table, the header
+    or the library."""
     from sta import lib
     L = lib.load()
     vp, i, f, l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
     grid = [i, i, vp, vp, i, i]                                                 # ny, nx, oy, ox, s, wrap
-    assert lib.SYMBOLS["sta_window_split_ring"] == (i, [vp, vp, l, i, i, i, i] + grid + [i, i, vp])
-    assert lib.SYMBOLS["sta_window_fuse_ring"] == (i, [vp, vp, l, i, i, i] + grid + [i, vp])
-    assert lib.SYMBOLS["sta_sampler_step_windows_ring"] == (i, [vp] * 7 + [l, i, i, i] + grid + [f] * 8 + [i, vp])
-    assert lib.SYMBOLS["sta_sampler_step_windows_masked_ring"] == (i, [vp] * 10 + [l, i, i, i] + grid + [f] * 10 + [i, vp])
-    assert lib.SYMBOLS["sta_window_blend_ring"] == (i, [vp] * 6 + [l, i, i, i] + grid + [f, f, i, vp])
-    for name in RING:                                                           # the sibling's list with one int after s
-        old = lib.SYMBOLS[name[:-len("_ring")]][1]
-        at = [k for k in range(len(old) - 2) if old[k:k + 3] == [vp, vp, i] and old[k - 1] == i][-1] + 3
-        assert lib.SYMBOLS[name][1] == old[:at] + [i] + old[at:], name
-        assert getattr(L, name).argtypes == lib.SYMBOLS[name][1] and getattr(L, name).restype is i
+    assert lib.SYMBOLS["sta_window_split"] == (i, [vp, vp, l, i, i, i, i] + grid + [i, i, vp])
+    assert lib.SYMBOLS["sta_window_fuse"] == (i, [vp, vp, l, i, i, i] + grid + [i, vp])
+    assert lib.SYMBOLS["sta_sampler_step_windows"] == (i, [vp] * 7 + [l, i, i, i] + grid + [f] * 8 + [i, vp])
+    assert lib.SYMBOLS["sta_sampler_step_windows_masked"] == (i, [vp] * 10 + [l, i, i, i] + grid + [f] * 10 + [i, vp])
+    assert lib.SYMBOLS["sta_window_blend"] == (i, [vp] * 6 + [l, i, i, i] + grid + [f, f, i, vp])
+    assert not [name for name in lib.SYMBOLS if name.endswith("_ring")]
+    for name in WINDOW_ENTRY_POINTS:
+        args = lib.SYMBOLS[name][1]
+        assert [args[k:k + 6] for k in range(len(args) - 5)].count(grid) == 1, name            # the grid with its wrap, once
+        assert getattr(L, name).argtypes == args and getattr(L, name).restype is i
+        assert not hasattr(L, name + "_ring"), name                             # the library exports no sibling
     header = " ".join(open(os.path.join(ROOT, "include", "sta_unet.h")).read().split())
-    for decl in ("int sta_window_split_ring(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, "
+    for decl in ("int sta_window_split(const void* src, void* xin, long P, int rows, int C, int Hc, int Wc, int ny, int nx, const int* oy, "
                  "const int* ox, int s, int wrap, int src_dtype, int dtype, void* stream);",
-                 "int sta_window_fuse_ring(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, "
+                 "int sta_window_fuse(const void* eps, void* out, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, "
                  "const int* ox, int s, int wrap, int dtype, void* stream);",
-                 "int sta_sampler_step_windows_ring(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, "
+                 "int sta_sampler_step_windows(const void* eps, const float* x, const float* m_prev, const float* noise, float* x_next, "
                  "float* m, void* xin, long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, "
                  "float scale, float sigma_t, float alpha_t, float c_x, float c_m, float c_p, float c_e, float c_n, int dtype, void* stream);",
-                 "int sta_sampler_step_windows_masked_ring(const void* eps, const float* x, const float* m_prev, const float* noise, "
+                 "int sta_sampler_step_windows_masked(const void* eps, const float* x, const float* m_prev, const float* noise, "
                  "const float* x0, const float* keep, const float* qnoise, float* x_next, float* m, void* xin, long P, int C, int Hc, int Wc, "
                  "int ny, int nx, const int* oy, const int* ox, int s, int wrap, float scale, float sigma_t, float alpha_t, float c_x, "
                  "float c_m, float c_p, float c_e, float c_n, float q_a, float q_b, int dtype, void* stream);",
-                 "int sta_window_blend_ring(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, "
+                 "int sta_window_blend(const float* x, const float* x0, const float* keep, const float* noise, float* x_out, void* xin, "
                  "long P, int C, int Hc, int Wc, int ny, int nx, const int* oy, const int* ox, int s, int wrap, float q_a, float q_b, "
                  "int dtype, void* stream);"):
         assert decl in header, decl
-    assert "sta_window_split_ring" in header.split("#define STA_MAX_WINDOW_OFFSETS")[0]      # documented in the section's comment block
-    assert L.sta_version() == 0x000500
+    assert "_ring(" not in header
+    assert "`int wrap` directly after s" in header.split("#define STA_MAX_WINDOW_OFFSETS")[0]   # documented in the section's comment block
+    assert L.sta_version() == 0x000600
     for want in ("window_split_kernel", "window_fuse_kernel", "sampler_step_windows_kernel", "sampler_step_windows_masked_kernel",
                  "window_blend_kernel"):                                        # by substring: every wrap instantiation falls under the rule
         assert want in lib.NO_SPILL_KERNELS["sta_sampler.hip"]
 
 
-@pytest.mark.parametrize("name", RING)
+@pytest.mark.parametrize("name", FIVE)
 def test_ring_argument_rules_reach_no_launch(name):
     """Every rule of a wrapped axis -> STA_E_ARG with its numbers; the rules of a non-wrapped axis are the clamped grid's; an accepted
-    grid is shown by the refusal that comes after the grid's (dtype 7), never by a launch."""
+    grid is shown by the refusal that comes after the grid's (dtype 7), never by a launch. The texts carry the entry point's name."""
     from sta import lib
     L = lib.load()
     ring6, ring17 = (0, 8, 16, 24, 32, 40), tuple(range(0, 136, 8))
@@ -352,6 +356,7 @@ def test_ring_argument_rules_reach_no_launch(name):
     for kw, text in refused:
         rc, err = _call(L, name, **kw)
         assert rc == STA_E_ARG and text in err, (name, kw, rc, err)
+        assert err == "null pointer" or err.startswith(name[len("sta_"):] + ": "), (name, kw, err)
     accepted = [dict(), dict(ox=(0, 16, 32)), dict(ox=(0, 16, 24, 40)), dict(ox=(0, 8, 24, 32)),       # o + s > L is allowed
                 dict(ox=tuple(range(0, 128, 8)), Wc=128),                                              # 16 offsets
                 dict(wrap=2, ox=(0,), Wc=16, Hc=48, oy=ring6), dict(wrap=3, Hc=48, oy=ring6), dict(wrap=3, Hc=32, Wc=32, oy=(0, 8, 16, 24), ox=(0, 8, 16, 24)),
@@ -359,12 +364,12 @@ def test_ring_argument_rules_reach_no_launch(name):
     for kw in accepted:
         rc, err = _call(L, name, dtype=7, **kw)
         assert rc == STA_E_UNSUP and err == "dtype 7", (name, kw, rc, err)
-    rc, err = _call(L, name, **{dict(sta_window_split_ring="src", sta_window_fuse_ring="eps", sta_window_blend_ring="x").get(name, "eps"): 0})
+    rc, err = _call(L, name, **{dict(sta_window_split="src", sta_window_fuse="eps", sta_window_blend="x").get(name, "eps"): 0})
     assert rc == STA_E_ARG and "null pointer" in err
     if "masked" in name or "blend" in name:
         rc, err = _call(L, name, keep=0)
         assert rc == STA_E_ARG and "null pointer" in err
-    rc, err = _call(L, name, **{"out" if name == "sta_window_fuse_ring" else "xin": PTR + 0x100008})       # an output each of the five takes
+    rc, err = _call(L, name, **{"out" if name == "sta_window_fuse" else "xin": PTR + 0x100008})       # an output each of the five takes
     assert rc == STA_E_ARG and "16-byte aligned" in err
 
 

@@ -1,5 +1,5 @@
-"""Wrap-around canvases on the MI355X: the five `_ring` launches of csrc/sta_window.hip against their clamped siblings (wrap = 0), the
-torch restatements of sta.canvas on a ring and float64, their roll equivariance, the masked identities, and `sample_canvas(wrap="x")` /
+"""Wrap-around canvases on the MI355X: the five launches of csrc/sta_window.hip on wrapped grids against the torch restatements of
+sta.canvas on a ring and float64, their roll equivariance, the masked identities, and `sample_canvas(wrap="x")` /
 `inpaint_canvas(wrap="x")` against the fp32 host trajectory, the three-launch form and graph replay."""
 import pytest
 import torch
@@ -37,34 +37,6 @@ def _tensors(g, dtype, seed):
 # kernels
 # ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("grid", [(24, 40, 16, 8), (16, 40, 16, 16), (32, 64, 32, 16)])
-def test_ring_entry_points_with_wrap_0_are_their_siblings(grid, dtype, monkeypatch):
-    """The dispatchers forced onto the `_ring` entry points with wrap = 0 on clamped grids: every output of the five launches equals
-    the sibling's bit for bit."""
-    from sta import canvas, lib, solver
-    g = _grid(grid)
-    eps, x, m_prev, noise, x0, qn = _tensors(g, dtype, 3)
-    bl = solver.Blend(x0, keep_mask(P, g.Hc, g.Wc).cuda(), qn, Q_A, Q_B)
-    pair = torch.randn(2 * P, 4, g.Hc, g.Wc, device="cuda").to(dtype)
-
-    def run():
-        out = [canvas.window_split(x, g, dtype), canvas.window_split(pair, g, dtype, rows=2), canvas.window_fuse(eps, g)]
-        for mode in MODES:
-            out += canvas.sampler_step_windows(eps, x, m_prev, noise, _coef(mode), g, want_xin=True)
-            out += canvas.sampler_step_windows_masked(eps, x, m_prev, noise, _coef(mode), bl, g, want_xin=True)
-        return out + list(canvas.window_blend(x, bl, g, dtype, want_xin=True))
-    want = run()
-    names, inner = [], canvas._grid_args
-    monkeypatch.setattr(canvas, "_grid_args", lambda grid: inner(grid)[:5] + (0,))
-    monkeypatch.setattr(canvas, "_entry", lambda name, grid: (names.append(name), (getattr(lib.load(), name + "_ring"), name + "_ring"))[1])
-    got = run()
-    assert set(names) == {"sta_window_split", "sta_window_fuse", "sta_sampler_step_windows", "sta_sampler_step_windows_masked", "sta_window_blend"}
-    assert len(got) == len(want) == 3 + 6 * len(MODES) + 2
-    for k, (a, b) in enumerate(zip(got, want)):
-        assert a.dtype == b.dtype and torch.equal(a, b), k
-
-
-@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", SHAPES)
 def test_ring_split_fuse_and_blend_equal_their_restatements(shape, dtype):
     """Bit for bit: both `rows` forms and source types of the split, the fuse (fp32 sum in ascending w, IEEE division, one rounding) and
@@ -98,7 +70,7 @@ def test_ring_split_fuse_and_blend_equal_their_restatements(shape, dtype):
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("mode", MODES)
 def test_ring_step_launches_vs_fp64(mode, shape, dtype):
-    """sta_sampler_step_windows_ring and sta_sampler_step_windows_masked_ring for every presence of m_prev / noise, held to the float64
+    """sta_sampler_step_windows and sta_sampler_step_windows_masked on a ring for every presence of m_prev / noise, held to the float64
     bound of tests/test_canvas_gpu.py and tests/test_canvas_inpaint_gpu.py, 1e-6 (1 + the sum of the absolute terms), on the
     restatement's fp32 overlap means (bit-checked by the fuse test); xin is the split of the kernel's own rounded x_next, bit for bit;
     a launch without the spare tensors and a second launch give the same bits. Measured: at most 2.1e-7."""
@@ -233,7 +205,7 @@ def _host(kind, masked):
 @pytest.mark.parametrize("dtype,tol_max,tol_mean", TOLS)
 @pytest.mark.parametrize("kind", ["plms", "ddim", "dpm"])
 def test_ring_canvas_vs_fp32_host_trajectory(kind, dtype, tol_max, tol_mean):
-    """sample_canvas(wrap="x") on the GPU (PLMS: ring split + fuse per call; DDIM and DPM-Solver++: one sta_sampler_step_windows_ring
+    """sample_canvas(wrap="x") on the GPU (PLMS: ring split + fuse per call; DDIM and DPM-Solver++: one sta_sampler_step_windows
     launch per call) vs the same trajectory in fp32 on the host, inside TOLS of tests/test_solver_gpu.py, the bounds of
     tests/test_canvas_gpu.py: fp16 max 1 %, mean 0.5 %; bf16 max 3 %, mean 2 % of max|x| / mean|x|.
     Measured (max / mean): PLMS fp16 0.25 % / 0.25 %, bf16 1.30 % / 1.19 %; DDIM fp16 0.23 % / 0.25 %, bf16 1.17 % / 1.21 %; DPM-Solver++
@@ -250,7 +222,7 @@ def test_ring_canvas_vs_fp32_host_trajectory(kind, dtype, tol_max, tol_mean):
 @pytest.mark.parametrize("dtype,tol_max,tol_mean", TOLS)
 @pytest.mark.parametrize("kind", ["ddim", "dpm"])
 def test_ring_inpaint_canvas_vs_fp32_host_trajectory(kind, dtype, tol_max, tol_mean):
-    """inpaint_canvas(wrap="x") with a mixed keep mask on the GPU (sta_window_blend_ring, then one sta_sampler_step_windows_masked_ring
+    """inpaint_canvas(wrap="x") with a mixed keep mask on the GPU (sta_window_blend, then one sta_sampler_step_windows_masked
     launch per call) vs the host, inside TOLS, the bounds of tests/test_canvas_inpaint_gpu.py.
     Measured (max / mean): DDIM fp16 0.27 % / 0.22 %, bf16 1.45 % / 1.02 %; DPM-Solver++ fp16 0.27 % / 0.23 %, bf16 1.10 % / 1.10 %."""
     keep, x0 = _kept()

@@ -18,7 +18,7 @@ from tests.test_canvas_cpu import _sampler as _any_sampler
 
 P, C, S, STRIDE = 2, 4, 16, 8
 SA, S1M = 0.5, 0.8660254
-NAMES = ("sta_latent_upscale_step_windows", "sta_latent_upscale_step_windows_ring")
+NAME = "sta_latent_upscale_step_windows"
 # (h, w, Hc, Wc, wrap): window 16, stride 8 — 2- and 4-fold overlap, clamped last windows, 2 .. 6 lane vectors per row, taps on both edges
 INTEGER = [(16, 24, 32, 48, "")]
 RATIONAL = [(16, 16, 24, 40, "")]                       # 1.5 x and 2.5 x
@@ -97,18 +97,17 @@ def bounds(shape, seed=3):
 def test_symbols_are_declared_and_bound_with_matching_argument_counts():
     from sta import lib
     vp, i, f, l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
-    assert lib.SYMBOLS[NAMES[0]] == (i, [vp] * 5 + [l, i, i, i, i, i, i, i, vp, vp, i, f, f, i, vp])
-    assert lib.SYMBOLS[NAMES[1]] == (i, [vp] * 5 + [l, i, i, i, i, i, i, i, vp, vp, i, i, f, f, i, vp])
+    assert lib.SYMBOLS[NAME] == (i, [vp] * 5 + [l, i, i, i, i, i, i, i, vp, vp, i, i, f, f, i, vp])
+    assert NAME + "_ring" not in lib.SYMBOLS
     header = " ".join(open(os.path.join(ROOT, "include", "sta_unet.h")).read().split())
     head = ("(const float* z, const float* noise, float* x, float* z_up, void* xin, long P, int C, int h, int w, int Hc, int Wc, int ny, "
-            "int nx, const int* oy, const int* ox, int s, ")
+            "int nx, const int* oy, const int* ox, int s, int wrap, ")
     tail = "float sqrt_a, float sqrt_1ma, int dtype, void* stream);"
-    for name, mid in zip(NAMES, ("", "int wrap, ")):
-        decl = "int " + name + head + mid + tail
-        assert decl in header, decl
-        assert decl.count(",") + 1 == len(lib.SYMBOLS[name][1])
+    decl = "int " + NAME + head + tail
+    assert decl in header and NAME + "_ring" not in header, decl
+    assert decl.count(",") + 1 == len(lib.SYMBOLS[NAME][1])
     L = lib.load()
-    assert all(hasattr(L, n) for n in NAMES)
+    assert hasattr(L, NAME) and not hasattr(L, NAME + "_ring")
     # with the window kernels, in the sampler step's unit (no flags), under the no-scratch rule of its siblings
     assert "latent_upscale_step_windows_kernel" in lib.NO_SPILL_KERNELS["sta_sampler.hip"] and "sta_sampler.hip" not in lib.PER_SOURCE_FLAGS
     window = open(os.path.join(lib.CSRC, "sta_window.hip")).read()
@@ -118,23 +117,22 @@ def test_symbols_are_declared_and_bound_with_matching_argument_counts():
     assert dev.count("float noise1(") == 1 and dev.count("noise1(") == 2 and "noise1(zu[k]" in window
 
 
-def _call(L, name, **kw):
+def _call(L, **kw):
     a = dict(z=PTR, noise=PTR + 0x100000, x=PTR + 0x200000, z_up=PTR + 0x300000, xin=PTR + 0x400000, P=2, C=4, h=16, w=24, Hc=16, Wc=40,
              oy=(0,), ox=(0, 16, 24), s=16, wrap=0, dtype=0)
     a.update(kw)
     keep_y, oy = _ints(a["oy"]) if a["oy"] is not None else (None, 0)
     keep_x, ox = _ints(a["ox"]) if a["ox"] is not None else (None, 0)
     args = [a[k] for k in ("z", "noise", "x", "z_up", "xin", "P", "C", "h", "w", "Hc", "Wc")] + [len(a["oy"] or ()), len(a["ox"] or ()), oy, ox,
-                                                                                                 a["s"]]
-    if name.endswith("_ring"):
-        args.append(a["wrap"])
-    rc = getattr(L, name)(*args, SA, S1M, a["dtype"], None)
+                                                                                                 a["s"], a["wrap"]]
+    rc = getattr(L, NAME)(*args, SA, S1M, a["dtype"], None)
     return rc, L.sta_last_error().decode()
 
 
-@pytest.mark.parametrize("name", NAMES)
-def test_argument_rules_reach_no_launch(name):
-    """Every pointer is fake: a call that reached a launch would fault (or, without a GPU, fail with a launch error, not STA_E_ARG)."""
+@pytest.mark.parametrize("wrap", [0, 1, 2, 3])
+def test_argument_rules_reach_no_launch(wrap):
+    """Every pointer is fake: a call that reached a launch would fault (or, without a GPU, fail with a launch error, not STA_E_ARG).
+    The default grid is valid at every wrap (40 - 24 <= 16: as a ring it closes); an axis is held to the clamped rules or to the ring's."""
     from sta import lib
     L = lib.load()
     bad = [(dict(oy=None), "null pointer"), (dict(ox=None), "null pointer")]
@@ -146,19 +144,26 @@ def test_argument_rules_reach_no_launch(name):
             (dict(C=0), "C=0"), (dict(C=-4), "C=-4"),                                                         # what scatter supports
             (dict(ox=(0, 12, 24)), "ox[1]=12 is not a multiple of 8"),                                        # the grid rules, verbatim
             (dict(ox=(0, 24)), "gap between ox[0]=0 and ox[1]=24"),
-            (dict(ox=(0, 16)), "gap behind ox[1]=16"),
             (dict(ox=tuple(range(0, 136, 8)), Wc=16 + 8 * 16), "nx=17"),                                      # > STA_MAX_WINDOW_OFFSETS
             (dict(oy=tuple(range(0, 136, 8)), Hc=16 + 8 * 16), "ny=17"),
             (dict(dtype=7), "dtype 7"), (dict(dtype=2), "dtype 2")]
-    if name.endswith("_ring"):
-        bad += [(dict(wrap=4), "wrap=4"), (dict(wrap=-1), "wrap=-1"),
-                (dict(wrap=1, ox=(0, 16), Wc=40), "the ring does not close behind ox[1]=16"),
-                (dict(wrap=1, ox=(0, 16, 40), Wc=40), "ox[2]=40 is not on the wrapped axis"),
-                (dict(wrap=2, oy=(0, 8), Hc=16, dtype=7), "dtype 7")]                                        # a valid ring reaches the dtype rule
+    bad += [(dict(wrap=4), "wrap=4"), (dict(wrap=-1), "wrap=-1")]
+    if wrap & 1:                                                                                              # x closes on itself: the ring's rules
+        bad += [(dict(ox=(0, 16)), "the ring does not close behind ox[1]=16"),
+                (dict(ox=(0, 16, 40)), "ox[2]=40 is not on the wrapped axis"),
+                (dict(ox=(0, 16, 32), dtype=7), "dtype 7")]                                                   # o + s > L is allowed there
+    else:
+        bad += [(dict(ox=(0, 16)), "gap behind ox[1]=16"), (dict(ox=(0, 16, 32)), "ox[2]=32 out of range")]
+    if wrap & 2:
+        bad += [(dict(oy=(0, 16), Hc=48), "the ring does not close behind oy[1]=16"),
+                (dict(oy=(0, 8), Hc=16, dtype=7), "dtype 7")]                                                 # a valid ring reaches the dtype rule
+    else:
+        bad += [(dict(oy=(0, 8)), "oy[1]=8 out of range")]
     for kw, text in bad:
-        rc, err = _call(L, name, **kw)
-        assert rc == STA_E_ARG and text in err, (name, kw, rc, err)
-    rc, err = _call(L, name, z_up=0, xin=0, dtype=7)                                                         # the optional tensors may be NULL
+        rc, err = _call(L, **dict(dict(wrap=wrap), **kw))
+        assert rc == STA_E_ARG and text in err, (wrap, kw, rc, err)
+        assert err == "null pointer" or err.startswith(NAME[len("sta_"):] + ": "), (wrap, kw, err)            # one name whatever the wrap
+    rc, err = _call(L, wrap=wrap, z_up=0, xin=0, dtype=7)                                                         # the optional tensors may be NULL
     assert rc == STA_E_ARG and "dtype 7" in err
 
 

@@ -1,4 +1,4 @@
-"""The layout-guided hi-res fix on the MI355X: the fused upscale launch (sta_latent_upscale_step_windows and its `_ring` sibling,
+"""The layout-guided hi-res fix on the MI355X: the fused upscale launch (sta_latent_upscale_step_windows,
 csrc/sta_window.hip) against the float64 evaluation of tests/test_hires_cpu.py, under rolls of a ring, with one window and against the
 unfused entry; `DDIMSampler.hires_canvas` against the fp32 host trajectory, graph replay and the `disc_scale` keyword; the entry-point
 script with --hires end to end."""
@@ -33,7 +33,7 @@ def _launch(shape, dtype, z=None, noise=None, seed=3, **kw):
 @pytest.mark.parametrize("shape", ALL)
 def test_kernel_vs_float64(shape, dtype):
     """x and z_up elementwise within 16 x 2^-24 x (|sa| max|z| + |s1m noise|) (z_up: 16 x 2^-24 x max|z|) of the float64 evaluation with
-    the same fp32 weights; xin bit for bit sta_window_split[_ring] of the launch's own x; z_up / xin NULL leave x as it is."""
+    the same fp32 weights; xin bit for bit sta_window_split of the launch's own x; z_up / xin NULL leave x as it is."""
     from sta import canvas
     g = _grid(shape)
     assert P * C * g.Hc * g.Wc // 8 in (384, 960, 1536)        # 1.5, 3.75 and 6 blocks of 256 lanes: the last block partly idle twice

@@ -2,9 +2,9 @@
 
 One 512 x 2048 canvas (latent 64 x 256, windows of 64, stride 32: T = 7 clamped, T = 8 wrapped along x), fp16, K = 2, full-width synthetic
 UNet, NHWC trunk, no VAE.
-1. The update launch sta_latent_guide_windows[_ring] (xin and stats written, no mask), HIP events around every launch, in the same process
+1. The update launch sta_latent_guide_windows (xin and stats written, no mask), HIP events around every launch, in the same process
    and alternating with the unfused sequence it replaces: the adjoint gather in torch (an fp32 sum over the windows, rounded to the 16-bit
-   pair), sta_latent_guide on the canvas-shaped pair, sta_window_split[_ring]. Every event-timed launch sits on a floor of several us.
+   pair), sta_latent_guide on the canvas-shaped pair, sta_window_split. Every event-timed launch sits on a floor of several us.
 2. DDIM with --ddim_steps calls on the canvas: unguided `sample_canvas`, `sample_canvas` with --guided guided calls (CanvasGuidance, one
    update each, readouts at 16 x 16, eta = 0.1), and guided `sample_batch` of T 512 x 512 images (AttnGuidance) — the same UNet batch per
    call —, alternating, host clock around each call ending in a device synchronise, medians. One ordinary (graph-replayed) canvas call =
@@ -57,8 +57,8 @@ def launch_leg(name, grid):
     g = (torch.randn(2 * grid.T, 4, S_WIN, S_WIN, generator=gen, device=dev) * 1e-3).to(DT)
     step = torch.full((1,), 0.05, device=dev)
     count = torch.full((1,), float(x.numel()), device=dev)
-    variants = {"sta_latent_guide_windows" + ("_ring" if grid.wrap else ""): lambda: canvas.latent_guide_windows(g, x, step, count, grid, want_xin=True),
-                "gather (torch) + sta_latent_guide + sta_window_split" + ("_ring" if grid.wrap else ""): lambda: unfused(g, x, step, grid)}
+    variants = {"sta_latent_guide_windows": lambda: canvas.latent_guide_windows(g, x, step, count, grid, want_xin=True),
+                "gather (torch) + sta_latent_guide + sta_window_split": lambda: unfused(g, x, step, grid)}
     one, three = (fn() for fn in variants.values())
     torch.cuda.synchronize()
     # the unfused form rounds the summed gradient to 16 bits before the update: the two agree to that rounding, not bit for bit

@@ -2,8 +2,8 @@
 tools/canvas_wrap_throughput.py — DDIM, 50 steps, t_start = 25, K = 2, fixed blend weights, synthetic weights, hipGraph replay, latents only.
 
 Three figures, all from this one run.
-(a) The entry launch, timed with HIP events around it: the fused sta_vae_encode_step_windows[_ring] against sta_vae_encode_step +
-    sta_window_split[_ring] issued back to back, the two forms alternating. Every event-timed launch sits on a floor of several us, so for
+(a) The entry launch, timed with HIP events around it: the fused sta_vae_encode_step_windows against sta_vae_encode_step +
+    sta_window_split issued back to back, the two forms alternating. Every event-timed launch sits on a floor of several us, so for
     a launch of this size the ratio says little more than which side of 1 it is on; the bytes each form moves are counted from the shapes.
 (b) Seconds per `decode_canvas` trajectory (25 UNet calls of 2 T window rows) against `decode_batch` of T 512 x 512 images at the same
     t_start, which runs the same UNet batch per call: the ratio is the cost of the window work.

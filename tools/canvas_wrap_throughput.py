@@ -2,8 +2,8 @@
 runs over the seam) and clamped (T = 7), in the same run and at the settings of tools/canvas_throughput.py — DDIM, 50 steps, K = 2, fixed
 blend weights, synthetic weights, hipGraph replay, latents only.
 
-Two figures. The step launch between the UNet calls, timed with HIP events around it (sta_sampler_step_windows_ring against
-sta_sampler_step_windows; every event-timed launch sits on a floor of several us, so the ratio of the two is an UPPER bound on the ratio
+Two figures. The step launch between the UNet calls, timed with HIP events around it (sta_sampler_step_windows at wrap = 1 against
+wrap = 0; every event-timed launch sits on a floor of several us, so the ratio of the two is an UPPER bound on the ratio
 of the kernels). And the wall time of whole trajectories of the wrapped canvas against `sample_batch` of eight 512 x 512 images, which runs
 the same UNet batch of 16 rows per call: the ratio is the cost of the window work on the ring. The clamped launch is also what the
 previous build's profiles/canvas_throughput.json holds (canvas_fused_step.their_device_us_per_call), for a comparison across builds.

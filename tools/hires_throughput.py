@@ -2,8 +2,8 @@
 blend weights, synthetic weights, hipGraph replay, latents only.
 
 Two figures, both from this one run.
-(a) The entry launch, timed with HIP events around it: the fused sta_latent_upscale_step_windows[_ring] against the sequence it replaces
-    (the torch restatement of the upscale and the noising, then sta_window_split[_ring]) issued back to back, the two forms alternating, for
+(a) The entry launch, timed with HIP events around it: the fused sta_latent_upscale_step_windows against the sequence it replaces
+    (the torch restatement of the upscale and the noising, then sta_window_split) issued back to back, the two forms alternating, for
     512^2 -> 1024^2 and 512x2048 -> 1024x4096 pixels (windows 512, stride 256), clamped and wrapped along x. Median and quartiles: the
     quartiles are the run's own spread. Every event-timed launch sits on a floor of several us, which the fused form pays once and the
     sequence once per launch in it; the bytes the fused form moves are counted from the shapes. The two forms round the noising
