@@ -428,12 +428,46 @@ def xattn_forward_proj(y, wq_packed, packed, mask, coef, scale, qfrag=False, ofr
 _PROJ_STATS = {}
 
 
+def _cuda_device(device=None):
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def _capturing(device):
+    with torch.cuda.device(device):
+        return torch.cuda.is_current_stream_capturing()
+
+
+def _refuse_under_capture(buffers, what):
+    devices = {t.device for t in buffers}
+    if torch.cuda.is_available():
+        devices.add(_cuda_device())      # the current device too: refused whether or not a buffer exists yet
+    for d in devices:
+        if _capturing(d):
+            raise RuntimeError("%s: not while a stream is being captured (the fill would become a node of the graph)" % what)
+
+
+def _zero_in_place(buffers, what):
+    """Zero cached state buffers where they are (same tensors, same addresses: a captured graph that holds one keeps a valid pointer).
+    Refused while a stream is being captured — the fill would become a node of the graph — before anything is touched. The device is
+    synchronised on both sides of the fill: the buffers belong to other streams than the one that zeroes them."""
+    _refuse_under_capture(buffers, what)
+    for d in sorted({t.device for t in buffers}, key=lambda d: d.index):
+        torch.cuda.synchronize(d)
+        with torch.cuda.device(d):
+            for t in buffers:
+                if t.device == d:
+                    t.zero_()
+        torch.cuda.synchronize(d)
+
+
 def proj_stats(device=None):
     """The statistics / adaptive-switch words the head-pair kernel keeps across launches (include/sta_xattn.h: sta_xattn_fwd_proj_ex), one
     buffer per device: int32 tensor of lib.P3_STATS_WORDS words — [0] launches still sitting the optimistic softmax out, [4] / [5]
     wave-level context evaluations / fall-backs so far IN THE SAMPLE (every 8th workgroup counts), [6] launches, [7] launches that sat out. The words only steer which of two exact
     softmax paths runs, so launches of several streams may share them. Never created while a stream is being captured (the zero-fill
-    would become a node of the graph and wipe the words at every replay): a capture without a buffer runs without statistics."""
+    would become a node of the graph and wipe the words at every replay): a capture without a buffer runs without statistics.
+    reset_proj_stats() zeroes them."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     t = _PROJ_STATS.get(device)
     if t is None:
@@ -441,6 +475,12 @@ def proj_stats(device=None):
             return None
         t = _PROJ_STATS[device] = torch.zeros(_lib.P3_STATS_WORDS, dtype=torch.int32, device=device)
     return t
+
+
+def reset_proj_stats():
+    """Zero the head-pair kernel's words of every device in place: the next launch starts optimistic, with empty
+    counters. Buffers and addresses stay (captured graphs keep replaying into them). RuntimeError under stream capture."""
+    _zero_in_place(list(_PROJ_STATS.values()), "reset_proj_stats")
 
 
 def proj_stats_summary():
@@ -514,9 +554,20 @@ def to_sfrag(x):
 
 
 def reset_selfattn_optimistic_state():
-    """Forget the optimistic self-attention kernel's per-(device, stream, shape) state words (calls still sitting the optimistic loop out):
-    the next call of every shape starts optimistic again. Results never depend on the state — it only selects between two exact loops."""
-    _SA_FLAGS.clear()
+    """Zero the optimistic self-attention kernel's per-(device, stream, shape) flags buffers in place (the state words — calls still
+    sitting the optimistic loop out — and the per-workgroup flags): the next call of every shape starts optimistic again. The cache
+    keeps its entries and every buffer its address, so a captured graph that holds one replays into live memory. RuntimeError under
+    stream capture. The state selects between two loops that round differently (2 eps apart, each 4 eps of the exact softmax): the same
+    inputs give the same BITS only from the same state — what this reset restores."""
+    _zero_in_place(list(_SA_FLAGS.values()), "reset_selfattn_optimistic_state")
+
+
+def reset_adaptive_state():
+    """Both resets: every device-side word that lets an earlier call steer a later one (level-0 self-attention, head-pair cross-attention)
+    back to zero, in place. After it a call gives the bits it gives in a fresh process."""
+    _refuse_under_capture(list(_SA_FLAGS.values()) + list(_PROJ_STATS.values()), "reset_adaptive_state")      # in front of BOTH sets
+    reset_selfattn_optimistic_state()
+    reset_proj_stats()
 
 
 SELFATTN_OPTIMISTIC = os.environ.get("STA_SELFATTN_OPTIMISTIC", "1") != "0"      # (env: A/B in tools/sa_opt_bench_ab.sh) self-attention at level 0 (both 16-bit types) through sta_selfattn_fwd_optimistic (profiles/r05_selfattn.md)
